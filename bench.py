@@ -13,6 +13,7 @@ Nothing is skipped, cached across steps or run at reduced size.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...      (no launcher: bench.py starts torch.distributed.run itself as a CHILD process before
                                        anything touches the GPU and relays its output and exit code)
+    python bench.py ... --dump-outputs DIR   (also writes the last timed step's outputs to DIR/*.npy: see dump_outputs)
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the bf16 MFMA GEMM): algorithmic
 flops per launch / average launch duration, measured with HIP events on the launch stream during
@@ -404,6 +405,32 @@ def extra_cases(model, vq, opt, dev, args, steps=5):
     return out
 
 
+def dump_outputs(out_dir, last, model, opt, n_hidden=1 << 20, n_per_param=8192, seed=0):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files (about 11 MB at the default shape), so that two
+    builds can be compared output for output on the same seeded inputs:
+      loss.npy           float64 []           the t2i loss
+      image_tokens.npy   float64 [B, 256]     MAGVITv2's image tokens (ids in the LLM vocabulary, exact)
+      hidden_sample.npy  float32 [n_hidden]   final-norm hidden states behind the (lazy) logits, at fixed seeded positions
+      params_sample.npy  float32 [...]        every parameter after the AdamW update, up to n_per_param fixed seeded
+                                              entries each, in named_parameters() order"""
+    import numpy as np
+    opt.synchronize()
+    torch.cuda.synchronize()
+    g = torch.Generator().manual_seed(seed)
+
+    def sample(t, n):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > n:
+            flat = flat[torch.randint(flat.numel(), (n,), generator=g).sort().values.to(flat.device)]
+        return flat.float().cpu()
+    arrays = {"loss": last["loss"].double().cpu(), "image_tokens": last["codes"].double().cpu(),
+              "hidden_sample": sample(last["hidden"], n_hidden),
+              "params_sample": torch.cat([sample(p, n_per_param) for _, p in model.named_parameters()])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+
+
 RCCL_LOG = None            # NCCL_DEBUG_FILE of this rank (set before init_process_group at N > 1 on the nccl backend)
 
 
@@ -550,7 +577,10 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary cases (pt1 mixed batch, real mask ratios, SFT, DPO, MaskGIT)")
     ap.add_argument("--no-ar", action="store_true", help="skip the AR image-token generation measurement (second half of the metric)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -607,17 +637,20 @@ def main():
     images = torch.rand(B, 3, 256, 256, device=dev, generator=g) * 2 - 1
     text = torch.randint(0, 151643, (B, args.text_len), device=dev, generator=g)
     losses = []
+    last = {}                                                       # the latest step's outputs, kept for --dump-outputs
 
     def step():
         codes = vq.get_code(images) + TEXT_VOCAB
         masked = torch.full_like(codes, MASK_ID)                    # mask_prob = 1: every image token is a label
         ids, labels, mask = t2i_rows(ops, text, masked, codes)
-        _, l_t2i, _, _ = model(input_ids=ids, attention_mask=mask, labels=labels, batch_size_t2i=B,
-                               max_seq_length=args.text_len + 1, num_vq_tokens=NVQ)
+        logits, l_t2i, _, _ = model(input_ids=ids, attention_mask=mask, labels=labels, batch_size_t2i=B,
+                                    max_seq_length=args.text_len + 1, num_vq_tokens=NVQ)
         l_t2i.backward()
         opt.step()
         opt.zero_grad(set_to_none=True)
         losses.append(l_t2i.detach())
+        if args.dump_outputs:
+            last.update(loss=losses[-1], codes=codes, hidden=logits.hn)
 
     def barrier():
         torch.cuda.synchronize()
@@ -661,6 +694,8 @@ def main():
     w0 = time.time()
     dt, acct = timed_block(args.steps)
     power = sampler.report(w0, time.time()) if sampler is not None else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model, opt)             # before any later step changes the weights
     exchange = None
     if world > 1:
         # proof that the exchange's communicator spans N ranks: a SUM of ones on the process group the buckets move through

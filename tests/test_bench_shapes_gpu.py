@@ -155,3 +155,38 @@ def test_head_and_cross_entropy_full_vocabulary_matches_oracle(dev):
     with torch.no_grad():
         lo32 = qwen2_ref.unigen_forward_ref(lm, seq, mask, None, autocast=False)[:, -(n + 1):-1]
     fp32_yardstick("V=159867 head", got, lo[:, -(n + 1):-1], lo32)
+
+
+def test_bench_dump_outputs_holds_the_last_timed_step(dev, tmp_path):
+    """bench.py --dump-outputs DIR (the headline step, the other cases off): the line reports exactly --steps timed steps, DIR holds
+    float32 / float64 arrays of at most 64 MB in all whose loss is the line's last loss, and a second run with the same arguments
+    sees the same inputs: identical image tokens and the same loss.  Hidden states and weights after three AdamW updates carry
+    run-to-run noise of the gradient reductions (1.0e-2 relative measured on the hidden states), so they are checked for shape only."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        cmd = [sys.executable, bench, "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-roofline", "--no-ar",
+               "--no-extra", "--dump-outputs", str(out)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
+        line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        arrs = {p.stem: np.load(p) for p in out.glob("*.npy")}
+        assert set(arrs) == {"loss", "image_tokens", "hidden_sample", "params_sample"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["image_tokens"].shape == (16, 256) and arrs["hidden_sample"].size == 1 << 20
+        assert np.isfinite(arrs["hidden_sample"]).all() and np.isfinite(arrs["params_sample"]).all()
+        assert round(float(arrs["loss"]), 4) == line["loss_first_last"][1]
+        runs.append(arrs)
+    a, b = runs
+    assert np.array_equal(a["image_tokens"], b["image_tokens"])
+    assert abs(float(a["loss"]) - float(b["loss"])) <= 1e-3 * abs(float(b["loss"]))
+    assert a["params_sample"].shape == b["params_sample"].shape

@@ -164,6 +164,14 @@ def test_bench_self_launch_refuses_more_ranks_than_gpus():
         assert r.returncode != 0 and "one GPU per rank" in (r.stderr + r.stdout)
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    """`ms_per_step` is the timed block over `--steps`: zero steps is refused by the argument check, before any work."""
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dump-outputs", "unused"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr[-2000:]
+
+
 def test_bench_power_report_reads_the_busy_card_and_survives_a_cut_off_line(tmp_path):
     """bench.py's `power` object (round 4): from the sampler's file -- two cards of which one ran the steps, a running-average ramp at the
     start of the window, samples outside the window, a last line cut off by the terminate -- the report is the busy card's last two
