@@ -256,6 +256,39 @@ int ug_decode_sw_head(const float* h, const float* pend, int64_t ld_pend, float*
 /* finish a split-K fp32 accumulation: mode 0: out_bf16 = bf16(acc + bias); mode 1: resid += bf16round(acc) */
 int ug_skinny_finish(const float* acc, const void* bias, void* out_bf16, float* resid, int64_t M, int64_t N,
                      int mode, hipStream_t stream);
+/* Ordered (deterministic) decode forms: the split-K launches above sum partial products with fp32 atomics, so their results depend on
+ * the order workgroups arrive in.  These entry points write every k-slice's partial tile into a SLOT of its own by plain stores (no
+ * atomics, no clears; every slot element has exactly one writer) and the consumer sums the slots in ONE fixed order -- ascending slot
+ * index, in fp32 -- before the rounding the default form applies at the same point.  Same step, bit-reproducible run to run and between
+ * eager and captured replay.  Slot p of a [slots][rows][ld] buffer starts p * rows * ld floats in, unless a stride is given.
+ *   ug_gemv_bf16_ord       part[s * part_stride + r * ldpart + n] = sum_{k in slice s} x[r][k] W[n][k]; slices of 256 k (ceil(K / 256)
+ *                          slots; one slot for K < 256).  R <= 32.
+ *   ug_skinny_finish_ord   v = sum_{p < nparts} parts[p * part_stride + m * N + n] (ascending p), then exactly one of:
+ *                          out_bf16 = bf16(v + bias) | resid += bf16round(v) | out_f32 = v.
+ * The single-writer decode layer (R <= 16, ug_decode_sw_supported() sizes; K / 1792 == 5 k-blocks for the down projection):
+ *   ug_decode_gemv_resid_norm_ord  q/k/v.  As ug_decode_gemv_resid_norm, with the pending term = bf16round(sum_{p < npend} pend[p][R]
+ *                          [ld_pending]) (the previous layer's down k-block slots; npend 0 -- layer 0 -- or 5); the projection lands in
+ *                          part[slab][R][ldpart] (ceil(K / 256) slabs) and the row sums of squares of slab s in ss_part[s * 32 + r].
+ *   ug_attn_decode_fused_ord   as ug_attn_decode_fused, fed by those slots (nparts == 6: hidden 1536): q/k/v and the statistics are
+ *                          the ascending-slab sums, then rstd, bias and RoPE as in the default form.
+ *   ug_decode_sw_kblock_ord    down projection: k-block b's partial (its seven slabs pre-reduced in LDS in wave order) is stored into
+ *                          part[b][R][ldpart].
+ *   ug_decode_finish_resid_norm_ord  x += bf16round(sum_{p < nparts} parts[p][rows][ldp]); xn = bf16(rmsnorm(x) * w) if xn is given. */
+int ug_gemv_bf16_ord(const void* x, int64_t ldx, int64_t R, const void* W, int64_t ldw, float* part, int64_t ldpart, int64_t part_stride,
+                     int64_t N, int64_t K, hipStream_t stream);
+int ug_skinny_finish_ord(const float* parts, int64_t nparts, int64_t part_stride, const void* bias, void* out_bf16, float* out_f32,
+                         float* resid, int64_t M, int64_t N, hipStream_t stream);
+int ug_decode_gemv_resid_norm_ord(const float* x_in, const float* pend_parts, int64_t ld_pending, int64_t npend, const float* norm_w,
+                                  float* x_out, float* ss_part, int64_t R, const void* W, int64_t ldw, float* part, int64_t ldpart,
+                                  int64_t N, int64_t K, hipStream_t stream);
+int ug_attn_decode_fused_ord(const float* qkv_part, int64_t ldpart, int64_t nparts, const float* ss_part, float eps, int64_t norm_cols,
+                             const void* bias, const float* cos_tab, const float* sin_tab, const int* pos_dev, void* cache_k,
+                             void* cache_v, const uint8_t* key_valid, void* o, int64_t ldo, int64_t rows, int H, int HKV, int head_dim,
+                             int64_t Tmax, int64_t max_pos, float scale, hipStream_t stream);
+int ug_decode_sw_kblock_ord(const void* x, int64_t ldx, int64_t R, const void* W, int64_t ldw, float* part, int64_t ldpart, int64_t N,
+                            int64_t K, hipStream_t stream);
+int ug_decode_finish_resid_norm_ord(const float* parts, int64_t ldp, int64_t nparts, float* x, const float* w, void* xn, int64_t rows,
+                                    int64_t cols, float eps, int* pos_inc, int* len_inc, hipStream_t stream);
 
 /* ---- device-side prompt / mask assembly --------------------------------- */
 /* replaces the per-sample Python loops of UniversalPromptingQwen2.t2i_prompt (training/prompting_utils.py:59-111, prompt

@@ -171,6 +171,9 @@ constexpr int ADF_WAVES = 8;            // one 64-key chunk per wave up to 512 k
 // the new token as one more (m, l, O) partial.
 // (Argument order: the first 14 dwords are what the kernel's first loads need -- with -mllvm -amdgpu-kernarg-preload-count=16 hipcc preloads
 // that many, they arrive in SGPRs with the wave; the rest comes by one batch of scalar loads.)
+// NQP > 0: the ORDERED form (deterministic decode, ug_attn_decode_fused_ord): acc_qkv holds NQP k-slab partial slots [NQP][R][lda] and
+// ss NQP slots of 32 row sums of squares; the prologue requests all of them with its first loads and sums them in ascending slab order.
+template <int NQP = 0>
 __global__ __launch_bounds__(64 * ADF_WAVES) void attn_decode_fused_kernel(
     const float* __restrict__ acc_qkv, const float* __restrict__ ss, const int* __restrict__ pos_dev, bf16_t* __restrict__ ck,
     bf16_t* __restrict__ cv, int R, int HKV, int H, int lda, int Tmax, int max_pos,
@@ -242,6 +245,17 @@ __global__ __launch_bounds__(64 * ADF_WAVES) void attn_decode_fused_kernel(
     ld4(ssr, ss + r);
     ld4(a1, arow + col0 + lane); ld4(a2, arow + col0 + lane + DHD / 2);
   }
+  float pss[NQP > 1 ? NQP - 1 : 1], pa1[NQP > 1 ? NQP - 1 : 1], pa2[NQP > 1 ? NQP - 1 : 1];     // ordered: slots 1 .. NQP - 1
+  if constexpr (NQP > 1) {
+    if (wave < 3) {
+#pragma unroll
+      for (int p = 1; p < NQP; ++p) {
+        const float* prow = arow + (int64_t)p * R * lda;
+        ld4(pss[p - 1], ss + p * 32 + r);
+        ld4(pa1[p - 1], prow + col0 + lane); ld4(pa2[p - 1], prow + col0 + lane + DHD / 2);
+      }
+    }
+  }
   asm volatile("" ::"s"(Tmax), "s"(max_pos), "s"(bias), "s"(cs), "s"(sn), "s"(key_valid), "s"(o), "s"(ldo), "s"(__float_as_int(eps)),
                "s"(norm_cols), "s"(__float_as_int(scale)));  // batch 2
   wait_lgkm0();                                            // (the position word; the batch above is behind the same counter)
@@ -259,6 +273,13 @@ __global__ __launch_bounds__(64 * ADF_WAVES) void attn_decode_fused_kernel(
   if (wave < 3) {
     if (has_chunk) wait_vm<32>(); else wait_vm<0>();       // the prologue's loads are older than the chunk's 16 + 16
     tie(ssr); tie(a1); tie(a2); tie(bb1); tie(bb2); tie(rc); tie(rsn);
+    if constexpr (NQP > 1) {
+#pragma unroll
+      for (int p = 0; p < NQP - 1; ++p) {                  // ascending slab order, fp32
+        tie(pss[p]); tie(pa1[p]); tie(pa2[p]);
+        ssr += pss[p]; a1 += pa1[p]; a2 += pa2[p];
+      }
+    }
     const float b1 = bf2f((bf16_t)bb1), b2 = bf2f((bf16_t)bb2);
     float x1, x2;
     {
@@ -584,6 +605,7 @@ struct DecodeIn {
   const float* gu; int64_t ld_gu; const float* ss_in; float eps; int norm_cols;                              // SWIGLU
   float* zero0; float* zero1; float* ss_zero;                                                               // clears
   int n0_4, per0, n1_4, per1;           // float4 counts and every workgroup's share of them (set_clear_shares, on the host)
+  int part_slot;                        // ordered forms: floats between two k-slabs' partial tiles (gemv_ring_kernel)
 };
 
 // Round 5: everything uniform is 32-bit and comes from the host.  The round-4 form divided int64 counts by the grid size in every
@@ -673,7 +695,9 @@ struct TileAddr {
 };
 
 // XIN_BF16: one wave per workgroup (see above).  Grid (k-slabs, groups of KW weight-row groups).
-template <int RB, int KW>
+// ORD (deterministic decode): no clears, and the wave's partial tile is STORED into k-slab blockIdx.x's slot
+// acc[blockIdx.x * f.part_slot + r * sr + n * sn] instead of added: one writer per slot element, the consumer sums the slots in order.
+template <int RB, int KW, bool ORD = false>
 __global__ __launch_bounds__(64) void gemv_ring_kernel(const bf16_t* __restrict__ x, int ldx, int R, const bf16_t* __restrict__ W,
                                                        int ldw, float* __restrict__ acc, int sr, int sn, int N, int K, DecodeIn f) {
   __shared__ __attribute__((aligned(1024))) char tile[2][8192];
@@ -682,7 +706,7 @@ __global__ __launch_bounds__(64) void gemv_ring_kernel(const bf16_t* __restrict_
   const int kbase = blockIdx.x * 256;
   const bool whole = (N & 15) == 0;                                 // every 16-row group is complete: no per-row clamp
   // the clears this launch carries go out first: stores behind the loads would sit between them in the memory queue
-  decode_clear(f, lane, linear_block());
+  if constexpr (!ORD) decode_clear(f, lane, linear_block());
   TileAddr ta;
   ta.init(lane, kbase, K, ldw);
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(tile[0]));
@@ -737,12 +761,16 @@ __global__ __launch_bounds__(64) void gemv_ring_kernel(const bf16_t* __restrict_
       }
     const int n = (grp0 + t) * 16 + row;
     float* ap = acc + __umul24(n, sn);
+    if constexpr (ORD) ap += (int64_t)blockIdx.x * f.part_slot;
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int r = rb * 16 + g * 4 + j;
-        if (r < R && n < N) atomicAdd(ap + __umul24(r, sr), d[rb][j]);
+        if (r < R && n < N) {
+          if constexpr (ORD) ap[__umul24(r, sr)] = d[rb][j];
+          else atomicAdd(ap + __umul24(r, sr), d[rb][j]);
+        }
       }
     }
   }
@@ -761,13 +789,21 @@ __global__ __launch_bounds__(64) void gemv_ring_kernel(const bf16_t* __restrict_
 // decode_operand_load; p1 = the statistics slot for XIN_SWIGLU); built with kernarg preload (Makefile) they arrive in SGPRs with the wave.
 // CLR = the launch carries clears (its first memory operations, so their arguments are fetched up front); a launch without them
 // fetches the rest of its arguments behind the first tiles' requests.
-template <int RB, int KW, int XIN, int NW, bool CLR>
+// NPEND >= 0: the ORDERED form of the XIN_RESID_NORM launch (deterministic decode, ug_decode_gemv_resid_norm_ord).  The pending term is
+// NPEND partial slots p1[p][R][ld1] (the k-block partials of the previous down projection; 0 = none), summed in ascending p in fp32 and
+// then rounded to bf16 like the raw accumulator; the workgroup's partial tile is STORED into k-slab `slab`'s slot acc[slab][R][sr], and
+// weight group 0's workgroups store their slab's row sums of squares (waves summed in ascending order through LDS) into ss_out[slab][32].
+// No float atomics, no clears.
+template <int RB, int KW, int XIN, int NW, bool CLR, int NPEND = -1>
 __global__ __launch_bounds__(64 * NW) void gemv_ring4_kernel(const float* __restrict__ p0, const float* __restrict__ p1, const float* __restrict__ nw,
                                                              const bf16_t* __restrict__ W, int R, int K, int ld1, int ldw, int N, int nslabs,
                                                              float* __restrict__ acc, int sr, int sn, DecodeIn f) {
   __shared__ __attribute__((aligned(1024))) char tile[NW][2][8192];
   __shared__ __attribute__((aligned(16))) bf16x8_t frag[RB][8][64];
   constexpr int UPW = (8 + NW - 1) / NW;           // k-steps of the operand each wave converts
+  constexpr bool ORD = NPEND >= 0;
+  static_assert(!ORD || (XIN == XIN_RESID_NORM && !CLR), "the ordered form is the q/k/v launch, which carries no clears");
+  __shared__ float ssl[ORD ? NW : 1][RB * 16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, row = lane & 15;
   const int slab = blockIdx.x + 8 * blockIdx.z, chunk = blockIdx.y;
   asm volatile("" ::"s"(p0), "s"(p1), "s"(nw), "s"(W), "s"(R), "s"(K), "s"(ld1), "s"(ldw), "s"(N), "s"(nslabs));      // batch 1 (vmem_asm.h, argument hoisting)
@@ -792,6 +828,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_ring4_kernel(const float* __rest
   // the ring's third tile could only be requested after that.  Now the image is built as soon as the operand's own round trip ends.
   // operand loads of this wave's k-steps go out first, then the weight DMA
   f32x4_t a[RB][UPW][2], b[RB][UPW][2], w[RB][UPW][2];
+  f32x4_t pp[ORD && NPEND > 0 ? NPEND : 1][RB][UPW][2];       // ORD: the pending partial slots
   float rs[RB];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
@@ -801,7 +838,19 @@ __global__ __launch_bounds__(64 * NW) void gemv_ring4_kernel(const float* __rest
 #pragma unroll
     for (int uu = 0; uu < UPW; ++uu) {
       const int u = min(wave + uu * NW, 7);
-      decode_operand_load<XIN>(p0, p1, ld1, nw, ar, min(kbase + u * 32, K - 32) + g * 8, K, a[rb][uu], b[rb][uu], w[rb][uu]);
+      const int k0 = min(kbase + u * 32, K - 32) + g * 8;
+      if constexpr (ORD) {
+        const float* xp = p0 + (__umul24(ar, K) + k0);
+        ld16(a[rb][uu][0], xp); ld16(a[rb][uu][1], xp + 4);
+        ld16(w[rb][uu][0], nw + k0); ld16(w[rb][uu][1], nw + k0 + 4);
+#pragma unroll
+        for (int p = 0; p < NPEND; ++p) {
+          const float* q = p1 + ((p * R + ar) * ld1 + k0);
+          ld16(pp[p][rb][uu][0], q); ld16(pp[p][rb][uu][1], q + 4);
+        }
+      } else {
+        decode_operand_load<XIN>(p0, p1, ld1, nw, ar, k0, K, a[rb][uu], b[rb][uu], w[rb][uu]);
+      }
     }
   }
   TileAddr ta;
@@ -827,8 +876,18 @@ __global__ __launch_bounds__(64 * NW) void gemv_ring4_kernel(const float* __rest
     if constexpr (XIN == XIN_SWIGLU) tie(rs[rb]);
 #pragma unroll
     for (int uu = 0; uu < UPW; ++uu) {
-      tie(a[rb][uu][0]); tie(a[rb][uu][1]); tie(b[rb][uu][0]); tie(b[rb][uu][1]);
-      if constexpr (XIN == XIN_RESID_NORM) { tie(w[rb][uu][0]); tie(w[rb][uu][1]); }
+      if constexpr (ORD) {
+        tie(a[rb][uu][0]); tie(a[rb][uu][1]); tie(w[rb][uu][0]); tie(w[rb][uu][1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {              // pending term: slots summed in ascending order (bf16-rounded in decode_operand_make)
+          b[rb][uu][h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int p = 0; p < NPEND; ++p) { tie(pp[p][rb][uu][h]); b[rb][uu][h] = p == 0 ? pp[0][rb][uu][h] : b[rb][uu][h] + pp[p][rb][uu][h]; }
+        }
+      } else {
+        tie(a[rb][uu][0]); tie(a[rb][uu][1]); tie(b[rb][uu][0]); tie(b[rb][uu][1]);
+        if constexpr (XIN == XIN_RESID_NORM) { tie(w[rb][uu][0]); tie(w[rb][uu][1]); }
+      }
     }
   }
   float ssq_row[RB];
@@ -880,12 +939,16 @@ __global__ __launch_bounds__(64 * NW) void gemv_ring4_kernel(const float* __rest
       }
     const int n = (grp0 + t) * 16 + row;
     float* ap = acc + __umul24(n, sn);
+    if constexpr (ORD) ap += (int64_t)slab * R * sr;
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int r = rb * 16 + g * 4 + j;
-        if (r < R && n < N) atomicAdd(ap + __umul24(r, sr), d[rb][j]);
+        if (r < R && n < N) {
+          if constexpr (ORD) ap[__umul24(r, sr)] = d[rb][j];
+          else atomicAdd(ap + __umul24(r, sr), d[rb][j]);
+        }
       }
     }
   }
@@ -904,12 +967,93 @@ __global__ __launch_bounds__(64 * NW) void gemv_ring4_kernel(const float* __rest
             *reinterpret_cast<f32x4_t*>(op + 4) = a[rb][uu][1];
           }
         }
-        if (live && g == 0 && f.ss_out && ssq_row[rb] != 0.f) atomicAdd(f.ss_out + rb * 16 + row, ssq_row[rb]);
+        if constexpr (ORD) { if (g == 0) ssl[wave][rb * 16 + row] = ssq_row[rb]; }
+        else if (live && g == 0 && f.ss_out && ssq_row[rb] != 0.f) atomicAdd(f.ss_out + rb * 16 + row, ssq_row[rb]);
+      }
+      if constexpr (ORD) {
+        __syncthreads();
+        const int r = threadIdx.x;
+        if (r < RB * 16 && r < R) {
+          float s = ssl[0][r];
+#pragma unroll
+          for (int ww = 1; ww < NW; ++ww) s += ssl[ww][r];
+          f.ss_out[slab * 32 + r] = s;
+        }
       }
     }
   }
 }
 
+// ---- ordered finishers (deterministic decode): partial slots summed in ascending slot order in fp32, then the default form's rounding
+// parts[p * slot + ...], p < np.  out_bf16 = bf16(sum + bias) | resid += bf16round(sum) | out_f32 = sum  (whichever is given)
+__global__ __launch_bounds__(256) void skinny_finish_ord_kernel(const float* __restrict__ parts, int np, int64_t slot,
+                                                                const bf16_t* __restrict__ bias, bf16_t* __restrict__ out_bf16,
+                                                                float* __restrict__ out_f32, float* __restrict__ resid, int64_t total, int N) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    float v = parts[i];
+    for (int p = 1; p < np; ++p) v += parts[p * slot + i];
+    if (out_bf16) {
+      if (bias) v += bf2f(bias[i % N]);
+      out_bf16[i] = f2bf(v);
+    } else if (resid) {
+      resid[i] += bf2f(f2bf(v));
+    } else {
+      out_f32[i] = v;
+    }
+  }
+}
+
+// finish_resid_norm_kernel fed by np partial slots parts[p][rows][ldp] (the last layer's down k-blocks): x[r] += bf16round(sum_p parts[p][r])
+// in place; xn[r] = bf16(rmsnorm(x[r]) * w) when xn is given.  Same per-lane statistics order as rmsnorm_fwd_kernel.
+template <int MAXV>
+__global__ __launch_bounds__(64) void finish_resid_norm_ord_kernel(const float* __restrict__ parts, int ldp, int np, float* __restrict__ x,
+                                                                   const float* __restrict__ w, bf16_t* __restrict__ xn, int cols, float eps,
+                                                                   int* __restrict__ pos_inc, int* __restrict__ len_inc) {
+  const int row = blockIdx.x, lane = threadIdx.x, nv = cols >> 2;
+  const int64_t slot = (int64_t)gridDim.x * ldp;
+  float4* xr = reinterpret_cast<float4*>(x + (int64_t)row * cols);
+  const float4* wr = reinterpret_cast<const float4*>(w);
+  float4 v[MAXV], gw[MAXV], dl[MAXV];
+#pragma unroll
+  for (int c = 0; c < MAXV; ++c) {
+    const int i = lane + c * 64;
+    if (i < nv) { v[c] = xr[i]; gw[c] = wr[i]; dl[c] = reinterpret_cast<const float4*>(parts + (int64_t)row * ldp)[i]; }
+  }
+  for (int p = 1; p < np; ++p) {
+    const float4* pr = reinterpret_cast<const float4*>(parts + p * slot + (int64_t)row * ldp);
+#pragma unroll
+    for (int c = 0; c < MAXV; ++c) {
+      const int i = lane + c * 64;
+      if (i < nv) { const float4 t = pr[i]; dl[c].x += t.x; dl[c].y += t.y; dl[c].z += t.z; dl[c].w += t.w; }
+    }
+  }
+  float ss = 0.f;
+#pragma unroll
+  for (int c = 0; c < MAXV; ++c) {
+    const int i = lane + c * 64;
+    if (i < nv) {
+      v[c].x += bf2f(f2bf(dl[c].x)); v[c].y += bf2f(f2bf(dl[c].y));
+      v[c].z += bf2f(f2bf(dl[c].z)); v[c].w += bf2f(f2bf(dl[c].w));
+      xr[i] = v[c];
+      ss += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
+    }
+  }
+  if (xn) {
+    ss = wave_sum(ss);
+    const float rs = rsqrtf(ss / (float)cols + eps);
+#pragma unroll
+    for (int c = 0; c < MAXV; ++c) {
+      const int i = lane + c * 64;
+      if (i < nv) {
+        uint2 o;
+        o.x = pack_bf2(gw[c].x * (v[c].x * rs), gw[c].y * (v[c].y * rs));
+        o.y = pack_bf2(gw[c].z * (v[c].z * rs), gw[c].w * (v[c].w * rs));
+        reinterpret_cast<uint2*>(xn + (int64_t)row * cols)[i] = o;
+      }
+    }
+  }
+  if (pos_inc && blockIdx.x == 0 && threadIdx.x == 0) { ++*pos_inc; ++*len_inc; }
+}
 
 template <int RB>
 void launch_gemv(int U, dim3 grid, hipStream_t st, const bf16_t* x, int64_t ldx, int R, const bf16_t* W, int64_t ldw,
@@ -1134,7 +1278,7 @@ extern "C" int ug_attn_decode_fused(const float* acc_qkv, int64_t ldacc, const f
   // (XCD-aware placement: see the kernel)
   const dim3 grid(8u, (unsigned)(H / HKV), (unsigned)((rows * HKV + 7) / 8));
   UG_REQUIRE(ldacc > 0 && ldacc < (1ll << 31), "ug_attn_decode_fused: ldacc out of range");
-  hipLaunchKernelGGL(attn_decode_fused_kernel, grid, dim3(64 * ADF_WAVES), 0, st, acc_qkv, ss_in, pos_dev, (bf16_t*)cache_k,
+  hipLaunchKernelGGL(attn_decode_fused_kernel<>, grid, dim3(64 * ADF_WAVES), 0, st, acc_qkv, ss_in, pos_dev, (bf16_t*)cache_k,
                      (bf16_t*)cache_v, (int)rows, HKV, H, (int)ldacc, (int)Tmax, (int)max_pos, (const bf16_t*)bias, cos_tab, sin_tab,
                      key_valid, (bf16_t*)o, ldo, eps, (int)norm_cols, scale);
   UG_CHECK_LAUNCH("ug_attn_decode_fused");
@@ -1149,5 +1293,100 @@ extern "C" int ug_skinny_finish(const float* acc, const void* bias, void* out_bf
   hipLaunchKernelGGL(skinny_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, acc, (const bf16_t*)bias, (bf16_t*)out_bf16, resid,
                      total, (int)N, mode);
   UG_CHECK_LAUNCH("ug_skinny_finish");
+  return UG_OK;
+}
+
+// ------------------------------------------------------------------ ordered (deterministic) decode forms: include/unigen_hip.h
+extern "C" int ug_gemv_bf16_ord(const void* x, int64_t ldx, int64_t R, const void* W, int64_t ldw, float* part, int64_t ldpart,
+                                int64_t part_stride, int64_t N, int64_t K, hipStream_t st) {
+  UG_REQUIRE(R > 0 && R <= 32 && N > 0 && K > 0 && K % 32 == 0 && x && W && part, "ug_gemv_bf16_ord: need 1 <= rows <= 32 and K %% 32 == 0 (rows=%ld K=%ld)",
+             (long)R, (long)K);
+  UG_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ug_aligned16(x) && ug_aligned16(W) && ldpart >= N && part_stride >= R * ldpart,
+             "ug_gemv_bf16_ord: 16-byte aligned rows, ldpart >= N and slots of rows x ldpart required");
+  const int64_t groups = (N + 15) / 16, nslabs = (K + 255) / 256;
+  UG_REQUIRE(part_stride * nslabs < (1ll << 31) && ldx < (1 << 24), "ug_gemv_bf16_ord: partial slots beyond 2^31 floats");
+  const bf16_t* xb = (const bf16_t*)x;
+  const bf16_t* wb = (const bf16_t*)W;
+  // one wave per (k-slab, 16 weight rows): slot = k-slab (a contraction shorter than 256 is one slab; the tile loads clamp to K and the
+  // steps past K are skipped)
+  UG_RING_RANGES("ug_gemv_bf16_ord", N, K, ldw, ldpart, 1);
+  DecodeIn f{};
+  f.part_slot = (int)part_stride;
+  const dim3 grid((unsigned)nslabs, (unsigned)groups);
+  if (R <= 16) hipLaunchKernelGGL((gemv_ring_kernel<1, 1, true>), grid, dim3(64), 0, st, xb, (int)ldx, (int)R, wb, (int)ldw, part, (int)ldpart, 1, (int)N, (int)K, f);
+  else hipLaunchKernelGGL((gemv_ring_kernel<2, 1, true>), grid, dim3(64), 0, st, xb, (int)ldx, (int)R, wb, (int)ldw, part, (int)ldpart, 1, (int)N, (int)K, f);
+  UG_CHECK_LAUNCH("ug_gemv_bf16_ord");
+  return UG_OK;
+}
+
+extern "C" int ug_skinny_finish_ord(const float* parts, int64_t nparts, int64_t part_stride, const void* bias, void* out_bf16, float* out_f32,
+                                    float* resid, int64_t M, int64_t N, hipStream_t st) {
+  UG_REQUIRE(parts && M > 0 && N > 0 && nparts > 0 && nparts < (1 << 20) && part_stride >= M * N &&
+                 (out_bf16 != nullptr) + (out_f32 != nullptr) + (resid != nullptr) == 1 && (bias == nullptr || out_bf16 != nullptr),
+             "ug_skinny_finish_ord: bad args (one output of out_bf16 / out_f32 / resid; slots of at least rows x N floats)");
+  const int64_t total = M * N;
+  int64_t g = (total + 255) / 256; if (g > 1024) g = 1024;
+  hipLaunchKernelGGL(skinny_finish_ord_kernel, dim3((unsigned)g), dim3(256), 0, st, parts, (int)nparts, part_stride, (const bf16_t*)bias,
+                     (bf16_t*)out_bf16, out_f32, resid, total, (int)N);
+  UG_CHECK_LAUNCH("ug_skinny_finish_ord");
+  return UG_OK;
+}
+
+extern "C" int ug_decode_gemv_resid_norm_ord(const float* x_in, const float* pend_parts, int64_t ld_pending, int64_t npend, const float* norm_w,
+                                             float* x_out, float* ss_part, int64_t R, const void* W, int64_t ldw, float* part, int64_t ldpart,
+                                             int64_t N, int64_t K, hipStream_t st) {
+  UG_REQUIRE(R > 0 && R <= 16 && K >= 256 && K % 32 == 0 && N > 0 && W && ldw % 8 == 0 && ug_aligned16(W) && part && ldpart >= N,
+             "ug_decode_gemv_resid_norm_ord: need 1 <= rows <= 16, K >= 256, K %% 32 == 0 (rows=%ld K=%ld)", (long)R, (long)K);
+  UG_REQUIRE(npend == 0 || npend == 5, "ug_decode_gemv_resid_norm_ord: built for 0 or 5 pending k-block slots (got %ld)", (long)npend);
+  UG_REQUIRE(x_in && norm_w && x_out && ss_part && x_in != x_out && (npend == 0 || pend_parts) && ld_pending % 4 == 0 && ug_aligned16(x_in) &&
+                 ug_aligned16(pend_parts) && ug_aligned16(norm_w) && ug_aligned16(x_out),
+             "ug_decode_gemv_resid_norm_ord: bad args (x_in and x_out must be distinct, 16-byte aligned fp32 buffers)");
+  UG_RING_RANGES("ug_decode_gemv_resid_norm_ord", N, K, ldw, ldpart, 1);
+  const int64_t nslabs = (K + 255) / 256, groups = (N + 15) / 16;
+  UG_REQUIRE(npend * R * ld_pending < (1ll << 31) && nslabs * R * ldpart < (1ll << 31) && ld_pending < (1 << 24),
+             "ug_decode_gemv_resid_norm_ord: partial slots beyond 2^31 floats");
+  DecodeIn f{};
+  f.x_out = x_out; f.ss_out = ss_part;
+  const dim3 grid((unsigned)nslabs, (unsigned)((groups + 3) / 4));          // four waves x one 16-row group per workgroup
+  if (npend == 0)
+    hipLaunchKernelGGL((gemv_ring4_kernel<1, 1, XIN_RESID_NORM, 4, false, 0>), grid, dim3(256), 0, st, x_in, pend_parts, norm_w, (const bf16_t*)W,
+                       (int)R, (int)K, (int)ld_pending, (int)ldw, (int)N, (int)nslabs, part, (int)ldpart, 1, f);
+  else
+    hipLaunchKernelGGL((gemv_ring4_kernel<1, 1, XIN_RESID_NORM, 4, false, 5>), grid, dim3(256), 0, st, x_in, pend_parts, norm_w, (const bf16_t*)W,
+                       (int)R, (int)K, (int)ld_pending, (int)ldw, (int)N, (int)nslabs, part, (int)ldpart, 1, f);
+  UG_CHECK_LAUNCH("ug_decode_gemv_resid_norm_ord");
+  return UG_OK;
+}
+
+extern "C" int ug_attn_decode_fused_ord(const float* qkv_part, int64_t ldpart, int64_t nparts, const float* ss_part, float eps, int64_t norm_cols,
+                                        const void* bias, const float* cos_tab, const float* sin_tab, const int* pos_dev,
+                                        void* cache_k, void* cache_v, const uint8_t* key_valid, void* o, int64_t ldo, int64_t rows,
+                                        int H, int HKV, int head_dim, int64_t Tmax, int64_t max_pos, float scale, hipStream_t st) {
+  UG_REQUIRE(rows > 0 && rows <= 32 && head_dim == DHD && HKV > 0 && H % HKV == 0 && qkv_part && ss_part && norm_cols > 0 && pos_dev && cache_k &&
+                 cache_v && o, "ug_attn_decode_fused_ord: bad args");
+  UG_REQUIRE(nparts == 6, "ug_attn_decode_fused_ord: built for six k-slab slots (a 1536-wide hidden size; got %ld)", (long)nparts);
+  UG_REQUIRE(ldpart > 0 && nparts * rows * ldpart < (1ll << 31), "ug_attn_decode_fused_ord: ldpart out of range");
+  const dim3 grid(8u, (unsigned)(H / HKV), (unsigned)((rows * HKV + 7) / 8));
+  hipLaunchKernelGGL(attn_decode_fused_kernel<6>, grid, dim3(64 * ADF_WAVES), 0, st, qkv_part, ss_part, pos_dev, (bf16_t*)cache_k,
+                     (bf16_t*)cache_v, (int)rows, HKV, H, (int)ldpart, (int)Tmax, (int)max_pos, (const bf16_t*)bias, cos_tab, sin_tab,
+                     key_valid, (bf16_t*)o, ldo, eps, (int)norm_cols, scale);
+  UG_CHECK_LAUNCH("ug_attn_decode_fused_ord");
+  return UG_OK;
+}
+
+extern "C" int ug_decode_finish_resid_norm_ord(const float* parts, int64_t ldp, int64_t nparts, float* x, const float* w, void* xn, int64_t rows,
+                                               int64_t cols, float eps, int* pos_inc, int* len_inc, hipStream_t st) {
+  UG_REQUIRE((pos_inc == nullptr) == (len_inc == nullptr), "ug_decode_finish_resid_norm_ord: pos_inc / len_inc come together");
+  UG_REQUIRE(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 4096 && ldp >= cols && ldp % 4 == 0 && nparts > 0 && parts && x && w,
+             "ug_decode_finish_resid_norm_ord: bad args (cols=%ld, multiple of 4 and <= 4096)", (long)cols);
+  UG_REQUIRE(ug_aligned16(x) && ug_aligned16(w) && ug_aligned16(parts) && ((uintptr_t)xn & 7) == 0 && nparts * rows * ldp < (1ll << 31),
+             "ug_decode_finish_resid_norm_ord: alignment / slot range");
+  if (cols <= 2048)
+    hipLaunchKernelGGL(finish_resid_norm_ord_kernel<8>, dim3((unsigned)rows), dim3(64), 0, st, parts, (int)ldp, (int)nparts, x, w, (bf16_t*)xn,
+                       (int)cols, eps, pos_inc, len_inc);
+  else
+    hipLaunchKernelGGL(finish_resid_norm_ord_kernel<16>, dim3((unsigned)rows), dim3(64), 0, st, parts, (int)ldp, (int)nparts, x, w, (bf16_t*)xn,
+                       (int)cols, eps, pos_inc, len_inc);
+  UG_CHECK_LAUNCH("ug_decode_finish_resid_norm_ord");
   return UG_OK;
 }

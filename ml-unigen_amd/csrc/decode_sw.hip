@@ -24,7 +24,7 @@
 namespace {
 
 enum { PRO_NORM = 0, PRO_BF16 = 1 };
-enum { EPI_RESID = 1, EPI_SWIGLU = 2, EPI_STORE = 3, EPI_ATOMIC = 4 };
+enum { EPI_RESID = 1, EPI_SWIGLU = 2, EPI_STORE = 3, EPI_ATOMIC = 4, EPI_PART = 5 };
 
 struct SwArgs {
   const bf16_t* W; int ldw; int K; int R;
@@ -35,7 +35,8 @@ struct SwArgs {
   const bf16_t* xb; int ldx;                               // PRO_BF16: finished bf16 operand [R][ldx]
   float* h_io;                                             // EPI_RESID: h[r][col] += float(bf16(y))
   bf16_t* act; int ld_act; int I;                          // EPI_SWIGLU
-  float* out; int ld_out;                                  // EPI_STORE; EPI_ATOMIC: out[r][col] += y (fp32 atomics, one per k-block)
+  float* out; int ld_out;                                  // EPI_STORE; EPI_ATOMIC: out[r][col] += y (fp32 atomics, one per k-block);
+                                                           //   EPI_PART: out[k-block][R][ld_out] = y (ordered decode: one slot per k-block)
   float* zero0; float* zero1; float* ss_zero;              // EPI_ATOMIC: accumulators this launch clears (consumed by earlier launches)
   int n0_4, per0, n1_4, per1;                              //   float4 counts and every workgroup's share of them
   int* pos_inc; int* len_inc;                              // advanced by workgroup 0 when given (the step's last reader of pos is behind us)
@@ -65,7 +66,8 @@ struct RowMap {
 // NW waves per workgroup, wave w owns k-slab w (K == 256 NW) and walks MAXT tiles of 16 weight rows through a RING-slot LDS ring of
 // MAXI KiB slots.  The whole ring is requested before the operand prologue (staging only part of it first measured no faster).
 // KBLK (split-K in k-blocks of NW slabs, grid.y = k-block): the partial tile of a workgroup joins the accumulator by ONE atomic per
-// element (EPI_ATOMIC) -- the down projection, whose 287 KB operand rules the whole-K cut out: 5 atomics per output instead of 35.
+// element (EPI_ATOMIC) -- the down projection, whose 287 KB operand rules the whole-K cut out: 5 atomics per output instead of 35 -- or
+// is stored into the k-block's own partial slot (EPI_PART, the deterministic decode's form: no atomics, no clears).
 template <int PRO, int EPI, int NW, int MAXT, int RING, int MAXI, bool PEND = false, bool KBLK = false>
 __global__ __launch_bounds__(64 * NW) void gemv_sw_kernel(const bf16_t* W_, const void* opnd_, const void* aux_, int ldw_, int K_, int R_, int nunits_,
                                                           int upw_, int ld_opnd_, int I_, float eps_, SwArgs a) {
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_sw_kernel(const bf16_t* W_, cons
     const bf16_t* W; int ldw, K, R, nunits, upw; const float* h; const float* norm_w; float eps; const bf16_t* xb; int ldx; float* h_io; int I;
   } f = {W_, ldw_, K_, R_, nunits_, upw_, (const float*)opnd_, (const float*)aux_, eps_, (const bf16_t*)opnd_, ld_opnd_, (float*)const_cast<void*>(aux_), I_};
   asm volatile("" ::"s"(W_), "s"(opnd_), "s"(aux_), "s"(ldw_), "s"(K_), "s"(R_), "s"(nunits_), "s"(upw_), "s"(ld_opnd_), "s"(I_));
-  static_assert(KBLK == (EPI == EPI_ATOMIC) && (!KBLK || PRO == PRO_BF16), "k-blocks accumulate; whole-K launches store");
+  static_assert(KBLK == (EPI == EPI_ATOMIC || EPI == EPI_PART) && (!KBLK || PRO == PRO_BF16), "k-blocks accumulate or fill slots; whole-K launches store");
   static_assert(RING <= MAXT && MAXT <= RING * MAXI, "ring too small for the reduction image");
   static_assert(MAXT <= NW, "wave t finishes tile t");
   static_assert(!PEND || PRO == PRO_NORM, "a pending accumulator joins the fp32 stream only");
@@ -94,6 +96,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_sw_kernel(const bf16_t* W_, cons
     else if constexpr (EPI == EPI_STORE && PEND)
       asm volatile("" ::"s"(a.pend), "s"(a.ld_pend), "s"(a.x_out), "s"(a.out), "s"(a.ld_out), "s"(a.pos_inc), "s"(a.len_inc));
     else if constexpr (EPI == EPI_STORE) asm volatile("" ::"s"(a.out), "s"(a.ld_out), "s"(a.pos_inc), "s"(a.len_inc));
+    else if constexpr (EPI == EPI_PART) asm volatile("" ::"s"(a.out), "s"(a.ld_out));
   };
   // EPI_ATOMIC: the clears this launch carries (accumulators consumed by earlier launches).  They go out BEHIND the operand loads and the
   // first weight tiles (their arguments are not among the preloaded ones, and stores between those loads would delay them); a thread
@@ -283,6 +286,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_sw_kernel(const bf16_t* W_, cons
           const int r = g * 4 + j;
           if (r < f.R) {
             if constexpr (EPI == EPI_ATOMIC) atomicAdd(a.out + ((int64_t)r * a.ld_out + col), v[j]);
+            else if constexpr (EPI == EPI_PART) a.out[((int64_t)blockIdx.y * f.R + r) * a.ld_out + col] = v[j];
             else a.out[(int64_t)r * a.ld_out + col] = v[j];
           }
         }
@@ -402,5 +406,21 @@ extern "C" int ug_decode_sw_head(const float* h, const float* pend, int64_t ld_p
   if (pend) hipLaunchKernelGGL((gemv_sw_kernel<PRO_NORM, EPI_STORE, 6, 2, 2, 8, true>), dim3(grid), dim3(64 * 6), 0, st, UG_SW_LEAD_NORM(a), a);
   else hipLaunchKernelGGL((gemv_sw_kernel<PRO_NORM, EPI_STORE, 6, 2, 2, 8>), dim3(grid), dim3(64 * 6), 0, st, UG_SW_LEAD_NORM(a), a);
   UG_CHECK_LAUNCH("ug_decode_sw_head");
+  return UG_OK;
+}
+
+extern "C" int ug_decode_sw_kblock_ord(const void* x, int64_t ldx, int64_t R, const void* W, int64_t ldw, float* part, int64_t ldpart, int64_t N,
+                                       int64_t K, hipStream_t st) {
+  UG_SW_COMMON("ug_decode_sw_kblock_ord");
+  UG_REQUIRE(x && part && K > 0 && K % (256 * 7) == 0 && ldx >= K && ldx % 8 == 0 && ldx < (1 << 20) && ldw >= K && ug_aligned16(x) &&
+                 ldpart >= N && (K / (256 * 7)) * R * ldpart < (1ll << 31),
+             "ug_decode_sw_kblock_ord: bad args (the contraction must be a whole number of 1792-wide k-blocks; K=%ld)", (long)K);
+  SwArgs a{};
+  a.W = (const bf16_t*)W; a.ldw = (int)ldw; a.K = (int)K; a.R = (int)R;
+  a.nunits = (int)N; a.xb = (const bf16_t*)x; a.ldx = (int)ldx; a.out = part; a.ld_out = (int)ldpart;
+  a.upw = 32;                                                  // two 16-row tiles per workgroup, as ug_decode_sw_kblock
+  const dim3 grid((unsigned)((a.nunits + a.upw - 1) / a.upw), (unsigned)(K / (256 * 7)));
+  hipLaunchKernelGGL((gemv_sw_kernel<PRO_BF16, EPI_PART, 7, 2, 2, 8, false, true>), grid, dim3(64 * 7), 0, st, UG_SW_LEAD_BF16(a, nullptr), a);
+  UG_CHECK_LAUNCH("ug_decode_sw_kblock_ord");
   return UG_OK;
 }

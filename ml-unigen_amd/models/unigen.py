@@ -582,12 +582,16 @@ class UniGen(ModelMixin, ConfigMixin):
             text_vocab_size: int = 151936,
             image_token_num_per_image: int = 256,
             generator: Optional[torch.Generator] = None,
+            deterministic: Optional[bool] = None,
             **kwargs,
     ):
         """Token-by-token image generation with CFG (reference models/unigen.py:457-521).  The reference
         only works when both embedding tensors are supplied; ids are accepted here too
-        and embedded, which is what its callers intend."""
-        from unigen_hip.qwen2 import DecodeState
+        and embedded, which is what its callers intend.
+        deterministic: decode with the ordered (atomic-free) kernels, so the same inputs, seed and generator give the same tokens on
+        every call; None follows torch.are_deterministic_algorithms_enabled()."""
+        from unigen_hip.qwen2 import DecodeState, resolve_deterministic
+        det = resolve_deterministic(deterministic)
         gen = self._use_gen()          # gen_projector path (reference :486-495,512-514): img_head on the last hidden state, the next
         n = image_token_num_per_image  # input is gen_projector(gen_embed(raw code)); no text-vocabulary offset anywhere
         embed = self.llm.model.embed_tokens
@@ -622,7 +626,8 @@ class UniGen(ModelMixin, ConfigMixin):
                     eng.fp.w("embed").data_ptr(), eng.fp.w("l0.wqkv").data_ptr(), eng.fp.p("embed").data_ptr(), eng.fp.p("norm").data_ptr(),
                     # (every other pointer the captured step bakes in lives in the same two flat buffers; the last layer's weights and the
                     # RoPE tables stand in for "nothing was reallocated in between")
-                    eng.fp.w(f"l{eng.dims.num_hidden_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(P + n)))
+                    eng.fp.w(f"l{eng.dims.num_hidden_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(P + n)),
+                    det)                                     # (a captured step belongs to one decode mode: its scratch differs)
         sess = getattr(eng, "_ar_session", None) if (use_graph and fused and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0") else None
         if sess is not None and sess["key"] != sess_key:
             sess = None
@@ -632,7 +637,7 @@ class UniGen(ModelMixin, ConfigMixin):
             if key_valid is not None:
                 st.key_valid[:, :P].copy_(key_valid)
         else:
-            st = DecodeState(eng.dims, R, P + n, dev, key_valid=key_valid)
+            st = DecodeState(eng.dims, R, P + n, dev, key_valid=key_valid, deterministic=det)
             out_tokens = torch.zeros((bsz, n), dtype=torch.int, device=dev)
             x = torch.empty((R, eng.dims.hidden_size), dtype=torch.float32, device=dev)      # static: next token's embedding
             tok = torch.zeros((bsz, 1), dtype=torch.long, device=dev)                        # static: last sampled token
@@ -656,7 +661,10 @@ class UniGen(ModelMixin, ConfigMixin):
                     logit_trace.append(acc_head.clone())
 
             def sample(hn):
-                ops.decode_gemv_(hn, w_head, acc_head)
+                if det:
+                    ops.skinny_linear_ord(hn, w_head, out_f32=acc_head)
+                else:
+                    ops.decode_gemv_(hn, w_head, acc_head)
                 keep_logits()
                 ops.ar_sample_(acc_head, bsz, V, guidance_scale, temperature, greedy, uniforms, st.pos, P, n, w_embed,
                                text_vocab_size, tok, out_tokens, x)
@@ -693,7 +701,7 @@ class UniGen(ModelMixin, ConfigMixin):
             out_tokens[:, 0] = tok[:, 0]
 
         # single-writer layer (csrc/decode_sw.hip): the final RMSNorm and the head slice are ONE launch behind the last layer
-        sw_head = fused and eng.decode_sw(st)
+        sw_head = fused and (eng.decode_ord_sw(st) if det else eng.decode_sw(st))
 
         def step():
             if sw_head:
@@ -724,6 +732,7 @@ class UniGen(ModelMixin, ConfigMixin):
                 out_tokens[:, i] = tok[:, 0]
         mark("replay")
         eng.last_decode_graph = graph is not None
+        eng.last_decode_deterministic = det
         if graph is not None and fused and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0":
             eng._ar_session = {"key": sess_key, "st": st, "out_tokens": out_tokens, "x": x, "tok": tok, "acc_head": acc_head,
                                "uniforms": uniforms, "graph": graph}
@@ -734,7 +743,7 @@ class UniGen(ModelMixin, ConfigMixin):
     @torch.no_grad()
     def generate(self, input_ids=None, input_embeddings=None, attention_mask=None, max_new_tokens=20, do_sample=False,
                  temperature=1.0, top_k=None, top_p=None, eos_token_id=None, pad_token_id=None, use_cache=True,
-                 generator=None, **kwargs):
+                 generator=None, deterministic=None, **kwargs):
         """Causal text generation with the conventions of transformers' `generate`, which the reference delegates to
         (models/unigen.py:584-588; caller evaluation/inference_unigen_cot.py:360): prompts as ids [B, L] or as
         `input_embeddings` [B, L, H] with an optional 2-D [B, L] key-validity mask (left padding); greedy when
@@ -742,8 +751,9 @@ class UniGen(ModelMixin, ConfigMixin):
         `eos_token_id` is filled with `pad_token_id` from then on and decoding stops when every row has finished.
         Returns prompt + continuation [B, L + new] for ids, the continuation alone [B, new] for embeddings (HF rule).
         One prefill into the static KV cache, then one decode step per token (`use_cache` is accepted and ignored: the
-        recompute form would return the same tokens)."""
-        from unigen_hip.qwen2 import DecodeState
+        recompute form would return the same tokens).  deterministic: ordered decode kernels (the same tokens on every call for the
+        same inputs and generator); None follows torch.are_deterministic_algorithms_enabled()."""
+        from unigen_hip.qwen2 import DecodeState, resolve_deterministic
         from .sampling import top_k_top_p_filtering
         unsupported = [k for k in ("num_beams", "num_return_sequences", "repetition_penalty", "penalty_alpha") if kwargs.get(k) not in (None, 1, 1.0)]
         if unsupported:
@@ -763,7 +773,9 @@ class UniGen(ModelMixin, ConfigMixin):
         eos = [] if eos_token_id is None else ([int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple)) else [int(eos_token_id)])
         if eos and pad_token_id is None:
             pad_token_id = eos[0]
-        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid)
+        det = resolve_deterministic(deterministic)
+        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
+        eng.last_decode_deterministic = det
         hn = eng.prefill(st, prompt, key_valid)
         eng.check_errors()
         V = self.config.vocab_size
@@ -800,14 +812,18 @@ class UniGen(ModelMixin, ConfigMixin):
     # ------------------------------------------------------------------ text decoding for understanding
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
-                     top_k=None, eot_token=None, use_cache=True):
+                     top_k=None, eot_token=None, use_cache=True, deterministic=None):
         """Greedy / top-k text continuation (reference models/unigen.py:523-581).  The reference re-runs the whole
         growing sequence every step and extends the additive mask by one row that copies the previous last row;
         here the prompt is prefilled once under its mask into the static KV cache and every new token is one decode
         step that attends to the keys the prompt's last row could see plus everything generated since (the same
-        function of the inputs; `use_cache=False` keeps the step-by-step recomputation for comparison)."""
+        function of the inputs; `use_cache=False` keeps the step-by-step recomputation for comparison).  deterministic: ordered
+        decode kernels for the cached form; None follows torch.are_deterministic_algorithms_enabled()."""
+        from unigen_hip.qwen2 import resolve_deterministic
+        det = resolve_deterministic(deterministic)
+        self.llm.engine.last_decode_deterministic = det
         if use_cache and attention_mask is not None and attention_mask.shape[0] == 1:
-            return self._mmu_generate_cached(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token)
+            return self._mmu_generate_cached(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det)
         return self._mmu_generate_recompute(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token)
 
     @staticmethod
@@ -821,7 +837,7 @@ class UniGen(ModelMixin, ConfigMixin):
         return torch.argmax(last, dim=-1).reshape(-1, 1)
 
     @torch.no_grad()
-    def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token):
+    def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False):
         from unigen_hip.qwen2 import DecodeState
         eng = self.llm.engine
         embed = self.llm.model.embed_tokens
@@ -831,7 +847,7 @@ class UniGen(ModelMixin, ConfigMixin):
         mb = eng.mask_bits(attention_mask, 1, L)
         eng.check_errors()
         key_valid = (attention_mask.reshape(L, L)[-1] == 0).view(1, L)
-        st = DecodeState(eng.dims, 1, L + max_new_tokens, dev, key_valid=key_valid)
+        st = DecodeState(eng.dims, 1, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, mask_bits=mb)
         V = self.config.vocab_size
         x = torch.empty((1, eng.dims.hidden_size), dtype=torch.float32, device=dev)
@@ -849,7 +865,7 @@ class UniGen(ModelMixin, ConfigMixin):
 
     @torch.no_grad()
     def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=0.0,
-                           top_k=None, eot_token=None):
+                           top_k=None, eot_token=None, deterministic=None):
         """`mmu_generate` for up to 32 prompts at once -- the rating loop of CoT-V (reference
         evaluation/inference_unigen_cot.py:308-415 calls mmu_generate once per (image, question) pair; every decode
         step streams the whole backbone whatever the row count, so R pairs cost about one).  Rows are LEFT-padded to a
@@ -857,9 +873,11 @@ class UniGen(ModelMixin, ConfigMixin):
         the pad columns blocked (the reference's mask builders do that for left-padded rows).  Each row follows the
         procedure of `mmu_generate`: prefill under its mask, then one decode step per token attending to the keys its
         last prompt row could see plus everything generated since.  Returns R lists of tokens, each cut after its
-        `eot_token`."""
-        from unigen_hip.qwen2 import DecodeState
+        `eot_token`.  deterministic: ordered decode kernels; None follows torch.are_deterministic_algorithms_enabled()."""
+        from unigen_hip.qwen2 import DecodeState, resolve_deterministic
         eng = self.llm.engine
+        det = resolve_deterministic(deterministic)
+        eng.last_decode_deterministic = det
         embed = self.llm.model.embed_tokens
         prompt = (embed(idx) if input_embeddings is None else input_embeddings).float()
         dev = prompt.device
@@ -871,7 +889,7 @@ class UniGen(ModelMixin, ConfigMixin):
         mb = eng.mask_bits(attention_mask, R, L)
         eng.check_errors()
         key_valid = attention_mask[:, 0, -1, :] == 0
-        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid)
+        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, mask_bits=mb)
         V = self.config.vocab_size
         x = torch.empty((R, eng.dims.hidden_size), dtype=torch.float32, device=dev)

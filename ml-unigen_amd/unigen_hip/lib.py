@@ -64,6 +64,12 @@ SIGNATURES = {
     "ug_ar_sample": [P, I64, I64, I64, F32, F32, I32, P, P, I64, I64, P, I64, I64, I64, P, P, P, P],
     "ug_maskgit_step": [P, I64, I64, I64, I64, I32, F32, P, P, P, I64, I64, I64, F32, P, P, P, P, P, P],
     "ug_skinny_finish": [P, P, P, P, I64, I64, I32, P],
+    "ug_gemv_bf16_ord": [P, I64, I64, P, I64, P, I64, I64, I64, I64, P],
+    "ug_skinny_finish_ord": [P, I64, I64, P, P, P, P, I64, I64, P],
+    "ug_decode_gemv_resid_norm_ord": [P, P, I64, I64, P, P, P, I64, P, I64, P, I64, I64, I64, P],
+    "ug_attn_decode_fused_ord": [P, I64, I64, P, F32, I64, P, P, P, P, P, P, P, P, I64, I64, I32, I32, I32, I64, I64, F32, P],
+    "ug_decode_sw_kblock_ord": [P, I64, I64, P, I64, P, I64, I64, I64, P],
+    "ug_decode_finish_resid_norm_ord": [P, I64, I64, P, P, P, I64, I64, F32, P, P, P],
     "ug_ce_fwd": [P, I64, I64, I64, P, I64, P, P, P, P, P],
     "ug_ce_bwd": [P, I64, I64, I64, P, I64, P, P, P, P, P],
     "ug_adamw_flat": [P, P, P, P, P, I64, F32, F32, F32, F32, F32, I64, F32, I32, P],

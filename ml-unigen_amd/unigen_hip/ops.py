@@ -649,6 +649,75 @@ def attn_decode_fused(acc_qkv, ss_in, eps, norm_cols, bias, cos, sin, pos_dev, c
     return out
 
 
+# ------------------------------------------------------------------------------------ ordered (deterministic) decode forms
+# Every split-K product lands in slots of its own by plain stores and is summed by its consumer in ascending slot order (fp32), then
+# rounded as the default form rounds it: bit-reproducible run to run (include/unigen_hip.h, "Ordered (deterministic) decode forms").
+ORD_QKV_SLABS = 6                 # ug_attn_decode_fused_ord is built for a 1536-wide hidden size (six 256-wide k-slabs)
+ORD_DOWN_KBLOCKS = 5              # ug_decode_gemv_resid_norm_ord is built for 0 or 5 pending k-block slots (intermediate 8 960)
+ORD_ROW_BLOCK = 32                # ug_gemv_bf16_ord takes up to 32 rows per launch
+
+
+def ord_slices(K):
+    """number of partial slots ug_gemv_bf16_ord writes for a contraction of K"""
+    return (K + 255) // 256
+
+
+def skinny_linear_ord(x, w, bias=None, resid=None, out_f32=None):
+    """skinny_linear without atomics: per-256-k-slice partials (blocks of 32 rows) summed in slice order.  resid given -> in-place
+    residual update; out_f32 given -> fp32 result written there; else bf16 output."""
+    M, N, K = x.shape[0], w.shape[0], w.shape[1]
+    if K % 32:
+        raise _l.UniGenHipError(f"skinny_linear_ord: K={K} must be a multiple of 32")
+    S = ord_slices(K)
+    parts = torch.empty((S, M, N), dtype=torch.float32, device=x.device)
+    L = _l.load()
+    for r0 in range(0, M, ORD_ROW_BLOCK):
+        r1 = min(M, r0 + ORD_ROW_BLOCK)
+        _l.check(L.ug_gemv_bf16_ord(_p(x[r0:r1]), x.stride(0), r1 - r0, _p(w), w.stride(0), _p(parts[:, r0:r1]), N, M * N, N, K, _stream()),
+                 "ug_gemv_bf16_ord")
+    out = None
+    if resid is None and out_f32 is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    _l.check(L.ug_skinny_finish_ord(_p(parts), S, M * N, _p(bias), _p(out), _p(out_f32), _p(resid), M, N, _stream()), "ug_skinny_finish_ord")
+    return out if out is not None else (resid if resid is not None else out_f32)
+
+
+def decode_gemv_resid_norm_ord_(x_in, pend_parts, norm_w, x_out, ss_part, w, part):
+    """ordered q/k/v launch: operand = bf16(norm_w * (x_in + bf16round(sum of the pending slots))) (pend_parts [P, R, ld] or None),
+    partials into part [slabs, R, N], row sums of squares into ss_part [slabs, 32]"""
+    npend = 0 if pend_parts is None else pend_parts.shape[0]
+    _l.check(_l.load().ug_decode_gemv_resid_norm_ord(_p(x_in), _p(pend_parts), pend_parts.stride(1) if npend else 0, npend, _p(norm_w), _p(x_out),
+                                                     _p(ss_part), x_in.shape[0], _p(w), w.stride(0), _p(part), part.stride(1), w.shape[0],
+                                                     w.shape[1], _stream()), "ug_decode_gemv_resid_norm_ord")
+    return part
+
+
+def attn_decode_fused_ord(qkv_part, ss_part, eps, norm_cols, bias, cos, sin, pos_dev, cache_k, cache_v, key_valid, out, H, HKV, hd, Tmax,
+                          scale=None):
+    """attn_decode_fused fed by the ordered q/k/v slots qkv_part [6, R, N] / ss_part [6, 32]"""
+    scale = 1.0 / math.sqrt(hd) if scale is None else scale
+    _l.check(_l.load().ug_attn_decode_fused_ord(_p(qkv_part), qkv_part.stride(1), qkv_part.shape[0], _p(ss_part), eps, norm_cols, _p(bias),
+                                                _p(cos), _p(sin), _p(pos_dev), _p(cache_k), _p(cache_v), _p(key_valid), _p(out),
+                                                out.stride(0), qkv_part.shape[1], H, HKV, hd, Tmax, cos.shape[0], scale, _stream()),
+             "ug_attn_decode_fused_ord")
+    return out
+
+
+def decode_sw_kblock_ord_(x, w, part):
+    """part[b, r, n] = sum over k-block b (1 792 wide) of x[r, k] w[n, k]: one slot per k-block, plain stores"""
+    _l.check(_l.load().ug_decode_sw_kblock_ord(_p(x), x.stride(0), x.shape[0], _p(w), w.stride(0), _p(part), part.stride(1), w.shape[0],
+                                               w.shape[1], _stream()), "ug_decode_sw_kblock_ord")
+    return part
+
+
+def decode_finish_resid_norm_ord_(parts, x, w, xn, eps, advance=None):
+    """x += bf16round(sum of the slots parts [P, R, ld]) in place; xn = bf16(rmsnorm(x) * w) if xn is given; advance = (pos, len)"""
+    pos, ln = advance if advance is not None else (None, None)
+    _l.check(_l.load().ug_decode_finish_resid_norm_ord(_p(parts), parts.stride(1), parts.shape[0], _p(x), _p(w), _p(xn), x.shape[0], x.shape[1],
+                                                       eps, _p(pos), _p(ln), _stream()), "ug_decode_finish_resid_norm_ord")
+    return xn
+
+
 # ------------------------------------------------------------------------------------ MaskGIT sampler
 def maskgit_step(logits, N, n, cfg, guidance_scale, u_sample, u_conf, cur_ids, mask_id, id_offset, mask_len_sched, temperature,
                  want_masking=False):

@@ -416,12 +416,22 @@ def _head_deferral_methods(cls):
     return cls
 
 
+def resolve_deterministic(deterministic=None):
+    """The decode mode of a generation call: `deterministic` if given, else torch's global flag
+    (torch.use_deterministic_algorithms)."""
+    return torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
+
+
 class DecodeState:
     """Static KV cache for autoregressive generation: per layer K,V [rows][HKV][Tmax][128] bf16, the write
-    position and visible length as DEVICE ints (so one captured graph serves every step)."""
+    position and visible length as DEVICE ints (so one captured graph serves every step).
+    deterministic: the decode steps on this state use the ORDERED forms (no float atomics: every split-K partial lands in a slot
+    of its own and its consumer sums the slots in ascending order), so the same inputs give the same bits on every run, eager or
+    captured.  The state's scratch is then partial slots instead of accumulators, so a captured step belongs to one mode."""
 
-    def __init__(self, dims, rows, Tmax, device, key_valid=None):
+    def __init__(self, dims, rows, Tmax, device, key_valid=None, deterministic=False):
         self.rows, self.Tmax = rows, Tmax
+        self.deterministic = bool(deterministic)
         n, hk, hd = dims.num_hidden_layers, dims.num_key_value_heads, dims.head_dim
         self.k = [torch.zeros((rows, hk, Tmax, hd), dtype=torch.bfloat16, device=device) for _ in range(n)]
         self.v = [torch.zeros((rows, hk, Tmax, hd), dtype=torch.bfloat16, device=device) for _ in range(n)]
@@ -457,6 +467,20 @@ class DecodeState:
         if not sw and getattr(self, "acc_gu", None) is None:
             self.acc_gu, self.acc_o = z(self.rows, 2 * dims.intermediate_size), z(self.rows, dims.hidden_size)
 
+    def ensure_parts(self, dims):
+        """Scratch of the ordered single-writer layer: the q/k/v k-slab slots [6][rows][q/k/v width] with their row statistics [6][32],
+        ONE set of down-projection k-block slots [5][rows][hidden] (layer l + 1's q/k/v launch consumes them before layer l + 1's down
+        projection rewrites them: no second set, no clears), the second residual-stream buffer and the finished bf16 `act`."""
+        if getattr(self, "qkv_part", None) is not None:
+            return
+        dev = self.pos.device
+        nqkv = (dims.num_attention_heads + 2 * dims.num_key_value_heads) * dims.head_dim
+        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        self.qkv_part, self.ss_part = e(ops.ORD_QKV_SLABS, self.rows, nqkv), e(ops.ORD_QKV_SLABS, 32)
+        self.down_part = e(ops.ORD_DOWN_KBLOCKS, self.rows, dims.hidden_size)
+        self.x_mid = torch.zeros((self.rows, dims.hidden_size), dtype=torch.float32, device=dev)
+        self.act = torch.empty((self.rows, dims.intermediate_size), dtype=torch.bfloat16, device=dev)
+
 
 def _decode_methods(cls):
     def prefill(self, st, embeds, key_valid=None, mask_bits=None):
@@ -482,6 +506,41 @@ def _decode_methods(cls):
         d = self.dims
         return (getattr(self, "decode_fused", True) and os.environ.get("UNIGEN_DECODE_SW", "1") != "0" and st.rows <= 16
                 and ops.decode_sw_supported(d.hidden_size, d.intermediate_size, d.num_attention_heads * d.head_dim, d.head_dim))
+
+    def decode_ord_sw(self, st):
+        """Whether a deterministic decode state runs the ordered single-writer layer (the sizes its kernels are built for: hidden 1536,
+        intermediate 5 x 1792); every other deterministic shape takes the ordered wide form."""
+        d = self.dims
+        return (self.decode_sw(st) and d.hidden_size == 256 * ops.ORD_QKV_SLABS and d.intermediate_size == 1792 * ops.ORD_DOWN_KBLOCKS
+                and d.num_hidden_layers >= 1)
+
+    def _decode_layers_ord(self, st, x):
+        """The decoder stack of one deterministic decode step, five launches per layer as _decode_layers_sw, without float atomics:
+          q/k/v      ordered split-K: operand = the stream + bf16(sum of the previous layer's down k-block slots, in order);
+                     stores one partial tile per k-slab (6 slots) and the slabs' row sums of squares
+          attention  sums the 6 slots in slab order in its prologue, then finishes q/k/v as the default form does
+          o, gate/up the single-writer launches of the default form (already one writer per element)
+          down       k-blocks with the partial tile STORED into the k-block's slot (5 slots)
+        -> the residual stream after the last layer is stream + bf16round(sum of st.down_part)."""
+        d, fp = self.dims, self.fp
+        Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
+        H = d.hidden_size
+        cos, sin = self.rope(st.Tmax)
+        st.ensure_parts(d)
+        eps = d.rms_norm_eps
+        o = torch.empty((st.rows, Hq * hd), dtype=torch.bfloat16, device=x.device)
+        bufs = (x, st.x_mid)
+        n = d.num_hidden_layers
+        for i in range(n):
+            xin, xout = bufs[i & 1], bufs[(i + 1) & 1]
+            ops.decode_gemv_resid_norm_ord_(xin, None if i == 0 else st.down_part, fp.p(f"l{i}.ln1"), xout, st.ss_part, fp.w(f"l{i}.wqkv"),
+                                            st.qkv_part)
+            ops.attn_decode_fused_ord(st.qkv_part, st.ss_part, eps, H, fp.w(f"l{i}.bqkv"), cos, sin, st.pos, st.k[i], st.v[i], st.key_valid, o,
+                                      Hq, Hk, hd, st.Tmax)
+            ops.decode_sw_resid_(o, fp.w(f"l{i}.wo"), xout)
+            ops.decode_sw_gate_up_(xout, fp.p(f"l{i}.ln2"), eps, fp.w(f"l{i}.wgu"), st.act)
+            ops.decode_sw_kblock_ord_(st.act, fp.w(f"l{i}.wdown"), st.down_part)
+        return bufs[n & 1]
 
     def _decode_layers_sw(self, st, x):
         """The decoder stack of one decode step, five launches per layer (measured forms: profiles/r06_decode_forms.md):
@@ -517,7 +576,18 @@ def _decode_methods(cls):
     def decode_step_logits(self, st, x, w_head, logits):
         """decode_step + the head slice in one go (single-writer layer only): logits fp32 [rows, N] = rows `w_head` of the tied
         embedding applied to the final-norm hidden state; advances st.pos / st.len.  The final RMSNorm and the last layer's
-        pending residual add ride in the head launch's prologue."""
+        pending residual add ride in the head launch's prologue.
+        Deterministic state: the last layer's down slots are summed in order by their own launch ahead of the head (ordered
+        single-writer layer), or the step runs the ordered wide form and the head is an ordered skinny GEMV."""
+        self.last_decode_deterministic = st.deterministic
+        if st.deterministic:
+            if not self.decode_ord_sw(st):
+                hn = self.decode_step(st, x)
+                return ops.skinny_linear_ord(hn, w_head, out_f32=logits)
+            stream = self._decode_layers_ord(st, x)
+            ops.decode_finish_resid_norm_ord_(st.down_part, stream, self.fp.p("norm"), None, self.dims.rms_norm_eps)
+            ops.decode_sw_head_(stream, self.fp.p("norm"), self.dims.rms_norm_eps, w_head, logits, advance=(st.pos, st.len))
+            return logits
         stream, pending = self._decode_layers_sw(st, x)
         ops.decode_sw_head_(stream, self.fp.p("norm"), self.dims.rms_norm_eps, w_head, logits, pend=pending, advance=(st.pos, st.len))
         return logits
@@ -531,6 +601,14 @@ def _decode_methods(cls):
         d, fp = self.dims, self.fp
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
         R, H, I = st.rows, d.hidden_size, d.intermediate_size
+        self.last_decode_deterministic = st.deterministic
+        if st.deterministic:
+            if not self.decode_ord_sw(st):
+                return self._decode_step_wide(st, x)
+            hn = torch.empty((R, H), dtype=torch.bfloat16, device=x.device)
+            stream = self._decode_layers_ord(st, x)
+            ops.decode_finish_resid_norm_ord_(st.down_part, stream, fp.p("norm"), hn, d.rms_norm_eps, advance=(st.pos, st.len))
+            return hn
         if not getattr(self, "decode_fused", True) or R > 32 or hd != 128 or min(H, I, Hq * hd) < 256 or H % 32 or I % 32:
             return self._decode_step_wide(st, x)
         eps = d.rms_norm_eps
@@ -558,21 +636,23 @@ def _decode_methods(cls):
         return hn
 
     def _decode_step_wide(self, st, x):
-        """> 32 rows: the GEMV kernel does not apply; split-K GEMMs + separate finishing kernels."""
+        """> 32 rows: the GEMV kernel does not apply; split-K GEMMs + separate finishing kernels.  Deterministic state: every
+        projection is the ordered skinny linear (per-k-slice partial slots in blocks of 32 rows, summed in slice order)."""
         d, fp = self.dims, self.fp
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
         cos, sin = self.rope(st.Tmax)
+        lin = ops.skinny_linear_ord if st.deterministic else ops.skinny_linear
         for i in range(d.num_hidden_layers):
             xn, _ = ops.rmsnorm_fwd(x, fp.p(f"l{i}.ln1"), d.rms_norm_eps, want_rstd=False)
-            qkv = ops.skinny_linear(xn, fp.w(f"l{i}.wqkv"), bias=fp.w(f"l{i}.bqkv"))
+            qkv = lin(xn, fp.w(f"l{i}.wqkv"), bias=fp.w(f"l{i}.bqkv"))
             ops.rope_at_(qkv, cos, sin, Hq + Hk, hd, st.pos)
             ops.kv_store(qkv, st.k[i], st.v[i], st.rows, 1, Hq, Hk, hd, st.Tmax, st.pos, 0)
             o = ops.attn_decode(qkv, st.k[i], st.v[i], st.key_valid, Hq, Hk, hd, st.Tmax, st.len)
-            ops.skinny_linear(o, fp.w(f"l{i}.wo"), resid=x)
+            lin(o, fp.w(f"l{i}.wo"), resid=x)
             xn2, _ = ops.rmsnorm_fwd(x, fp.p(f"l{i}.ln2"), d.rms_norm_eps, want_rstd=False)
-            gu = ops.skinny_linear(xn2, fp.w(f"l{i}.wgu"))
+            gu = lin(xn2, fp.w(f"l{i}.wgu"))
             act = ops.swiglu_fwd(gu)
-            ops.skinny_linear(act, fp.w(f"l{i}.wdown"), resid=x)
+            lin(act, fp.w(f"l{i}.wdown"), resid=x)
         hn, _ = ops.rmsnorm_fwd(x, fp.p("norm"), d.rms_norm_eps, want_rstd=False)
         st.advance()
         return hn
@@ -587,6 +667,7 @@ def _decode_methods(cls):
     cls.prefill, cls.decode_step, cls.head_slice = prefill, decode_step, head_slice
     cls.decode_sw, cls._decode_layers_sw, cls.decode_step_logits = decode_sw, _decode_layers_sw, decode_step_logits
     cls._decode_step_wide = _decode_step_wide
+    cls.decode_ord_sw, cls._decode_layers_ord = decode_ord_sw, _decode_layers_ord
     return cls
 
 

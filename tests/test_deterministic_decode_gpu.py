@@ -1,0 +1,388 @@
+"""Deterministic decode mode (`deterministic=True`, or torch.use_deterministic_algorithms): the ordered, atomic-free decode forms.
+
+Every new entry point must match the existing atomic kernel and an fp64 restatement, give the same bits on every launch and overwrite
+every partial slot it owns; the engine, the model-level generation calls and the full-depth bench shape must give the same bits run to
+run, eager or captured or through the kept session -- with no near-tie carve-out."""
+import os
+
+import pytest
+import torch
+
+from helpers import additive, golden, llm_config_dir, rel_err
+
+pytestmark = pytest.mark.gpu
+BF = torch.bfloat16
+
+
+def _r(g, *shape, s=1.0):
+    return s * torch.randn(*shape, generator=g)
+
+
+def _seq(parts):
+    """the documented order: ascending slot index, fp32"""
+    acc = parts[0].clone()
+    for p in range(1, parts.shape[0]):
+        acc += parts[p]
+    return acc
+
+
+def _lib():
+    from unigen_hip import lib, ops
+    return lib.load(), ops._stream()
+
+
+# ------------------------------------------------------------------ kernel level
+@pytest.mark.parametrize("R", [1, 5, 16])
+def test_gemv_ord_and_skinny_finish_ord(dev, R):
+    from unigen_hip import ops
+    L, st = _lib()
+    g = torch.Generator().manual_seed(R)
+    for N, K in ((2048, 1536), (192, 64), (1536, 8960)):
+        x, W = _r(g, R, K).to(BF).to(dev), _r(g, N, K, s=0.05).to(BF).to(dev)
+        S = ops.ord_slices(K)
+        runs = []
+        for _ in range(3):
+            parts = torch.full((S, R, N), float("nan"), device=dev)
+            assert L.ug_gemv_bf16_ord(x.data_ptr(), K, R, W.data_ptr(), K, parts.data_ptr(), N, R * N, N, K, st) == 0
+            runs.append(parts)
+        torch.cuda.synchronize()
+        assert torch.isfinite(runs[0]).all()
+        assert all(torch.equal(runs[0], p) for p in runs[1:])
+        got = _seq(runs[0])
+        ref = (x.double() @ W.double().t()).float()
+        acc = torch.zeros(R, N, device=dev)
+        ops.gemv_acc_(x, W, acc)
+        assert rel_err(got, ref) < 1e-5 and rel_err(got, acc) < 1e-5, (N, K)
+        # the ordered finisher: fp32 result = the ordered sum bit for bit; bf16 + bias and the residual form round it as skinny_finish does
+        out = torch.full((R, N), float("nan"), device=dev)
+        assert L.ug_skinny_finish_ord(runs[0].data_ptr(), S, R * N, None, None, out.data_ptr(), None, R, N, st) == 0
+        assert torch.equal(out, got)
+        bias = _r(g, N).to(BF).to(dev)
+        ob = torch.empty(R, N, dtype=BF, device=dev)
+        assert L.ug_skinny_finish_ord(runs[0].data_ptr(), S, R * N, bias.data_ptr(), ob.data_ptr(), None, None, R, N, st) == 0
+        assert torch.equal(ob, (got + bias.float()).to(BF))
+        res = _r(g, R, N).to(dev)
+        want = res + got.to(BF).float()
+        assert L.ug_skinny_finish_ord(runs[0].data_ptr(), S, R * N, None, None, None, res.data_ptr(), R, N, st) == 0
+        assert torch.equal(res, want)
+        # the wrapper, more than 32 rows in blocks of 32
+        xl = _r(g, 40, K).to(BF).to(dev)
+        a, b = ops.skinny_linear_ord(xl, W), ops.skinny_linear_ord(xl, W)
+        assert torch.equal(a, b) and rel_err(a, (xl.double() @ W.double().t()).float()) < 1e-2
+
+
+@pytest.mark.parametrize("R", [1, 5, 16])
+@pytest.mark.parametrize("npend", [0, 5])
+def test_qkv_ord_matches_the_atomic_launch(dev, R, npend):
+    from unigen_hip import ops
+    g = torch.Generator().manual_seed(10 * R + npend)
+    H, N = 1536, 2048
+    x_in, nw = _r(g, R, H).to(dev), (1 + _r(g, H, s=0.1)).to(dev)
+    W = _r(g, N, H, s=0.05).to(BF).to(dev)
+    pend_parts = _r(g, 5, R, H, s=0.3).to(dev) if npend else None
+    pend = _seq(pend_parts) if npend else torch.zeros(R, H, device=dev)
+    acc, ss, x_out = torch.zeros(R, N, device=dev), torch.zeros(32, device=dev), torch.empty(R, H, device=dev)
+    ops.decode_gemv_resid_norm_(x_in, pend, nw, x_out, ss, W, acc)
+    runs = []
+    for _ in range(3):
+        part, ss_part = torch.full((6, R, N), float("nan"), device=dev), torch.full((6, 32), float("nan"), device=dev)
+        xo = torch.full((R, H), float("nan"), device=dev)
+        ops.decode_gemv_resid_norm_ord_(x_in, pend_parts, nw, xo, ss_part, W, part)
+        runs.append((part, ss_part[:, :R], xo))
+    torch.cuda.synchronize()
+    part, ssp, xo = runs[0]
+    assert torch.isfinite(part).all() and torch.isfinite(ssp).all()
+    for other in runs[1:]:
+        assert all(torch.equal(a, b) for a, b in zip(runs[0], other))
+    assert torch.equal(xo, x_out)
+    xnew = x_in + pend.to(BF).float()
+    ref = ((nw * xnew).to(BF).double() @ W.double().t()).float()
+    assert rel_err(_seq(part), ref) < 1e-5 and rel_err(_seq(part), acc) < 1e-5
+    assert rel_err(_seq(ssp), (xnew.double() ** 2).sum(1).float()) < 1e-5 and rel_err(_seq(ssp), ss[:R]) < 1e-5
+
+
+@pytest.mark.parametrize("R", [1, 5, 16])
+def test_attention_ord_equals_the_default_fed_with_the_ordered_sum(dev, R):
+    """Fed with partial slots, the ordered attention must produce exactly what the default kernel produces from their ascending sum."""
+    from unigen_hip import ops
+    g = torch.Generator().manual_seed(R)
+    Hq, Hk, hd, N, Tmax, pos = 12, 2, 128, 2048, 96, 70
+    part, ss_part = _r(g, 6, R, N, s=3.0).to(dev), (100 + 50 * torch.rand(6, 32, generator=g)).to(dev)
+    bias = _r(g, N, s=0.1).to(BF).to(dev)
+    cos, sin = ops.rope_tables(Tmax, hd, 1e6, dev)
+    k0, v0 = _r(g, R, Hk, Tmax, hd).to(BF).to(dev), _r(g, R, Hk, Tmax, hd).to(BF).to(dev)
+    p = torch.tensor([pos], dtype=torch.int32, device=dev)
+    kd, vd, od = k0.clone(), v0.clone(), torch.empty(R, Hq * hd, dtype=BF, device=dev)
+    ops.attn_decode_fused(_seq(part), _seq(ss_part), 1e-6, 1536, bias, cos, sin, p, kd, vd, None, od, Hq, Hk, hd, Tmax)
+    outs = []
+    for _ in range(3):
+        ko, vo, oo = k0.clone(), v0.clone(), torch.full((R, Hq * hd), float("nan"), dtype=BF, device=dev)
+        ops.attn_decode_fused_ord(part, ss_part, 1e-6, 1536, bias, cos, sin, p, ko, vo, None, oo, Hq, Hk, hd, Tmax)
+        outs.append((oo, ko, vo))
+    torch.cuda.synchronize()
+    for oo, ko, vo in outs:
+        assert torch.equal(oo, od) and torch.equal(ko, kd) and torch.equal(vo, vd)
+
+
+@pytest.mark.parametrize("R", [1, 5, 16])
+def test_down_kblock_ord_and_finish_ord(dev, R):
+    from unigen_hip import ops
+    g = torch.Generator().manual_seed(R)
+    H, I = 1536, 8960
+    act, W = _r(g, R, I).to(BF).to(dev), _r(g, H, I, s=0.03).to(BF).to(dev)
+    acc = torch.zeros(R, H, device=dev)
+    ops.decode_sw_kblock_(act, W, acc)
+    runs = []
+    for _ in range(3):
+        part = torch.full((5, R, H), float("nan"), device=dev)
+        ops.decode_sw_kblock_ord_(act, W, part)
+        runs.append(part)
+    torch.cuda.synchronize()
+    assert torch.isfinite(runs[0]).all() and all(torch.equal(runs[0], p) for p in runs[1:])
+    got = _seq(runs[0])
+    assert rel_err(got, (act.double() @ W.double().t()).float()) < 1e-5 and rel_err(got, acc) < 1e-5
+    # final finish: the same bits as the default finisher fed with the ordered sum
+    x, w = _r(g, R, H).to(dev), (1 + _r(g, H, s=0.1)).to(dev)
+    xd, xnd = x.clone(), torch.empty(R, H, dtype=BF, device=dev)
+    ops.decode_finish_resid_norm_(got.clone(), xd, w, xnd, 1e-6)
+    for _ in range(3):
+        xo, xno = x.clone(), torch.full((R, H), float("nan"), dtype=BF, device=dev)
+        ops.decode_finish_resid_norm_ord_(runs[0], xo, w, xno, 1e-6)
+        assert torch.equal(xo, xd) and torch.equal(xno, xnd)
+
+
+# ------------------------------------------------------------------ engine at the 1.5B width
+def _model_1p5b(dev, layers=2, vocab=4096):
+    from models import UniGen
+    from oracle import qwen2_ref, weights
+    cfg = dict(qwen2_ref.QWEN25_1P5B, num_hidden_layers=layers, vocab_size=vocab)
+    model = UniGen(w_und_encoder=False, vocab_size=vocab, llm_vocab_size=2048, llm_model_path=llm_config_dir(cfg), codebook_size=2047,
+                   num_vq_tokens=16, load_from_pretrained=True, device=dev, init_seed=-1).eval()
+    names = [(n, tuple(p.shape)) for n, p in model.llm.named_parameters()]
+    model.llm.load_state_dict(weights.synth_llm_state(names, seed=17), strict=False)
+    return model
+
+
+@pytest.fixture(scope="module")
+def m1p5(dev):
+    return _model_1p5b(dev)
+
+
+@pytest.mark.parametrize("R", [16, 5, 24, 40])
+def test_engine_ordered_steps_are_bit_reproducible(dev, m1p5, R):
+    from unigen_hip.qwen2 import DecodeState
+    eng = m1p5.llm.engine
+    g = torch.Generator().manual_seed(R)
+    P, steps = 37, 3
+    prompt = (0.02 * torch.randn(R, P, 1536, generator=g)).to(dev)
+    xs = [(0.02 * torch.randn(R, 1536, generator=g)).to(dev) for _ in range(steps)]
+    w_head = eng.fp.w("embed")[2048:4095]
+
+    def run(det):
+        st = DecodeState(eng.dims, R, P + steps, dev, deterministic=det)
+        eng.prefill(st, prompt)
+        assert eng.decode_ord_sw(st) == (R <= 16)
+        hs = [eng.decode_step(st, x.clone()).clone() for x in xs]
+        assert eng.last_decode_deterministic == det
+        assert int(st.pos.item()) == P + steps and int(st.len.item()) == P + steps + 1
+        logits = torch.full((R, 2047), float("nan"), device=dev)
+        if det or R <= 16:                              # (the default form's one-launch head exists for the single-writer layer only)
+            st2 = DecodeState(eng.dims, R, P + 1, dev, deterministic=det)
+            eng.prefill(st2, prompt)
+            eng.decode_step_logits(st2, xs[0].clone(), w_head, logits)
+            assert int(st2.pos.item()) == P + 1
+        return hs, [t.clone() for t in st.k + st.v], logits
+
+    with torch.no_grad():
+        runs = [run(True) for _ in range(3)]
+        for other in runs[1:]:
+            assert all(torch.equal(a, b) for a, b in zip(runs[0][0], other[0]))
+            assert all(torch.equal(a, b) for a, b in zip(runs[0][1], other[1]))
+            assert torch.equal(runs[0][2], other[2])
+        default = run(False)
+        for a, b in zip(runs[0][0], default[0]):
+            assert rel_err(a, b) < 1.5e-2
+        for a, b in zip(runs[0][1], default[1]):
+            assert rel_err(a[:, :, P:], b[:, :, P:]) < 1.5e-2
+        assert rel_err(runs[0][2], runs[0][0][0].float() @ w_head.float().t()) < 1.5e-2
+        # captured-graph replay == eager, bit for bit
+        st = DecodeState(eng.dims, R, P + steps, dev, deterministic=True)
+        eng.prefill(st, prompt)
+        x = xs[0].clone()
+        h1 = eng.decode_step(st, x).clone()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            hn = eng.decode_step(st, x)
+        got = [h1]
+        for i in (1, 2):
+            x.copy_(xs[i])
+            graph.replay()
+            got.append(hn.clone())
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(got, runs[0][0]))
+        assert all(torch.equal(a, b) for a, b in zip(st.k + st.v, runs[0][1]))
+
+
+# ------------------------------------------------------------------ model level (golden G9 / G13)
+def _g9_model(g, dev):
+    from models import UniGen
+    from oracle import weights
+    cfg, ids = g["cfg"], g["ids"]
+    m = UniGen(w_und_encoder=False, vocab_size=cfg["vocab_size"], llm_vocab_size=ids["text_vocab"], llm_model_path=llm_config_dir(cfg),
+               codebook_size=20, num_vq_tokens=16, load_from_pretrained=True, device=dev, init_seed=1)
+    names = [(n, tuple(p.shape)) for n, p in m.llm.named_parameters()]
+    m.llm.load_state_dict(weights.synth_llm_state(names, seed=g["weight_seed"], std=g["weight_std"]), strict=False)
+    return m.eval()
+
+
+def test_ar_generation_deterministic_on_golden_g9(dev):
+    g = golden("g9_generate.pt")
+    model = _g9_model(g, dev)
+    eng = model.llm.engine
+    ar, tv = g["ar"], g["ids"]["text_vocab"]
+
+    def run(use_graph=True, seed=None, greedy=True, **kw):
+        gen = None if seed is None else torch.Generator(device=dev).manual_seed(seed)
+        return model.t2i_generate_ar(input_ids=ar["cond"].to(dev), uncond_input_ids=ar["uncond"].to(dev), attention_mask=ar["attention_mask"].to(dev),
+                                     guidance_scale=ar["scale"], temperature=1.0, text_vocab_size=tv, image_token_num_per_image=ar["n"],
+                                     greedy=greedy, generator=gen, use_graph=use_graph, **kw).cpu()
+    eng._ar_session = None
+    eager = run(use_graph=False, deterministic=True)
+    assert eng.last_decode_deterministic and not eng.last_decode_graph
+    captured = run(deterministic=True)
+    sess = eng._ar_session
+    assert sess is not None and sess["st"].deterministic and eng.last_decode_graph
+    kept = run(deterministic=True)
+    assert eng._ar_session["graph"] is sess["graph"]
+    assert torch.equal(eager, captured) and torch.equal(eager, kept)
+    want, margin = ar["bf16"]["tokens"], ar["bf16"]["margin"]
+    compared = 0
+    for b in range(want.shape[0]):
+        for i in range(want.shape[1]):
+            if margin[b][i] < 0.05:
+                break
+            assert int(eager[b, i]) == int(want[b, i]), (b, i)
+            compared += 1
+    assert compared >= 24, compared
+    a = run(seed=5, greedy=False, deterministic=True)
+    b = run(seed=5, greedy=False, deterministic=True)
+    assert torch.equal(a, b)
+    # mode selection: the torch flag, and the keyword overriding it; sessions of the two modes are never shared
+    was = torch.are_deterministic_algorithms_enabled()
+    try:
+        torch.use_deterministic_algorithms(True, warn_only=True)
+        run()
+        assert eng.last_decode_deterministic and eng._ar_session["st"].deterministic
+        det_graph = eng._ar_session["graph"]
+        run(deterministic=False)
+        assert not eng.last_decode_deterministic and not eng._ar_session["st"].deterministic
+        assert eng._ar_session["graph"] is not det_graph
+        def_graph = eng._ar_session["graph"]
+        again = run(deterministic=None)
+        assert eng._ar_session["st"].deterministic and eng._ar_session["graph"] is not def_graph
+        assert torch.equal(again, captured)
+    finally:
+        torch.use_deterministic_algorithms(was)
+    run(deterministic=None)
+    assert eng.last_decode_deterministic == was
+
+
+def test_text_generation_deterministic_on_golden_g9(dev):
+    g = golden("g9_generate.pt")
+    model = _g9_model(g, dev)
+    eng = model.llm.engine
+    mm = g["mmu"]
+    idx, new = mm["idx"].to(dev), mm["max_new_tokens"]
+    mask = additive(mm["mask_allow"]).to(dev)
+    outs = [model.mmu_generate(idx=idx, attention_mask=mask, max_new_tokens=new, temperature=0.0, deterministic=True) for _ in range(2)]
+    assert [int(t) for t in outs[0]] == [int(t) for t in outs[1]] and eng.last_decode_deterministic
+    want, margin = mm["bf16"]["tokens"].tolist(), mm["bf16"]["margin"].tolist()
+    for i in range(len(want)):
+        if margin[i] < 0.05:
+            break
+        assert int(outs[0][i]) == want[i], i
+    L = idx.shape[1]
+    bidx, bmask = idx.repeat(3, 1), mask.reshape(1, 1, L, L).repeat(3, 1, 1, 1)
+    b1 = model.mmu_generate_batch(idx=bidx, attention_mask=bmask, max_new_tokens=new, deterministic=True)
+    b2 = model.mmu_generate_batch(idx=bidx, attention_mask=bmask, max_new_tokens=new, deterministic=True)
+    assert [[int(t) for t in r] for r in b1] == [[int(t) for t in r] for r in b2]
+    ids = torch.randint(0, 300, (3, 12), generator=torch.Generator().manual_seed(3)).to(dev)
+    for sample in (False, True):
+        res = [model.generate(input_ids=ids, max_new_tokens=10, do_sample=sample, deterministic=True,
+                              generator=torch.Generator(device=dev).manual_seed(9)) for _ in range(2)]
+        assert torch.equal(res[0], res[1]) and eng.last_decode_deterministic
+
+
+def test_ar_generation_deterministic_gen_head_g13(dev):
+    """The gen-head path (img_head on the last hidden state, the unfused sampler): golden tokens, eager == captured, bit for bit."""
+    from models import UniGen
+    from oracle import weights
+    g = golden("g13_ar_gen_head.pt")
+    cfg, ids = g["cfg"], g["ids"]
+    m = UniGen(w_und_encoder=False, vocab_size=cfg["vocab_size"], llm_vocab_size=ids["text_vocab"], llm_model_path=llm_config_dir(cfg),
+               codebook_size=g["codebook"], num_vq_tokens=g["n"], load_from_pretrained=True, gen_proj_depth=2, use_gen_dim=True,
+               gen_input_dim=16, device=dev, init_seed=1)
+    names = [(k, tuple(p.shape)) for k, p in m.named_parameters() if k != "_ddp_anchor"]
+    m.load_state_dict(weights.synth_llm_state(names, seed=g["weight_seed"], std=g["weight_std"]), strict=False)
+    m.eval()
+    runs = [m.t2i_generate_ar(input_ids=g["cond"].to(dev), uncond_input_ids=g["uncond"].to(dev), attention_mask=g["attention_mask"].to(dev),
+                              guidance_scale=g["scale"], temperature=1.0, text_vocab_size=ids["text_vocab"], image_token_num_per_image=g["n"],
+                              greedy=True, use_graph=ug, deterministic=True).cpu() for ug in (False, True, False)]
+    assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2]) and m.llm.engine.last_decode_deterministic
+    want, margin = g["dim1"]["bf16"]["tokens"], g["dim1"]["bf16"]["margin"]
+    compared = 0
+    for b in range(want.shape[0]):
+        for i in range(want.shape[1]):
+            if margin[b, i] < 0.3:
+                break
+            assert int(runs[0][b, i]) == int(want[b, i]), (b, i)
+            compared += 1
+    assert compared >= 8, compared
+
+
+# ------------------------------------------------------------------ full depth, the bench shape
+@pytest.fixture(scope="module")
+def full_model(dev):
+    from models import UniGen
+    from oracle import qwen2_ref, weights
+    TV, CB = 151674, 8192
+    V = TV + CB + 1
+    cfg = dict(qwen2_ref.QWEN25_1P5B, vocab_size=V)
+    model = UniGen(w_und_encoder=False, vocab_size=V, llm_vocab_size=TV, llm_model_path=llm_config_dir(cfg), codebook_size=CB,
+                   num_vq_tokens=256, load_from_pretrained=True, device=dev, init_seed=-1).eval()
+    names = [(n, tuple(p.shape)) for n, p in model.llm.named_parameters()]
+    model.llm.load_state_dict(weights.synth_llm_state(names, seed=93), strict=False)
+    return model, TV
+
+
+@pytest.mark.skipif(os.environ.get("UNIGEN_SKIP_FULL_DEPTH") == "1", reason="UNIGEN_SKIP_FULL_DEPTH=1")
+def test_28_layer_ar_generation_is_bit_reproducible(dev, full_model):
+    model, TV = full_model
+    eng = model.llm.engine
+    B, P, n, scale, PAD = 8, 186, 16, 6.0, 151643
+    g = torch.Generator().manual_seed(31)
+    cond = torch.randint(0, PAD, (B, P + n + 1), generator=g)
+    uncond = torch.randint(0, PAD, (B, P + n + 1), generator=g)
+    for b in range(B):
+        cond[b, :int(torch.randint(0, 60, (1,), generator=g))] = PAD
+        uncond[b, :int(torch.randint(90, 170, (1,), generator=g))] = PAD
+    am = torch.cat([cond != PAD, uncond != PAD]).long()
+    am[:, P:] = 1
+
+    def run(**kw):
+        return model.t2i_generate_ar(input_ids=cond.to(dev), uncond_input_ids=uncond.to(dev), attention_mask=am.to(dev), guidance_scale=scale,
+                                     temperature=1.0, text_vocab_size=TV, image_token_num_per_image=n, deterministic=True, **kw).cpu()
+    eng._ar_session = None
+    tr1, tr2 = [], []
+    e1 = run(greedy=True, use_graph=False, trace=tr1)
+    e2 = run(greedy=True, use_graph=False, trace=tr2)
+    assert len(tr1) == n and all(torch.equal(a, b) for a, b in zip(tr1, tr2)) and torch.equal(e1, e2)
+    captured = run(greedy=True)
+    assert eng.last_decode_graph and eng.last_decode_deterministic
+    kept = run(greedy=True)
+    assert torch.equal(e1, captured) and torch.equal(e1, kept)
+    s1 = run(greedy=False, generator=torch.Generator(device=dev).manual_seed(4))
+    s2 = run(greedy=False, generator=torch.Generator(device=dev).manual_seed(4))
+    assert torch.equal(s1, s2)
+    eng._ar_session = None
