@@ -452,8 +452,10 @@ class DecodeState:
         [rows][N]; each is cleared by a later launch once fully consumed), the second residual-stream buffer, and the row
         sum-of-squares slots that carry the RMSNorm statistics to the accumulators' consumers.  sw: the layer whose o and gate/up
         projections are single-writer launches (csrc/decode_sw.hip) -- no gate/up or o accumulator, a finished bf16 `act` instead,
-        and two down-projection accumulators that alternate by layer (the one layer l + 1 still reads is cleared by layer l + 1's
-        own down projection)."""
+        and two down-projection accumulators that alternate by layer: layer l adds into acc_down (l even) or acc_down2 (l odd) and
+        clears the other one, which layer l - 1 left and layer l's q/k/v launch has consumed.  The last layer's accumulator is
+        cleared by its reader when that is the final-norm launch of decode_step; the head launch of decode_step_logits leaves it
+        as it is, so at odd depth (where it is acc_down, the one layer 0 adds into) layer 0's q/k/v launch of the next step clears it."""
         dev = self.pos.device
         nqkv = (dims.num_attention_heads + 2 * dims.num_key_value_heads) * dims.head_dim
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
@@ -549,7 +551,10 @@ def _decode_methods(cls):
           o          single writer: the stream is FINISHED in place
           gate/up    single writer: act = SwiGLU, finished bf16
           down       split-K (k-blocks, LDS pre-reduction) on act into this layer's accumulator; clears the accumulators consumed so far
-        -> (stream, pending): the residual stream after the last layer is stream + bf16round(pending)."""
+        -> (stream, pending): the residual stream after the last layer is stream + bf16round(pending).
+        Accumulators: layer i adds into accd[i & 1] and clears accd[(i + 1) & 1].  `pending` is accd[(n - 1) & 1]; its reader may
+        leave it uncleared (the head launch of decode_step_logits does).  At even depth that is accd[1], which layer 0's down projection
+        clears; at odd depth it is accd[0], the one layer 0 adds into, so layer 0's q/k/v launch clears it first (even depth: no clear)."""
         d, fp = self.dims, self.fp
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
         R, H = st.rows, d.hidden_size
@@ -565,7 +570,10 @@ def _decode_methods(cls):
         for i in range(n):
             xin, xout = bufs[i & 1], bufs[(i + 1) & 1]
             pend = st.zeros if i == 0 else accd[(i - 1) & 1]
-            ops.decode_gemv_resid_norm_(xin, pend, fp.p(f"l{i}.ln1"), xout, st.ss_attn, fp.w(f"l{i}.wqkv"), st.acc_qkv)
+            # odd depth: the last layer's accumulator is accd[0], which layer 0's down projection adds into next; the previous step's
+            # head reads it without clearing it, so layer 0's q/k/v launch clears it (even depth: layer 0's down clears accd[1] itself)
+            clr = accd[0] if i == 0 and n & 1 else None
+            ops.decode_gemv_resid_norm_(xin, pend, fp.p(f"l{i}.ln1"), xout, st.ss_attn, fp.w(f"l{i}.wqkv"), st.acc_qkv, zero1=clr)
             ops.attn_decode_fused(st.acc_qkv, st.ss_attn, eps, H, fp.w(f"l{i}.bqkv"), cos, sin, st.pos, st.k[i], st.v[i],
                                   st.key_valid, o, Hq, Hk, hd, st.Tmax)
             ops.decode_sw_resid_(o, fp.w(f"l{i}.wo"), xout)
