@@ -333,6 +333,23 @@ int ug_ar_sample(float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidan
                  const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps, const float* embed, int64_t ld_embed,
                  int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, hipStream_t stream);
 
+/* ug_ar_sample with truncated sampling, in the order temperature -> top-k -> top-p -> min-p -> draw (transformers' order).  Per
+ * image: v[e] = the mixed logit exactly as ug_ar_sample forms it, mx = max v, ex[e] = exp(v[e] - mx).  Each filter is a value
+ * threshold and the kept set is {e : v[e] >= tau}, tau = max(tau_k, tau_p, tau_m):
+ *   top_k (0 or >= V: off): tau_k = the k-th largest value, duplicates counted; every value tied at tau_k is kept.
+ *   top_p (0 < top_p <= 1; 1: off): over S_k = {v >= tau_k}, Z = sum of ex over S_k: a value t is kept iff the mass of the strictly
+ *     greater values of S_k is <= top_p * Z.  A run of equal values is kept or dropped as a whole (a sorted cut through such a run
+ *     depends on the sort's order of equal keys); the maximum is always kept.
+ *   min_p (0 <= min_p <= 1; 0: off): tau_m = mx + log(min_p).
+ * The draw is ug_ar_sample's: inverse CDF in index order on uniforms[step*bsz + b] over ex with dropped entries counted as 0; the
+ * drawn token is always a kept one.  No float atomics: a step is a bit-reproducible function of its inputs.  greedy: the filters are
+ * ignored (the argmax is always kept) and stats is not written.  stats (optional, [bsz][2]): stats[2b] = the smallest kept value,
+ * stats[2b+1] = the number of kept entries. */
+int ug_ar_sample_filtered(float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature, int greedy,
+                          const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps, const float* embed,
+                          int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, int64_t top_k,
+                          float top_p, float min_p, float* stats, hipStream_t stream);
+
 /* ---- loss ------------------------------------------------------------------------------------ */
 /* replaces: F.cross_entropy(ignore_index=-100) x3 in UniGen.forward (models/unigen.py:310-338) and
  * get_batch_logps (training/train_dpo.py:51-90).  logits bf16 [R, ld], ld % 8 == 0.

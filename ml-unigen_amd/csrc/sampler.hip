@@ -232,6 +232,221 @@ __global__ __launch_bounds__(ARS_T) void ar_sample_kernel(float* __restrict__ ac
   for (int i = t; i < (H >> 2); i += ARS_T) { const float4 v = er[i]; x0[i] = v; x1[i] = v; }
 }
 
+// ------------------------------------------------------------------ the same step with top-k / top-p / min-p truncation
+// Every filter is a VALUE threshold (include/unigen_hip.h: ug_ar_sample_filtered), so nothing is sorted: the kept set is
+// {v >= tau}, tau = max(tau_k, tau_p, tau_m).  Values are compared through an order-preserving 32-bit key.  Thread t holds the keys
+// and exp(v - max) of its contiguous chunk in registers (exp is evaluated once per element); every float sum has a fixed order
+// (chunk in index order, xor tree over the wave, the sixteen wave partials in wave order), so the step is a function of its inputs.
+__device__ __forceinline__ uint32_t ar_key(float v) {
+  uint32_t b = __float_as_uint(v);
+  if (b == 0x80000000u) b = 0u;                                   // -0 and +0 compare equal: one key
+  return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float ar_unkey(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
+
+constexpr int AR_PER = AR_MAXV / ARS_T;
+struct ArProbe { float mass; uint32_t le, gt; };
+// Over the elements with key >= lo: mass = sum of ex over key >= bound; le = the largest key in [lo, bound) (lo if none); gt = the
+// smallest key in [bound, hi] (hi if none).  One barrier; consecutive calls alternate `par` (a wave can be one call ahead, not two).
+__device__ __forceinline__ ArProbe ar_probe(const uint32_t (&key)[AR_PER], const float (&ex)[AR_PER], uint32_t lo, uint32_t bound,
+                                            uint32_t hi, float (*s_mass)[ARS_T / 64], uint32_t (*s_le)[ARS_T / 64],
+                                            uint32_t (*s_gt)[ARS_T / 64], int par, int lane, int wave) {
+  float m = 0.f;
+  uint32_t le = lo, gt = hi;
+#pragma unroll
+  for (int j = 0; j < AR_PER; ++j) {
+    const uint32_t k = key[j];
+    m += (k >= bound && k >= lo) ? ex[j] : 0.f;
+    if (k < bound) le = max(le, k);
+    else if (k <= hi) gt = min(gt, k);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    m += __shfl_xor(m, o, 64);
+    le = max(le, (uint32_t)__shfl_xor((int)le, o, 64));
+    gt = min(gt, (uint32_t)__shfl_xor((int)gt, o, 64));
+  }
+  if (lane == 0) { s_mass[par][wave] = m; s_le[par][wave] = le; s_gt[par][wave] = gt; }
+  __syncthreads();
+  ArProbe r{0.f, lo, hi};
+#pragma unroll
+  for (int w = 0; w < ARS_T / 64; ++w) { r.mass += s_mass[par][w]; r.le = max(r.le, s_le[par][w]); r.gt = min(r.gt, s_gt[par][w]); }
+  return r;
+}
+
+__global__ __launch_bounds__(ARS_T) void ar_sample_filtered_kernel(float* __restrict__ acc, int64_t lda, int bsz, int V, float scale,
+                                                                  float inv_temp, const float* __restrict__ uniforms,
+                                                                  const int* __restrict__ pos_dev, int pos0, int nsteps,
+                                                                  const float* __restrict__ embed, int64_t lde, int H,
+                                                                  int64_t id_offset, int top_k, float top_p, float log_min_p,
+                                                                  int64_t* __restrict__ tok, int* __restrict__ out_tokens,
+                                                                  float* __restrict__ x, float* __restrict__ stats) {
+  __shared__ float mix[AR_MAXV + AR_MAXV / 32];
+  __shared__ float red[ARS_T / 64];
+  __shared__ float wtot[ARS_T / 64];
+  __shared__ __attribute__((aligned(16))) int hist[4][256];
+  __shared__ float s_mass[2][ARS_T / 64];
+  __shared__ uint32_t s_le[2][ARS_T / 64], s_gt[2][ARS_T / 64];
+  __shared__ int s_cnt[ARS_T / 64];
+  __shared__ uint32_t s_min[ARS_T / 64];
+  __shared__ int hit, last_el, chosen;
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  int pos_now;                                                  // (scalar load of the position word: see ar_sample_kernel)
+  sld4(pos_now, pos_dev);
+  float* c = acc + (int64_t)b * lda;
+  float* u = acc + (int64_t)(bsz + b) * lda;
+  // pass 1 (coalesced), as in ar_sample_kernel: mixed logits into LDS, accumulator rows cleared, running max per thread
+  float mx = -INFINITY;
+  {
+    float cr[AR_PER], ur[AR_PER];
+#pragma unroll
+    for (int j = 0; j < AR_PER; ++j) {
+      const int e = min(t + j * ARS_T, V - 1);
+      cr[j] = c[e]; ur[j] = u[e];
+    }
+#pragma unroll
+    for (int j = 0; j < AR_PER; ++j) {
+      const int e = t + j * ARS_T;
+      if (e < V) {
+        c[e] = 0.f; u[e] = 0.f;
+        const float cv = bf2f(f2bf(cr[j])), uv = bf2f(f2bf(ur[j]));
+        const float v = (uv + scale * (cv - uv)) * inv_temp;
+        mix[ar_pad(e)] = v;
+        mx = fmaxf(mx, v);
+      }
+    }
+  }
+  wait_lgkm0();
+  tie_s(pos_now);
+  const int step = min(max(pos_now - pos0, 0), nsteps - 1);
+  const float u01 = uniforms[(int64_t)step * bsz + b];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if (lane == 0) red[wave] = mx;
+  (&hist[0][0])[t] = 0;                                         // 4 x 256 digit counters, one per thread
+  if (t == 0) { hit = ARS_T; last_el = -1; chosen = 0; }
+  __syncthreads();
+  float bmx = red[0];
+#pragma unroll
+  for (int w = 1; w < ARS_T / 64; ++w) bmx = fmaxf(bmx, red[w]);
+  // thread t owns the contiguous chunk [t*C, t*C + nv): keys and exp in registers from here on (slots past nv: key 0, mass 0)
+  const int C = (V + ARS_T - 1) / ARS_T;
+  const int e0 = t * C, nv = min(max(V - e0, 0), C);
+  uint32_t key[AR_PER];
+  float ex[AR_PER];
+#pragma unroll
+  for (int j = 0; j < AR_PER; ++j) {
+    key[j] = 0u; ex[j] = 0.f;
+    if (j < nv) { const float v = mix[ar_pad(e0 + j)]; key[j] = ar_key(v); ex[j] = expf(v - bmx); }
+  }
+  // top-k: radix select of the k-th largest key, 8 bits per pass; every wave scans the 256 counters itself (one barrier per pass)
+  uint32_t tau_k = 0u;
+  if (top_k > 0) {
+    int kk = top_k;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int sh = 24 - 8 * p;
+#pragma unroll
+      for (int j = 0; j < AR_PER; ++j)
+        if (j < nv && (p == 0 || (key[j] >> ((sh + 8) & 31)) == (tau_k >> ((sh + 8) & 31)))) atomicAdd(&hist[p][(key[j] >> sh) & 255], 1);
+      __syncthreads();
+      const int4 h = reinterpret_cast<const int4*>(hist[p])[lane];              // digits 4*lane .. 4*lane+3
+      const int s = h.x + h.y + h.z + h.w;
+      int incl = s;                                                             // elements with a digit >= 4*lane
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_down(incl, o, 64);
+        if (lane + o < 64) incl += v;
+      }
+      int above = __shfl_down(incl, 1, 64);                                     // ... with a digit >= 4*lane+4
+      if (lane == 63) above = 0;
+      const int src = __ffsll((unsigned long long)__ballot(incl >= kk && above < kk)) - 1;       // the lane that holds the k-th
+      int d = 4 * lane + 3, cnt = h.w;
+      if (above + cnt < kk) { above += cnt; --d; cnt = h.z;
+        if (above + cnt < kk) { above += cnt; --d; cnt = h.y;
+          if (above + cnt < kk) { above += cnt; --d; } } }
+      const int digit = __shfl(d, src, 64);
+      kk = __shfl(kk - above, src, 64);
+      tau_k |= (uint32_t)digit << sh;
+    }
+  }
+  // top-p over S_k = {key >= tau_k}: the smallest value whose mass of strictly greater values is <= top_p * Z.  Bisection on the key;
+  // each probe also returns the present values next to the cut, so both ends move onto present values and the search stops when the
+  // interval holds one distinct value.  The mass is monotone in the cut under the fixed summation order, so the search is consistent.
+  uint32_t tau_p = tau_k;
+  if (top_p < 1.f) {
+    uint32_t lo = tau_k, hi = ar_key(bmx);
+    const float lim = top_p * ar_probe(key, ex, lo, lo, hi, s_mass, s_le, s_gt, 0, lane, wave).mass;
+    int par = 1;
+    while (lo < hi) {
+      const uint32_t mid = lo + ((hi - lo) >> 1);
+      const ArProbe r = ar_probe(key, ex, lo, mid + 1u, hi, s_mass, s_le, s_gt, par, lane, wave);
+      par ^= 1;
+      if (r.mass <= lim) hi = r.le; else lo = r.gt;
+    }
+    tau_p = hi;
+  }
+  // min-p: one compare (log_min_p = -inf when off: key below every finite value)
+  const uint32_t thr = max(tau_p, ar_key(bmx + log_min_p));
+  // inverse CDF in index order over the kept entries (dropped ones count 0)
+  unsigned kept = 0;
+  float local = 0.f;
+#pragma unroll
+  for (int j = 0; j < AR_PER; ++j)
+    if (j < nv && key[j] >= thr) { kept |= 1u << j; local += ex[j]; }
+  float incl = local;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) wtot[wave] = incl;
+  if (stats) {                                                  // diagnostics: smallest kept key and kept count
+    int cnt = __popc(kept);
+    uint32_t mn = 0xffffffffu;
+#pragma unroll
+    for (int j = 0; j < AR_PER; ++j) if (kept >> j & 1) mn = min(mn, key[j]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o, 64); mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64)); }
+    if (lane == 0) { s_cnt[wave] = cnt; s_min[wave] = mn; }
+  }
+  __syncthreads();
+  float base = 0.f, total = 0.f;
+#pragma unroll
+  for (int w = 0; w < ARS_T / 64; ++w) { const float wv = wtot[w]; if (w < wave) base += wv; total += wv; }
+  // The drawn token must be a kept one whatever the rounding of the running sums: only a thread with kept mass can be hit (the first
+  // whose inclusive bound exceeds the target; the last such thread if rounding leaves none), and it walks its kept entries only.
+  const float target = u01 * total;
+  if (local > 0.f) {
+    atomicMax(&last_el, t);
+    if (target < base + incl) atomicMin(&hit, t);
+  }
+  __syncthreads();
+  if (t == (hit < ARS_T ? hit : last_el)) {
+    float run = base + (incl - local);
+    int idx = e0;
+    bool done = false;
+#pragma unroll
+    for (int j = 0; j < AR_PER; ++j)
+      if (!done && (kept >> j & 1) && ex[j] > 0.f) { run += ex[j]; idx = e0 + j; done = run > target; }
+    chosen = idx;
+  }
+  if (stats && t == 0) {
+    int cnt = 0;
+    uint32_t mn = 0xffffffffu;
+    for (int w = 0; w < ARS_T / 64; ++w) { cnt += s_cnt[w]; mn = min(mn, s_min[w]); }
+    stats[2 * b] = ar_unkey(mn);
+    stats[2 * b + 1] = (float)cnt;
+  }
+  __syncthreads();
+  const int token = chosen;
+  if (t == 0) { tok[b] = token; out_tokens[(int64_t)b * nsteps + step] = token; }
+  const float4* er = reinterpret_cast<const float4*>(embed + (token + id_offset) * lde);
+  float4* x0 = reinterpret_cast<float4*>(x + (int64_t)b * H);
+  float4* x1 = reinterpret_cast<float4*>(x + (int64_t)(bsz + b) * H);
+  for (int i = t; i < (H >> 2); i += ARS_T) { const float4 v = er[i]; x0[i] = v; x1[i] = v; }
+}
+
 }  // namespace
 
 extern "C" int ug_maskgit_step(const void* logits, int64_t ld, int64_t V, int64_t N, int64_t n, int cfg, float guidance_scale,
@@ -263,5 +478,31 @@ extern "C" int ug_ar_sample(float* acc, int64_t ldacc, int64_t bsz, int64_t V, f
                      1.f / temperature, greedy, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, tok,
                      out_tokens, x);
   UG_CHECK_LAUNCH("ug_ar_sample");
+  return UG_OK;
+}
+
+extern "C" int ug_ar_sample_filtered(float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature,
+                                     int greedy, const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps,
+                                     const float* embed, int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens,
+                                     float* x, int64_t top_k, float top_p, float min_p, float* stats, hipStream_t st) {
+  UG_REQUIRE(acc && pos_dev && embed && tok && out_tokens && x && (greedy || uniforms), "ug_ar_sample_filtered: null argument");
+  UG_REQUIRE(V <= AR_MAXV, "ug_ar_sample_filtered: code-book slice of %ld columns exceeds the %d this build stages in LDS", (long)V,
+             AR_MAXV);
+  UG_REQUIRE(bsz > 0 && V > 0 && ldacc >= V && nsteps > 0 && H > 0 && H % 4 == 0 && ld_embed % 4 == 0 && temperature > 0.f &&
+                 ug_aligned16(embed) && ug_aligned16(x),
+             "ug_ar_sample_filtered: bad sizes (bsz=%ld V=%ld H=%ld temperature=%g)", (long)bsz, (long)V, (long)H, (double)temperature);
+  UG_REQUIRE(top_k >= 0 && top_p > 0.f && top_p <= 1.f && min_p >= 0.f && min_p <= 1.f,
+             "ug_ar_sample_filtered: bad filter (top_k=%ld >= 0, 0 < top_p=%g <= 1, 0 <= min_p=%g <= 1)", (long)top_k, (double)top_p,
+             (double)min_p);
+  if (greedy) {                                       // the argmax is always kept: the filters change nothing (stats stay unwritten)
+    hipLaunchKernelGGL(ar_sample_kernel, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V, guidance_scale,
+                       1.f / temperature, 1, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, tok,
+                       out_tokens, x);
+  } else {
+    hipLaunchKernelGGL(ar_sample_filtered_kernel, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V, guidance_scale,
+                       1.f / temperature, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset,
+                       top_k >= V ? 0 : (int)top_k, top_p, min_p > 0.f ? logf(min_p) : -INFINITY, tok, out_tokens, x, stats);
+  }
+  UG_CHECK_LAUNCH("ug_ar_sample_filtered");
   return UG_OK;
 }

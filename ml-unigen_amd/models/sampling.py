@@ -81,6 +81,46 @@ def get_mask_chedule(method, **schedule_kwargs):
     raise ValueError("Unknown schedule method: {}".format(method))
 
 
+def truncate_logits(logits, top_k=0, top_p=1.0, min_p=0.0):
+    """top-k -> top-p -> min-p truncation of [B, V] logits (already divided by the temperature) as VALUE thresholds: returns a new
+    tensor with -inf outside the kept set {v >= tau}, tau = max(tau_k, tau_p, tau_m).  The rule of the fused AR sampler
+    (include/unigen_hip.h: ug_ar_sample_filtered), in plain torch for the unfused paths, on CPU or GPU.
+      top_k (0 or >= V: off): tau_k = the k-th largest value; every value tied at it is kept (`logits < topk[..., -1]` dropped, as in
+        top_k_top_p_filtering).
+      top_p (1: off): over S_k = {v >= tau_k} with ex = exp(v - max), Z = sum of ex over S_k: a value is kept iff the mass of the
+        strictly greater values is <= top_p * Z.  For the first token of a run of equal values this is top_k_top_p_filtering's rule;
+        where that function cuts THROUGH a run of equal logits (which of them survive depends on the sort's order of equal keys),
+        this rule keeps the whole run.  The maximum is always kept.
+      min_p (0: off): tau_m = max + log(min_p) (transformers' rule; the softmax normaliser cancels).
+    Masses are summed in float64."""
+    if logits.dim() != 2:
+        raise ValueError("truncate_logits expects [B, V] logits")
+    if not (top_k >= 0 and 0.0 < top_p <= 1.0 and 0.0 <= min_p <= 1.0):
+        raise ValueError(f"truncate_logits: need top_k >= 0, 0 < top_p <= 1, 0 <= min_p <= 1 (got {top_k}, {top_p}, {min_p})")
+    V = logits.shape[-1]
+    v = logits.double()
+    mx = v.max(-1, keepdim=True).values
+    tau = torch.full_like(mx, float("-inf"))
+    if 0 < top_k < V:
+        tau = v.topk(int(top_k), dim=-1).values[..., -1:]
+    if top_p < 1.0:
+        ordered = torch.sort(v, dim=-1, descending=True).values
+        ex = torch.where(ordered >= tau, torch.exp(ordered - mx), torch.zeros_like(ordered))
+        cum = ex.cumsum(-1)
+        before = cum - ex                                    # mass sorted in front of each entry (equal values in front included)
+        first = torch.ones_like(ordered, dtype=torch.bool)
+        first[..., 1:] = ordered[..., 1:] != ordered[..., :-1]
+        pos = torch.arange(V, device=v.device).expand_as(ordered)
+        run_start = torch.where(first, pos, torch.zeros_like(pos)).cummax(-1).values
+        greater = before.gather(-1, run_start)               # mass of the strictly greater values
+        ok = (greater <= top_p * cum[..., -1:]) & (ordered >= tau)
+        tau_p = torch.where(ok, ordered, torch.full_like(ordered, float("inf"))).min(-1, keepdim=True).values
+        tau = torch.maximum(tau, tau_p)
+    if min_p > 0.0:
+        tau = torch.maximum(tau, mx + math.log(min_p))
+    return torch.where(v >= tau, logits, torch.full_like(logits, float("-inf")))
+
+
 def top_k_top_p_filtering(logits, top_k=0, top_p=1.0, filter_value=-float("Inf"), min_tokens_to_keep=1):
     """In-place top-k / nucleus filtering of [B, V] logits (reference :90-128)."""
     if top_k > 0:

@@ -583,14 +583,29 @@ class UniGen(ModelMixin, ConfigMixin):
             image_token_num_per_image: int = 256,
             generator: Optional[torch.Generator] = None,
             deterministic: Optional[bool] = None,
+            top_k: Optional[int] = 0,
+            top_p: Optional[float] = 1.0,
+            min_p: Optional[float] = 0.0,
             **kwargs,
     ):
         """Token-by-token image generation with CFG (reference models/unigen.py:457-521).  The reference
         only works when both embedding tensors are supplied; ids are accepted here too
         and embedded, which is what its callers intend.
         deterministic: decode with the ordered (atomic-free) kernels, so the same inputs, seed and generator give the same tokens on
-        every call; None follows torch.are_deterministic_algorithms_enabled()."""
+        every call; None follows torch.are_deterministic_algorithms_enabled().
+        top_k / top_p / min_p: truncated sampling in the order temperature -> top-k -> top-p -> min-p -> draw (0 / 1.0 / 0.0 or None:
+        off).  Each is a value threshold (models/sampling.py: truncate_logits; in the captured step the fused sampler kernel finds
+        it on the device): values tied at the top-k threshold are all kept, and top-p keeps or drops a run of equal logits as a
+        whole, where a sorted cut would split it by the sort's order of equal keys.  `greedy` ignores them (the argmax is always
+        kept)."""
         from unigen_hip.qwen2 import DecodeState, resolve_deterministic
+        from .sampling import truncate_logits
+        top_k = 0 if top_k is None else top_k
+        top_p = 1.0 if top_p is None else float(top_p)
+        min_p = 0.0 if min_p is None else float(min_p)
+        if not (isinstance(top_k, int) and top_k >= 0 and 0.0 < top_p <= 1.0 and 0.0 <= min_p <= 1.0):
+            raise UniGenHipError(f"t2i_generate_ar: need an int top_k >= 0, 0 < top_p <= 1 and 0 <= min_p <= 1 "
+                                 f"(got top_k={top_k!r}, top_p={top_p!r}, min_p={min_p!r})")
         det = resolve_deterministic(deterministic)
         gen = self._use_gen()          # gen_projector path (reference :486-495,512-514): img_head on the last hidden state, the next
         n = image_token_num_per_image  # input is gen_projector(gen_embed(raw code)); no text-vocabulary offset anywhere
@@ -614,6 +629,9 @@ class UniGen(ModelMixin, ConfigMixin):
         use_graph = bool(kwargs.get("use_graph", True))
         code_lo, code_hi = text_vocab_size, self.vocab_size - 1          # logits[..., text_vocab_size:-1]
         V = code_hi - code_lo
+        if top_k >= V:
+            top_k = 0
+        filt = (top_k, top_p, min_p) if not greedy and (top_k > 0 or top_p < 1.0 or min_p > 0.0) else None
         fused = (R <= 32 and eng.dims.hidden_size >= 256 and eng.dims.hidden_size % 32 == 0 and not kwargs.get("torch_sampler", False)
                  and not gen)
         # The captured decode step is kept ACROSS calls (round 5): Best-of-N generation calls this method once per prompt with the
@@ -627,7 +645,8 @@ class UniGen(ModelMixin, ConfigMixin):
                     # (every other pointer the captured step bakes in lives in the same two flat buffers; the last layer's weights and the
                     # RoPE tables stand in for "nothing was reallocated in between")
                     eng.fp.w(f"l{eng.dims.num_hidden_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(P + n)),
-                    det)                                     # (a captured step belongs to one decode mode: its scratch differs)
+                    det,                                     # (a captured step belongs to one decode mode: its scratch differs)
+                    filt)                                    # (the filter constants are kernel arguments of the captured sampler)
         sess = getattr(eng, "_ar_session", None) if (use_graph and fused and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0") else None
         if sess is not None and sess["key"] != sess_key:
             sess = None
@@ -660,14 +679,21 @@ class UniGen(ModelMixin, ConfigMixin):
                 if logit_trace is not None and not torch.cuda.is_current_stream_capturing():
                     logit_trace.append(acc_head.clone())
 
+            def draw():                            # the step's one sampling launch
+                if filt is None:
+                    ops.ar_sample_(acc_head, bsz, V, guidance_scale, temperature, greedy, uniforms, st.pos, P, n, w_embed,
+                                   text_vocab_size, tok, out_tokens, x)
+                else:
+                    ops.ar_sample_filtered_(acc_head, bsz, V, guidance_scale, temperature, greedy, uniforms, st.pos, P, n, w_embed,
+                                            text_vocab_size, tok, out_tokens, x, top_k=filt[0], top_p=filt[1], min_p=filt[2])
+
             def sample(hn):
                 if det:
                     ops.skinny_linear_ord(hn, w_head, out_f32=acc_head)
                 else:
                     ops.decode_gemv_(hn, w_head, acc_head)
                 keep_logits()
-                ops.ar_sample_(acc_head, bsz, V, guidance_scale, temperature, greedy, uniforms, st.pos, P, n, w_embed,
-                               text_vocab_size, tok, out_tokens, x)
+                draw()
         else:
             def sample(hn):
                 # (gen path: the reference mixes the bf16 img_head outputs in bf16 under autocast, :498-500)
@@ -677,7 +703,10 @@ class UniGen(ModelMixin, ConfigMixin):
                 if greedy:
                     nxt = lg.argmax(-1, keepdim=True)
                 else:
-                    nxt = torch.multinomial(torch.softmax(lg / temperature, dim=-1), num_samples=1, generator=generator)
+                    lg = lg / temperature
+                    if filt is not None:
+                        lg = truncate_logits(lg, top_k=filt[0], top_p=filt[1], min_p=filt[2])
+                    nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1, generator=generator)
                 tok.copy_(nxt)
                 if gen:
                     x.copy_(self.get_gen_embed(torch.cat([nxt, nxt]))[:, 0])
@@ -707,8 +736,7 @@ class UniGen(ModelMixin, ConfigMixin):
             if sw_head:
                 eng.decode_step_logits(st, x, w_head, acc_head)            # (also advances the cache position)
                 keep_logits()
-                ops.ar_sample_(acc_head, bsz, V, guidance_scale, temperature, greedy, uniforms, st.pos, P, n, w_embed,
-                               text_vocab_size, tok, out_tokens, x)
+                draw()
                 return
             hn = eng.decode_step(st, x)            # (also advances the cache position)
             sample(hn)

@@ -761,6 +761,17 @@ def ar_sample_(acc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_d
              "ug_ar_sample")
 
 
+def ar_sample_filtered_(acc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_dev, pos0, nsteps, embed_master, id_offset, tok,
+                        out_tokens, x, top_k=0, top_p=1.0, min_p=0.0, stats=None):
+    """ar_sample_ with top-k / top-p / min-p truncation as value thresholds (see include/unigen_hip.h: ug_ar_sample_filtered);
+    stats: optional fp32 [bsz, 2] taking the smallest kept value and the kept count per image."""
+    _l.check(_l.load().ug_ar_sample_filtered(_p(acc), acc.stride(0), bsz, V, float(guidance_scale), float(temperature), int(bool(greedy)),
+                                             _p(uniforms), _p(pos_dev), int(pos0), int(nsteps), _p(embed_master),
+                                             embed_master.stride(0), embed_master.shape[1], int(id_offset), _p(tok), _p(out_tokens),
+                                             _p(x), int(top_k), float(top_p), float(min_p), _p(stats), _stream()),
+             "ug_ar_sample_filtered")
+
+
 # ------------------------------------------------------------------------------------ loss
 def ce_fwd(logits, V, labels, ignore_index=-100, want_logp=False):
     """logits bf16 [R, ld>=V]; -> (loss_and_count [2], lse [R], loss_row [R], logp|None)"""

@@ -46,10 +46,17 @@ def run(n_img=8, prefix=138, n_tok=256, use_graph=True, reps=3):
             "hbm_floor_ms_per_step": round((1310.3e6 * 2 + 8192 * 1536 * 2) / 6.3e12 * 1e3, 3)}
 
 
-def run_modes(n_img=8, prefix=138, n_tok=256, rounds=5):
-    """Default vs deterministic decode (t2i_generate_ar(deterministic=...)) in ONE process at the bench shape, captured graph, the two
-    modes alternating.  One kept session exists at a time and the mode is part of its key, so each visit to a mode makes two calls
-    and times the second (it replays the session the first one captured).  Prints both medians and their ratio."""
+MODES = {   # name of the second mode -> the arguments of t2i_generate_ar that select it (the first mode is always the default call)
+    "deterministic": {"deterministic": True},
+    "truncated": {"top_k": 50, "top_p": 0.95},
+}
+
+
+def run_modes(second="deterministic", n_img=8, prefix=138, n_tok=256, rounds=5):
+    """Default vs a second mode (MODES: deterministic decode, or truncated sampling with top_k=50, top_p=0.95) in ONE process at the
+    bench shape, captured graph, the two modes alternating.  One kept session exists at a time and the mode is part of its key, so
+    each visit to a mode makes two calls and times the second (it replays the session the first one captured).  Prints both medians
+    and their ratio."""
     import statistics
     dev = torch.device("cuda:0")
     model = UniGen(w_und_encoder=False, vocab_size=VOCAB, llm_vocab_size=TEXT_VOCAB, llm_model_path="Qwen2.5-1.5B-Instruct",
@@ -61,32 +68,33 @@ def run_modes(n_img=8, prefix=138, n_tok=256, rounds=5):
     ids = torch.randint(0, 151643, (n_img, L), device=dev, generator=g)
     un = torch.randint(0, 151643, (n_img, L), device=dev, generator=g)
     am = torch.ones((2 * n_img, L), dtype=torch.long, device=dev)
-    times = {False: [], True: []}
+    modes = (("default", {"deterministic": False}), (second, {"deterministic": False, **MODES[second]}))
+    times = {name: [] for name, _ in modes}
     for _ in range(rounds):
-        for det in (False, True):
+        for name, kw in modes:
             for k in range(2):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 toks = model.t2i_generate_ar(input_ids=ids, uncond_input_ids=un, attention_mask=am, guidance_scale=6.0, temperature=1.0,
-                                             text_vocab_size=TEXT_VOCAB, image_token_num_per_image=n_tok, deterministic=det)
+                                             text_vocab_size=TEXT_VOCAB, image_token_num_per_image=n_tok, **kw)
                 torch.cuda.synchronize()
                 if k == 1:
-                    times[det].append(time.perf_counter() - t0)
-            assert model.llm.engine.last_decode_deterministic == det and model.llm.engine.last_decode_graph
+                    times[name].append(time.perf_counter() - t0)
+            assert model.llm.engine.last_decode_deterministic == kw["deterministic"] and model.llm.engine.last_decode_graph
             assert toks.shape == (n_img, n_tok) and int(toks.min()) >= 0 and int(toks.max()) < CODEBOOK
     out = {}
-    for det, name in ((False, "default"), (True, "deterministic")):
-        med = statistics.median(times[det])
+    for name, _ in modes:
+        med = statistics.median(times[name])
         out[name] = {"value": round(n_img * n_tok / med, 1), "unit": "img-tokens/s", "ms_per_step": round(med / n_tok * 1e3, 3),
-                     "calls_s": [round(t, 4) for t in times[det]]}
-    out["ratio"] = round(out["deterministic"]["value"] / out["default"]["value"], 4)
+                     "calls_s": [round(t, 4) for t in times[name]]}
+    out["ratio"] = round(out[second]["value"] / out["default"]["value"], 4)
     out.update({"images": n_img, "rows_with_cfg": 2 * n_img, "prefix": prefix, "decode_steps": n_tok, "graph": True})
     return out
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "--deterministic":
-        print(json.dumps(run_modes()), flush=True)
+    if len(sys.argv) > 1 and sys.argv[1] in ("--deterministic", "--truncated"):
+        print(json.dumps(run_modes(sys.argv[1][2:])), flush=True)
     elif len(sys.argv) > 1 and sys.argv[1] == "graph":          # profiling runs: the captured path only, one repetition after the warm-up
         print(json.dumps(run(use_graph=True, reps=3)), flush=True)
     else:
