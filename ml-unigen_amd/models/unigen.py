@@ -68,6 +68,40 @@ def _forgive_missing_anchor(module, incompatible_keys):
     incompatible_keys.missing_keys[:] = [k for k in incompatible_keys.missing_keys if not k.endswith("_ddp_anchor")]
 
 
+def text_token_loop(max_new_tokens, hn, pick, emit, head, embed, step):
+    """The token loop of every cached text generation (generate, mmu_generate, mmu_generate_batch), from the prefill's final-norm
+    hidden state `hn`: logits = head(hn) -> nxt = pick(logits) [R, 1] -> feed, stop = emit(i, nxt) -> hn = step(embed(feed)).
+    `emit` records token i and returns the ids to feed back and whether every row has finished; no decode step follows the last
+    token.  The engine comes in as the three callables, so the loop itself runs anywhere.  Returns the number of tokens emitted."""
+    for i in range(max_new_tokens):
+        feed, stop = emit(i, pick(head(hn)))
+        if stop or i + 1 == max_new_tokens:
+            return i + 1
+        hn = step(embed(feed))
+    return 0
+
+
+def emit_until_stop(out, stop, pad_token_id=None, lengths=None):
+    """The record and stop rule of the text loops: token i goes into out [R, new]; a row has finished once it has produced `stop` (an
+    id, or a 0-d / 1-D tensor of ids), and the loop stops when every row has.  pad_token_id (`generate`): a finished row is filled with it from
+    then on, before the token is recorded and fed back.  lengths [R] (`mmu_generate_batch`): a row's entry is set to end just after
+    its stop token.  stop None: no host sync, never stops early."""
+    done = torch.zeros(out.shape[0], dtype=torch.bool, device=out.device)
+
+    def emit(i, nxt):
+        if stop is not None and pad_token_id is not None:
+            nxt = torch.where(done[:, None], torch.full_like(nxt, int(pad_token_id)), nxt)
+        out[:, i] = nxt[:, 0]
+        if stop is None:
+            return nxt, False
+        hit = (nxt == stop).any(-1) & ~done
+        if lengths is not None:
+            lengths.masked_fill_(hit, i + 1)
+        done.logical_or_(hit)
+        return nxt, bool(done.all())
+    return emit
+
+
 class UniGen(ModelMixin, ConfigMixin):
     _supports_gradient_checkpointing = True
 
@@ -639,13 +673,12 @@ class UniGen(ModelMixin, ConfigMixin):
         # step + the capture).  A session = every buffer the graph reads or writes (cache, position, accumulators, token /
         # embedding slots, uniforms) + the graph; it is reused only when every size, every sampling constant baked into a kernel
         # argument and the weight storage are the same (UNIGEN_AR_GRAPH_CACHE=0 turns the reuse off), and dropped on any error.
-        sess_key = (R, P, n, bsz, V, int(text_vocab_size), greedy, float(guidance_scale), float(temperature), key_valid is None, str(dev),
-                    bool(getattr(eng, "decode_fused", True)), os.environ.get("UNIGEN_DECODE_SW", "1"),
+        form = eng.decode_form(R, det)               # (a captured step belongs to one layer form: its launches and scratch differ)
+        sess_key = (R, P, n, bsz, V, int(text_vocab_size), greedy, float(guidance_scale), float(temperature), key_valid is None, str(dev), form,
                     eng.fp.w("embed").data_ptr(), eng.fp.w("l0.wqkv").data_ptr(), eng.fp.p("embed").data_ptr(), eng.fp.p("norm").data_ptr(),
                     # (every other pointer the captured step bakes in lives in the same two flat buffers; the last layer's weights and the
                     # RoPE tables stand in for "nothing was reallocated in between")
                     eng.fp.w(f"l{eng.dims.num_hidden_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(P + n)),
-                    det,                                     # (a captured step belongs to one decode mode: its scratch differs)
                     filt)                                    # (the filter constants are kernel arguments of the captured sampler)
         sess = getattr(eng, "_ar_session", None) if (use_graph and fused and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0") else None
         if sess is not None and sess["key"] != sess_key:
@@ -730,7 +763,7 @@ class UniGen(ModelMixin, ConfigMixin):
             out_tokens[:, 0] = tok[:, 0]
 
         # single-writer layer (csrc/decode_sw.hip): the final RMSNorm and the head slice are ONE launch behind the last layer
-        sw_head = fused and (eng.decode_ord_sw(st) if det else eng.decode_sw(st))
+        sw_head = fused and form in ("sw", "ord_sw")
 
         def step():
             if sw_head:
@@ -806,33 +839,19 @@ class UniGen(ModelMixin, ConfigMixin):
         eng.last_decode_deterministic = det
         hn = eng.prefill(st, prompt, key_valid)
         eng.check_errors()
-        V = self.config.vocab_size
-        x = torch.empty((R, eng.dims.hidden_size), dtype=torch.float32, device=dev)
         out = torch.full((R, max_new_tokens), int(pad_token_id or 0), dtype=torch.long, device=dev)
-        done = torch.zeros(R, dtype=torch.bool, device=dev)
-        n_out = 0
-        for i in range(max_new_tokens):
-            last = eng.head_slice(hn, 0, V).float()
-            if do_sample:
-                if temperature is not None and temperature != 1.0:
-                    last = last / temperature
-                last = top_k_top_p_filtering(last, top_k=int(top_k or 0), top_p=float(1.0 if top_p is None else top_p))
-                u_dev = dev if generator is None else generator.device
-                nxt = torch.multinomial(torch.softmax(last, dim=-1).to(u_dev), num_samples=1, generator=generator).to(dev)
-            else:
-                nxt = last.argmax(-1, keepdim=True)
-            if eos:
-                nxt = torch.where(done[:, None], torch.full_like(nxt, int(pad_token_id)), nxt)
-            out[:, i] = nxt[:, 0]
-            n_out = i + 1
-            if eos:
-                done |= torch.isin(nxt[:, 0], torch.tensor(eos, device=dev))
-                if bool(done.all()):
-                    break
-            if i + 1 < max_new_tokens:
-                x.copy_(embed(nxt)[:, 0])
-                hn = eng.decode_step(st, x)            # (also advances the cache position)
-        out = out[:, :n_out]
+
+        def pick(last):
+            if not do_sample:
+                return last.argmax(-1, keepdim=True)
+            if temperature is not None and temperature != 1.0:
+                last = last / temperature
+            last = top_k_top_p_filtering(last, top_k=int(top_k or 0), top_p=float(1.0 if top_p is None else top_p))
+            u_dev = dev if generator is None else generator.device
+            return torch.multinomial(torch.softmax(last, dim=-1).to(u_dev), num_samples=1, generator=generator).to(dev)
+
+        stop = torch.tensor(eos, device=dev) if eos else None
+        out = out[:, :self._decode_text(st, hn, max_new_tokens, pick, emit_until_stop(out, stop, pad_token_id))]
         if input_embeddings is None:
             return torch.cat([input_ids.to(dev), out], dim=1)
         return out
@@ -864,32 +883,40 @@ class UniGen(ModelMixin, ConfigMixin):
             return torch.multinomial(torch.softmax(last, dim=-1), num_samples=1)
         return torch.argmax(last, dim=-1).reshape(-1, 1)
 
-    @torch.no_grad()
-    def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False):
+    def _decode_text(self, st, hn, max_new_tokens, pick, emit):
+        """text_token_loop on this model's engine from a prefilled state: vocabulary logits, embedding table, decode_step."""
+        eng, embed, V = self.llm.engine, self.llm.model.embed_tokens, self.config.vocab_size
+        x = torch.empty((st.rows, eng.dims.hidden_size), dtype=torch.float32, device=hn.device)
+        return text_token_loop(max_new_tokens, hn, pick, emit, head=lambda hn: eng.head_slice(hn, 0, V).float(),
+                               embed=lambda ids: x.copy_(embed(ids)[:, 0]),
+                               step=lambda x: eng.decode_step(st, x))            # (also advances the cache position)
+
+    def _mmu_decode(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det):
+        """Prefill R left-padded rows under their dense [R, 1, L, L] masks, then decode -> (tokens [R, max_new_tokens] on the device,
+        the rows' lengths cut after `eot_token` [R], the number of steps taken)."""
         from unigen_hip.qwen2 import DecodeState
         eng = self.llm.engine
-        embed = self.llm.model.embed_tokens
-        prompt = (embed(idx) if input_embeddings is None else input_embeddings).float()
+        prompt = (self.llm.model.embed_tokens(idx) if input_embeddings is None else input_embeddings).float()
         dev = prompt.device
-        L = prompt.shape[1]
-        mb = eng.mask_bits(attention_mask, 1, L)
+        R, L = prompt.shape[0], prompt.shape[1]
+        mb = eng.mask_bits(attention_mask, R, L)
         eng.check_errors()
-        key_valid = (attention_mask.reshape(L, L)[-1] == 0).view(1, L)
-        st = DecodeState(eng.dims, 1, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
+        key_valid = attention_mask[:, 0, -1, :] == 0
+        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, mask_bits=mb)
-        V = self.config.vocab_size
-        x = torch.empty((1, eng.dims.hidden_size), dtype=torch.float32, device=dev)
-        result = []
-        for i in range(max_new_tokens):
-            last = eng.head_slice(hn, 0, V).float()
-            idx_next = self._pick_next(last, temperature, top_k)
-            result.append(idx_next[0][0])
-            if eot_token is not None and idx_next.cpu() == eot_token:
-                break
-            if i + 1 < max_new_tokens:
-                x.copy_(embed(idx_next)[:, 0])
-                hn = eng.decode_step(st, x)            # (also advances the cache position)
-        return result
+        tokens = torch.zeros((R, max_new_tokens), dtype=torch.long, device=dev)
+        lengths = torch.full((R,), max_new_tokens, dtype=torch.long, device=dev)
+        steps = self._decode_text(st, hn, max_new_tokens, lambda last: self._pick_next(last, temperature, top_k),
+                                  emit_until_stop(tokens, eot_token, lengths=lengths))
+        return tokens, lengths, steps
+
+    @torch.no_grad()
+    def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False):
+        """The one-row case of the batch path -> list of 0-d device tensors (one row: it ends at its `eot_token`, so every step counts)."""
+        L = attention_mask.shape[-1]
+        tokens, _, steps = self._mmu_decode(idx, input_embeddings, attention_mask.reshape(1, 1, L, L), max_new_tokens, temperature, top_k,
+                                            eot_token, det)
+        return list(tokens[0, :steps])
 
     @torch.no_grad()
     def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=0.0,
@@ -902,41 +929,15 @@ class UniGen(ModelMixin, ConfigMixin):
         procedure of `mmu_generate`: prefill under its mask, then one decode step per token attending to the keys its
         last prompt row could see plus everything generated since.  Returns R lists of tokens, each cut after its
         `eot_token`.  deterministic: ordered decode kernels; None follows torch.are_deterministic_algorithms_enabled()."""
-        from unigen_hip.qwen2 import DecodeState, resolve_deterministic
-        eng = self.llm.engine
+        from unigen_hip.qwen2 import resolve_deterministic
         det = resolve_deterministic(deterministic)
-        eng.last_decode_deterministic = det
-        embed = self.llm.model.embed_tokens
-        prompt = (embed(idx) if input_embeddings is None else input_embeddings).float()
-        dev = prompt.device
-        R, L = prompt.shape[0], prompt.shape[1]
+        self.llm.engine.last_decode_deterministic = det
+        R, L = (idx if input_embeddings is None else input_embeddings).shape[:2]
         if R > 32:
             raise ValueError("mmu_generate_batch: at most 32 rows per call")
         if attention_mask is None or tuple(attention_mask.shape) != (R, 1, L, L):
             raise ValueError("mmu_generate_batch: attention_mask must be the rows' dense [R, 1, L, L] additive masks")
-        mb = eng.mask_bits(attention_mask, R, L)
-        eng.check_errors()
-        key_valid = attention_mask[:, 0, -1, :] == 0
-        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
-        hn = eng.prefill(st, prompt, mask_bits=mb)
-        V = self.config.vocab_size
-        x = torch.empty((R, eng.dims.hidden_size), dtype=torch.float32, device=dev)
-        tokens = torch.zeros((R, max_new_tokens), dtype=torch.long, device=dev)
-        done = torch.zeros(R, dtype=torch.bool, device=dev)
-        lengths = torch.full((R,), max_new_tokens, dtype=torch.long, device=dev)
-        for i in range(max_new_tokens):
-            last = eng.head_slice(hn, 0, V).float()
-            idx_next = self._pick_next(last, temperature, top_k)
-            tokens[:, i] = idx_next[:, 0]
-            if eot_token is not None:
-                hit = (idx_next[:, 0] == eot_token) & ~done
-                lengths = torch.where(hit, torch.full_like(lengths, i + 1), lengths)
-                done |= hit
-                if bool(done.all()):
-                    break
-            if i + 1 < max_new_tokens:
-                x.copy_(embed(idx_next)[:, 0])
-                hn = eng.decode_step(st, x)            # (also advances the cache position)
+        tokens, lengths, _ = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det)
         tokens, lengths = tokens.cpu(), lengths.cpu()
         return [list(tokens[r, :int(lengths[r])]) for r in range(R)]
 
@@ -954,14 +955,7 @@ class UniGen(ModelMixin, ConfigMixin):
             grown[L, :L] = m[-1]
             grown[L, L] = 0
             attention_mask = grown[None, None]
-            if temperature > 0:
-                last = last / temperature
-                if top_k is not None:
-                    v, _ = torch.topk(last, min(top_k, last.size(-1)))
-                    last[last < v[:, [-1]]] = -float('Inf')
-                idx_next = torch.multinomial(torch.softmax(last, dim=-1), num_samples=1)
-            else:
-                idx_next = torch.argmax(last, dim=-1).reshape(-1, 1)
+            idx_next = self._pick_next(last, temperature, top_k)
             result.append(idx_next[0][0])
             if self.config.w_und_encoder:
                 input_embeddings = torch.cat([input_embeddings, self.llm.model.embed_tokens(idx_next)], dim=1)

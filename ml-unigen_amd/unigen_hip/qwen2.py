@@ -177,6 +177,69 @@ def _hf_name_map(dims):
     return m
 
 
+def resolve_deterministic(deterministic=None):
+    """The decode mode of a generation call: `deterministic` if given, else torch's global flag
+    (torch.use_deterministic_algorithms)."""
+    return torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
+
+
+class DecodeState:
+    """Static KV cache for autoregressive generation: per layer K,V [rows][HKV][Tmax][128] bf16, the write
+    position and visible length as DEVICE ints (so one captured graph serves every step).
+    deterministic: the decode steps on this state use the ORDERED forms (no float atomics: every split-K partial lands in a slot
+    of its own and its consumer sums the slots in ascending order), so the same inputs give the same bits on every run, eager or
+    captured.  The state's scratch is then partial slots instead of accumulators, so a captured step belongs to one mode."""
+
+    def __init__(self, dims, rows, Tmax, device, key_valid=None, deterministic=False):
+        self.rows, self.Tmax = rows, Tmax
+        self.deterministic = bool(deterministic)
+        n, hk, hd = dims.num_hidden_layers, dims.num_key_value_heads, dims.head_dim
+        self.k = [torch.zeros((rows, hk, Tmax, hd), dtype=torch.bfloat16, device=device) for _ in range(n)]
+        self.v = [torch.zeros((rows, hk, Tmax, hd), dtype=torch.bfloat16, device=device) for _ in range(n)]
+        self.pos = torch.zeros(1, dtype=torch.int32, device=device)
+        self.len = torch.zeros(1, dtype=torch.int32, device=device)
+        self.key_valid = None
+        if key_valid is not None:
+            kv = torch.ones((rows, Tmax), dtype=torch.uint8, device=device)
+            kv[:, :key_valid.shape[1]] = key_valid.to(device=device, dtype=torch.uint8)
+            self.key_valid = kv
+
+    def advance(self):
+        self.pos.add_(1)
+        self.len.add_(1)
+
+    def ensure_scratch(self, dims, form):
+        """Persistent scratch of one decode layer form (Qwen2Engine.decode_form), allocated on first use.
+        splitk: one raw fp32 accumulator per split-K projection (row-major [rows][N]; each is cleared by a later launch once fully
+        consumed), the second residual-stream buffer, and the row sum-of-squares slots that carry the RMSNorm statistics to the
+        accumulators' consumers.
+        sw: the o and gate/up projections are single-writer launches (csrc/decode_sw.hip) -- no gate/up or o accumulator, a finished
+        bf16 `act` instead, and two down-projection accumulators that alternate by layer: layer l adds into acc_down (l even) or
+        acc_down2 (l odd) and clears the other one, which layer l - 1 left and layer l's q/k/v launch has consumed.  The last layer's
+        accumulator is cleared by its reader when that is the final-norm launch of decode_step; the head launch of decode_step_logits
+        leaves it as it is, so at odd depth (where it is acc_down, the one layer 0 adds into) layer 0's q/k/v launch of the next step
+        clears it.
+        ord_sw: the q/k/v k-slab slots [6][rows][q/k/v width] with their row statistics [6][32], ONE set of down-projection k-block
+        slots [5][rows][hidden] (layer l + 1's q/k/v launch consumes them before layer l + 1's down projection rewrites them: no second
+        set, no clears), the second residual-stream buffer and `act`.  The wide forms keep no scratch."""
+        if getattr(self, {"splitk": "acc_gu", "sw": "acc_down2", "ord_sw": "qkv_part"}[form], None) is not None:
+            return                                 # (every step asks; the buffer only this form has says it is all there)
+        dev = self.pos.device
+        R, H, I = self.rows, dims.hidden_size, dims.intermediate_size
+        nqkv = (dims.num_attention_heads + 2 * dims.num_key_value_heads) * dims.head_dim
+        z = lambda *shape: lambda: torch.zeros(shape, dtype=torch.float32, device=dev)
+        e = lambda *shape: lambda: torch.empty(shape, dtype=torch.float32, device=dev)
+        act = lambda: torch.empty((R, I), dtype=torch.bfloat16, device=dev)
+        acc = {"acc_qkv": z(R, nqkv), "acc_down": z(R, H), "x_mid": z(R, H), "ss_attn": z(32), "ss_mlp": z(32)}
+        want = {"splitk": {**acc, "acc_o": z(R, H), "acc_gu": z(R, 2 * I)},
+                "sw": {**acc, "zeros": z(R, H), "act": act, "acc_down2": z(R, H)},
+                "ord_sw": {"ss_part": e(ops.ORD_QKV_SLABS, 32), "down_part": e(ops.ORD_DOWN_KBLOCKS, R, H), "x_mid": z(R, H), "act": act,
+                           "qkv_part": e(ops.ORD_QKV_SLABS, R, nqkv)}}[form]               # (the form's own buffer last)
+        for name, make in want.items():
+            if getattr(self, name, None) is None:
+                setattr(self, name, make())
+
+
 class _Saved:
     __slots__ = ("h", "rstd1", "xn1", "qkv", "o", "lse", "h_mid", "rstd2", "xn2", "gu", "act")
 
@@ -354,8 +417,6 @@ class Qwen2Engine:
         # dlogits pad columns are zero (ug_ce_bwd), so K = V needs no padding
         return ops.gemm(dlogits, fp.w("embed"), M=R, N=d.hidden_size, K=d.vocab_size, b_kmajor=True)
 
-
-def _head_deferral_methods(cls):
     def _may_defer_head_wgrad(self, R):
         """Only inside a backward pass (the end-of-backward callback is the safety net), on the single-GPU path (with a gradient
         exchange the table's dense part is handed over right after the head instead, unigen_hip/ddp.py), and when the layers'
@@ -412,79 +473,7 @@ def _head_deferral_methods(cls):
         ops.gemm(dlogits[:, v0:], hn_rows, out=self.fp.g("embed")[v0:], M=V - v0, N=H, K=hn_rows.shape[0], a_kmajor=True,
                  b_kmajor=True, epilogue=ops.UG_EPI_F32, beta=beta)
 
-    cls._may_defer_head_wgrad, cls._head_wgrad_slice, cls.flush_deferred_head = _may_defer_head_wgrad, _head_wgrad_slice, flush_deferred_head
-    return cls
-
-
-def resolve_deterministic(deterministic=None):
-    """The decode mode of a generation call: `deterministic` if given, else torch's global flag
-    (torch.use_deterministic_algorithms)."""
-    return torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
-
-
-class DecodeState:
-    """Static KV cache for autoregressive generation: per layer K,V [rows][HKV][Tmax][128] bf16, the write
-    position and visible length as DEVICE ints (so one captured graph serves every step).
-    deterministic: the decode steps on this state use the ORDERED forms (no float atomics: every split-K partial lands in a slot
-    of its own and its consumer sums the slots in ascending order), so the same inputs give the same bits on every run, eager or
-    captured.  The state's scratch is then partial slots instead of accumulators, so a captured step belongs to one mode."""
-
-    def __init__(self, dims, rows, Tmax, device, key_valid=None, deterministic=False):
-        self.rows, self.Tmax = rows, Tmax
-        self.deterministic = bool(deterministic)
-        n, hk, hd = dims.num_hidden_layers, dims.num_key_value_heads, dims.head_dim
-        self.k = [torch.zeros((rows, hk, Tmax, hd), dtype=torch.bfloat16, device=device) for _ in range(n)]
-        self.v = [torch.zeros((rows, hk, Tmax, hd), dtype=torch.bfloat16, device=device) for _ in range(n)]
-        self.pos = torch.zeros(1, dtype=torch.int32, device=device)
-        self.len = torch.zeros(1, dtype=torch.int32, device=device)
-        self.key_valid = None
-        if key_valid is not None:
-            kv = torch.ones((rows, Tmax), dtype=torch.uint8, device=device)
-            kv[:, :key_valid.shape[1]] = key_valid.to(device=device, dtype=torch.uint8)
-            self.key_valid = kv
-
-    def advance(self):
-        self.pos.add_(1)
-        self.len.add_(1)
-
-    def ensure_accumulators(self, dims, sw=False):
-        """Persistent scratch of the five-launch decode layer: one raw fp32 accumulator per split-K projection (row-major
-        [rows][N]; each is cleared by a later launch once fully consumed), the second residual-stream buffer, and the row
-        sum-of-squares slots that carry the RMSNorm statistics to the accumulators' consumers.  sw: the layer whose o and gate/up
-        projections are single-writer launches (csrc/decode_sw.hip) -- no gate/up or o accumulator, a finished bf16 `act` instead,
-        and two down-projection accumulators that alternate by layer: layer l adds into acc_down (l even) or acc_down2 (l odd) and
-        clears the other one, which layer l - 1 left and layer l's q/k/v launch has consumed.  The last layer's accumulator is
-        cleared by its reader when that is the final-norm launch of decode_step; the head launch of decode_step_logits leaves it
-        as it is, so at odd depth (where it is acc_down, the one layer 0 adds into) layer 0's q/k/v launch of the next step clears it."""
-        dev = self.pos.device
-        nqkv = (dims.num_attention_heads + 2 * dims.num_key_value_heads) * dims.head_dim
-        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-        if getattr(self, "acc_qkv", None) is None:
-            self.acc_qkv, self.acc_down = z(self.rows, nqkv), z(self.rows, dims.hidden_size)
-            self.x_mid = z(self.rows, dims.hidden_size)
-            self.ss_attn, self.ss_mlp = z(32), z(32)
-        if sw and getattr(self, "act", None) is None:
-            self.acc_down2, self.zeros = z(self.rows, dims.hidden_size), z(self.rows, dims.hidden_size)
-            self.act = torch.empty((self.rows, dims.intermediate_size), dtype=torch.bfloat16, device=dev)
-        if not sw and getattr(self, "acc_gu", None) is None:
-            self.acc_gu, self.acc_o = z(self.rows, 2 * dims.intermediate_size), z(self.rows, dims.hidden_size)
-
-    def ensure_parts(self, dims):
-        """Scratch of the ordered single-writer layer: the q/k/v k-slab slots [6][rows][q/k/v width] with their row statistics [6][32],
-        ONE set of down-projection k-block slots [5][rows][hidden] (layer l + 1's q/k/v launch consumes them before layer l + 1's down
-        projection rewrites them: no second set, no clears), the second residual-stream buffer and the finished bf16 `act`."""
-        if getattr(self, "qkv_part", None) is not None:
-            return
-        dev = self.pos.device
-        nqkv = (dims.num_attention_heads + 2 * dims.num_key_value_heads) * dims.head_dim
-        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        self.qkv_part, self.ss_part = e(ops.ORD_QKV_SLABS, self.rows, nqkv), e(ops.ORD_QKV_SLABS, 32)
-        self.down_part = e(ops.ORD_DOWN_KBLOCKS, self.rows, dims.hidden_size)
-        self.x_mid = torch.zeros((self.rows, dims.hidden_size), dtype=torch.float32, device=dev)
-        self.act = torch.empty((self.rows, dims.intermediate_size), dtype=torch.bfloat16, device=dev)
-
-
-def _decode_methods(cls):
+    # ---------------------------------------------------------------- autoregressive decode
     def prefill(self, st, embeds, key_valid=None, mask_bits=None):
         """embeds fp32 [rows, P, H] -> final-norm hidden of the LAST position, bf16 [rows, H]; fills the cache.
         mask_bits: compressed [rows, P, P] mask of the prompt (default: causal with `key_valid` columns)."""
@@ -503,18 +492,36 @@ def _decode_methods(cls):
         hn, _ = ops.rmsnorm_fwd(h, self.fp.p("norm"), d.rms_norm_eps, want_rstd=False)
         return hn.view(R, P, H)[:, -1].contiguous()
 
-    def decode_sw(self, st):
-        """Whether this decode state runs the layer with single-writer o / gate-up / head launches (csrc/decode_sw.hip)."""
+    def decode_form(self, rows, deterministic):
+        """The layer form of a decode step on `rows` rows -- the ONE place that chooses it; recomputed on every call, since
+        `decode_fused` and UNIGEN_DECODE_SW may change between states on one engine:
+          sw        split-K q/k/v and down, single-writer o / gate-up / head launches (csrc/decode_sw.hip): <= 16 rows at the widths
+                    those kernels are built for
+          splitk    five split-K launches per layer: up to 32 rows, or UNIGEN_DECODE_SW=0
+          wide      separate kernels around skinny GEMMs: `decode_fused = False`, > 32 rows, or sizes the GEMV kernels do not take
+          ord_sw    deterministic: the ordered single-writer layer (hidden 1536, intermediate 5 x 1792)
+          ord_wide  deterministic, everything else: the wide form on ordered skinny linears
+        An intermediate size that is below 256 or no multiple of 32 takes the wide form whatever else holds (decode_sw() used to
+        answer True there at the 1536-wide dims, and t2i_generate_ar then ran into a launch that refuses the size)."""
         d = self.dims
-        return (getattr(self, "decode_fused", True) and os.environ.get("UNIGEN_DECODE_SW", "1") != "0" and st.rows <= 16
-                and ops.decode_sw_supported(d.hidden_size, d.intermediate_size, d.num_attention_heads * d.head_dim, d.head_dim))
+        H, I, hd, q_dim = d.hidden_size, d.intermediate_size, d.head_dim, d.num_attention_heads * d.head_dim
+        fused = getattr(self, "decode_fused", True)
+        sw_ok = (fused and os.environ.get("UNIGEN_DECODE_SW", "1") != "0" and rows <= 16
+                 and ops.decode_sw_supported(H, I, q_dim, hd))
+        if deterministic:
+            ord_dims = H == 256 * ops.ORD_QKV_SLABS and I == 1792 * ops.ORD_DOWN_KBLOCKS and d.num_hidden_layers >= 1
+            return "ord_sw" if sw_ok and ord_dims else "ord_wide"
+        if not fused or rows > 32 or hd != 128 or min(H, I, q_dim) < 256 or H % 32 or I % 32:
+            return "wide"
+        return "sw" if sw_ok else "splitk"
+
+    def decode_sw(self, st):
+        """Whether a default-mode decode state of st.rows rows runs the single-writer layer."""
+        return self.decode_form(st.rows, False) == "sw"
 
     def decode_ord_sw(self, st):
-        """Whether a deterministic decode state runs the ordered single-writer layer (the sizes its kernels are built for: hidden 1536,
-        intermediate 5 x 1792); every other deterministic shape takes the ordered wide form."""
-        d = self.dims
-        return (self.decode_sw(st) and d.hidden_size == 256 * ops.ORD_QKV_SLABS and d.intermediate_size == 1792 * ops.ORD_DOWN_KBLOCKS
-                and d.num_hidden_layers >= 1)
+        """Whether a deterministic decode state of st.rows rows runs the ordered single-writer layer."""
+        return self.decode_form(st.rows, True) == "ord_sw"
 
     def _decode_layers_ord(self, st, x):
         """The decoder stack of one deterministic decode step, five launches per layer as _decode_layers_sw, without float atomics:
@@ -523,12 +530,12 @@ def _decode_methods(cls):
           attention  sums the 6 slots in slab order in its prologue, then finishes q/k/v as the default form does
           o, gate/up the single-writer launches of the default form (already one writer per element)
           down       k-blocks with the partial tile STORED into the k-block's slot (5 slots)
-        -> the residual stream after the last layer is stream + bf16round(sum of st.down_part)."""
+        -> (stream, pending): the residual stream after the last layer is stream + bf16round(sum of pending = st.down_part)."""
         d, fp = self.dims, self.fp
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
         H = d.hidden_size
         cos, sin = self.rope(st.Tmax)
-        st.ensure_parts(d)
+        st.ensure_scratch(d, "ord_sw")
         eps = d.rms_norm_eps
         o = torch.empty((st.rows, Hq * hd), dtype=torch.bfloat16, device=x.device)
         bufs = (x, st.x_mid)
@@ -542,7 +549,7 @@ def _decode_methods(cls):
             ops.decode_sw_resid_(o, fp.w(f"l{i}.wo"), xout)
             ops.decode_sw_gate_up_(xout, fp.p(f"l{i}.ln2"), eps, fp.w(f"l{i}.wgu"), st.act)
             ops.decode_sw_kblock_ord_(st.act, fp.w(f"l{i}.wdown"), st.down_part)
-        return bufs[n & 1]
+        return bufs[n & 1], st.down_part
 
     def _decode_layers_sw(self, st, x):
         """The decoder stack of one decode step, five launches per layer (measured forms: profiles/r06_decode_forms.md):
@@ -559,7 +566,7 @@ def _decode_methods(cls):
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
         R, H = st.rows, d.hidden_size
         cos, sin = self.rope(st.Tmax)
-        st.ensure_accumulators(d, sw=True)
+        st.ensure_scratch(d, "sw")
         eps = d.rms_norm_eps
         o = torch.empty((R, Hq * hd), dtype=torch.bfloat16, device=x.device)
         bufs, accd = (x, st.x_mid), (st.acc_down, st.acc_down2)
@@ -581,53 +588,16 @@ def _decode_methods(cls):
             down(st.act, fp.w(f"l{i}.wdown"), accd[i & 1], zero0=st.acc_qkv, zero1=accd[(i + 1) & 1], ss_zero=st.ss_attn)
         return bufs[n & 1], accd[(n - 1) & 1]
 
-    def decode_step_logits(self, st, x, w_head, logits):
-        """decode_step + the head slice in one go (single-writer layer only): logits fp32 [rows, N] = rows `w_head` of the tied
-        embedding applied to the final-norm hidden state; advances st.pos / st.len.  The final RMSNorm and the last layer's
-        pending residual add ride in the head launch's prologue.
-        Deterministic state: the last layer's down slots are summed in order by their own launch ahead of the head (ordered
-        single-writer layer), or the step runs the ordered wide form and the head is an ordered skinny GEMV."""
-        self.last_decode_deterministic = st.deterministic
-        if st.deterministic:
-            if not self.decode_ord_sw(st):
-                hn = self.decode_step(st, x)
-                return ops.skinny_linear_ord(hn, w_head, out_f32=logits)
-            stream = self._decode_layers_ord(st, x)
-            ops.decode_finish_resid_norm_ord_(st.down_part, stream, self.fp.p("norm"), None, self.dims.rms_norm_eps)
-            ops.decode_sw_head_(stream, self.fp.p("norm"), self.dims.rms_norm_eps, w_head, logits, advance=(st.pos, st.len))
-            return logits
-        stream, pending = self._decode_layers_sw(st, x)
-        ops.decode_sw_head_(stream, self.fp.p("norm"), self.dims.rms_norm_eps, w_head, logits, pend=pending, advance=(st.pos, st.len))
-        return logits
-
-    def decode_step(self, st, x):
-        """x fp32 [rows, H] = embedding of the newest token (updated in place as the residual stream);
-        appends its K/V at st.pos, ADVANCES st.pos / st.len by one and returns the final-norm hidden bf16 [rows, H].  No host sync, no
-        shape depends on the step: capturable.  Five launches per layer (see include/unigen_hip.h): a split-K
-        projection leaves its raw fp32 accumulator behind and the NEXT kernel applies bias / RoPE / residual add /
-        RMSNorm / SiLU-mul while it builds its own operand, so kernel boundaries are the only synchronisation."""
+    def _decode_layers_splitk(self, st, x):
+        """The decoder stack of one decode step as five split-K launches per layer (see include/unigen_hip.h): a split-K projection leaves
+        its raw fp32 accumulator behind and the NEXT kernel applies bias / RoPE / residual add / RMSNorm / SiLU-mul while it builds its
+        own operand, so kernel boundaries are the only synchronisation.
+        -> (stream, pending): the residual stream after the last layer is stream + bf16round(pending = st.acc_down)."""
         d, fp = self.dims, self.fp
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
-        R, H, I = st.rows, d.hidden_size, d.intermediate_size
-        self.last_decode_deterministic = st.deterministic
-        if st.deterministic:
-            if not self.decode_ord_sw(st):
-                return self._decode_step_wide(st, x)
-            hn = torch.empty((R, H), dtype=torch.bfloat16, device=x.device)
-            stream = self._decode_layers_ord(st, x)
-            ops.decode_finish_resid_norm_ord_(st.down_part, stream, fp.p("norm"), hn, d.rms_norm_eps, advance=(st.pos, st.len))
-            return hn
-        if not getattr(self, "decode_fused", True) or R > 32 or hd != 128 or min(H, I, Hq * hd) < 256 or H % 32 or I % 32:
-            return self._decode_step_wide(st, x)
-        eps = d.rms_norm_eps
-        hn = torch.empty((R, H), dtype=torch.bfloat16, device=x.device)
-        if self.decode_sw(st):
-            stream, pending = self._decode_layers_sw(st, x)
-            # pending down_proj of the last layer + final RMSNorm (also clears that accumulator)
-            ops.decode_finish_resid_norm_(pending, stream, fp.p("norm"), hn, eps, advance=(st.pos, st.len))
-            return hn
+        R, H, eps = st.rows, d.hidden_size, d.rms_norm_eps
         cos, sin = self.rope(st.Tmax)
-        st.ensure_accumulators(d)
+        st.ensure_scratch(d, "splitk")
         o = torch.empty((R, Hq * hd), dtype=torch.bfloat16, device=x.device)
         for i in range(d.num_hidden_layers):
             # x (+ pending down_proj of the previous layer) -> x_mid ; q/k/v accumulator ; clears gate_up acc
@@ -639,12 +609,51 @@ def _decode_methods(cls):
             # x_mid + pending o_proj -> x ; gate/up accumulator
             ops.decode_gemv_resid_norm_(st.x_mid, st.acc_o, fp.p(f"l{i}.ln2"), x, st.ss_mlp, fp.w(f"l{i}.wgu"), st.acc_gu)
             ops.decode_gemv_swiglu_(st.acc_gu, st.ss_mlp, eps, H, fp.w(f"l{i}.wdown"), st.acc_down, zero0=st.acc_o)
-        # pending down_proj of the last layer + final RMSNorm (also clears acc_down for the next step)
-        ops.decode_finish_resid_norm_(st.acc_down, x, fp.p("norm"), hn, eps, advance=(st.pos, st.len))
+        return x, st.acc_down
+
+    def _decode_layers(self, form, st, x):
+        layers = {"sw": self._decode_layers_sw, "splitk": self._decode_layers_splitk, "ord_sw": self._decode_layers_ord}
+        return layers[form](st, x)
+
+    def decode_step_logits(self, st, x, w_head, logits):
+        """decode_step + the head slice in one go: logits fp32 [rows, N] = rows `w_head` of the tied embedding applied to the final-norm
+        hidden state; advances st.pos / st.len.  Exists for the forms sw, ord_sw and ord_wide; splitk and wide have no head launch and
+        are refused before anything is launched (nothing is appended to the cache).
+        sw: the final RMSNorm and the last layer's pending residual add ride in the head launch's prologue.  ord_sw: the last layer's
+        down slots are summed in order by their own launch ahead of the head.  ord_wide: the wide step, then an ordered skinny GEMV."""
+        d, fp = self.dims, self.fp
+        form = self.decode_form(st.rows, st.deterministic)
+        if form in ("splitk", "wide"):
+            raise UniGenHipError(f"decode_step_logits: {st.rows} rows on this engine take the {form} decode form, which has no head "
+                                 f"launch (decode_step + a head GEMV serve it)")
+        self.last_decode_deterministic = st.deterministic
+        if form == "ord_wide":
+            return ops.skinny_linear_ord(self._decode_step_wide(st, x), w_head, out_f32=logits)
+        stream, pending = self._decode_layers(form, st, x)
+        if form == "ord_sw":
+            ops.decode_finish_resid_norm_ord_(pending, stream, fp.p("norm"), None, d.rms_norm_eps)
+            pending = None
+        ops.decode_sw_head_(stream, fp.p("norm"), d.rms_norm_eps, w_head, logits, pend=pending, advance=(st.pos, st.len))
+        return logits
+
+    def decode_step(self, st, x):
+        """x fp32 [rows, H] = embedding of the newest token (updated in place as the residual stream);
+        appends its K/V at st.pos, ADVANCES st.pos / st.len by one and returns the final-norm hidden bf16 [rows, H].  No host sync, no
+        shape depends on the step: capturable.  decode_form picks the layer form; its finisher adds the last layer's pending down
+        projection, applies the final RMSNorm and clears what the next step expects cleared."""
+        d, fp = self.dims, self.fp
+        self.last_decode_deterministic = st.deterministic
+        form = self.decode_form(st.rows, st.deterministic)
+        if form in ("wide", "ord_wide"):
+            return self._decode_step_wide(st, x)
+        hn = torch.empty((st.rows, d.hidden_size), dtype=torch.bfloat16, device=x.device)
+        stream, pending = self._decode_layers(form, st, x)
+        finish = ops.decode_finish_resid_norm_ord_ if form == "ord_sw" else ops.decode_finish_resid_norm_
+        finish(pending, stream, fp.p("norm"), hn, d.rms_norm_eps, advance=(st.pos, st.len))
         return hn
 
     def _decode_step_wide(self, st, x):
-        """> 32 rows: the GEMV kernel does not apply; split-K GEMMs + separate finishing kernels.  Deterministic state: every
+        """The wide and ord_wide forms: the GEMV kernels do not apply; split-K GEMMs + separate finishing kernels.  Deterministic state: every
         projection is the ordered skinny linear (per-k-slice partial slots in blocks of 32 rows, summed in slice order)."""
         d, fp = self.dims, self.fp
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
@@ -671,13 +680,3 @@ def _decode_methods(cls):
         out = torch.empty((hn.shape[0], ops.round_up(n, 8)), dtype=torch.bfloat16, device=self.device)
         ops.gemm(hn, self.fp.w("embed")[v0:v1], out=out, N=n, K=self.dims.hidden_size)
         return out[:, :n]
-
-    cls.prefill, cls.decode_step, cls.head_slice = prefill, decode_step, head_slice
-    cls.decode_sw, cls._decode_layers_sw, cls.decode_step_logits = decode_sw, _decode_layers_sw, decode_step_logits
-    cls._decode_step_wide = _decode_step_wide
-    cls.decode_ord_sw, cls._decode_layers_ord = decode_ord_sw, _decode_layers_ord
-    return cls
-
-
-_decode_methods(Qwen2Engine)
-_head_deferral_methods(Qwen2Engine)

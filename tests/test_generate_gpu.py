@@ -261,7 +261,8 @@ def test_decode_step_forms_agree_at_1p5b_width(dev, monkeypatch, R):
     """`Qwen2Engine.decode_step` at the 1.5B model's width (two layers): the shipped layer (round 6: split-K q/k/v + attention, single-writer
     o / gate-up, down in k-blocks; rows <= 16), the five-launch split-K layer (UNIGEN_DECODE_SW=0, and what 17-32 rows take) and the
     separate-kernel path (`decode_fused = False`) must give the same final-norm hidden state up to bf16 rounding, append the same k / v
-    and advance the position; `decode_step_logits` (final norm + head slice in one launch) must match the head applied to that state."""
+    and advance the position; `decode_step_logits` (final norm + head slice in one launch) must match the head applied to that state,
+    and at 17-32 rows, where no form has that launch, refuse without touching the state."""
     from models import UniGen
     from oracle import qwen2_ref, weights
     from unigen_hip import ops
@@ -306,4 +307,25 @@ def test_decode_step_forms_agree_at_1p5b_width(dev, monkeypatch, R):
             eng.decode_step_logits(st, xs[0].clone(), w_head, logits)
             ref = wide[0][0].to(torch.bfloat16).float() @ w_head.float().cpu().t()
             assert rel_err(logits, ref) < 1.5e-2 and int(st.pos.item()) == P + 1
+        else:
+            # 17-32 rows take the split-K form, which has no head launch: decode_step_logits refuses on the host, before any launch, so
+            # nothing has been appended or advanced, and the state then steps as a fresh one does.  Two runs of the split-K form differ in
+            # the order of their fp32 atomic adds, and a flipped bf16 rounding of an intermediate (operands, q/k/v, act) spreads through
+            # the layers behind it, so they are two bf16 evaluations of the step: held to the bar this test holds any two of those to
+            # (a consumed accumulator or a half-run layer is an error of order 1)
+            from unigen_hip.lib import UniGenHipError
+            monkeypatch.setenv("UNIGEN_DECODE_SW", "1")
+            eng.decode_fused = True
+            assert eng.decode_form(R, False) == "splitk"
+            st = DecodeState(eng.dims, R, P + steps, dev)
+            eng.prefill(st, prompt)
+            logits = torch.zeros(R, 2047, device=dev)
+            with pytest.raises(UniGenHipError, match="splitk"):
+                eng.decode_step_logits(st, xs[0].clone(), eng.fp.w("embed")[2048:4095], logits)
+            assert int(st.pos.item()) == P and int(st.len.item()) == P + 1
+            assert not st.k[0][:, :, P].any() and not st.v[0][:, :, P].any() and not logits.any()
+            h = eng.decode_step(st, xs[0].clone()).float().cpu()
+            e = rel_err(h, got[0][0])
+            print(f"decode_step after the refused decode_step_logits vs a fresh state: rel err {e:.3e} (bar 1.5e-2)")
+            assert e < 1.5e-2 and int(st.pos.item()) == P + 1
     eng.decode_fused = True
