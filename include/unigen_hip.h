@@ -162,7 +162,16 @@ int ug_attn_mask_causal(const uint8_t* key_valid /* [B,L] or null */, uint64_t* 
                         int64_t B, int64_t L, hipStream_t stream);
 /* replaces: torch SDPA in Qwen2Attention.forward (modeling_qwen2.py:196-234), GQA H:HKV, head_dim 128.
  * q/k/v: row (b*L+t), head h at column h*128, row stride ldq.
- * o: [tokens, ldo] bf16, lse: [B][H][L] fp32. */
+ * o: [tokens, ldo] bf16, lse: [B][H][L] fp32 (natural log of the sum of exp(scale * q.k) over the visible keys).
+ * Rows and keys the mask hides completely (left-padded prompts: ug_attn_mask_causal with key_valid):
+ *   - a query row that sees no key gets o = 0 (all bits zero) and lse = +INFINITY; ug_attn_bwd gives it dq = 0 and it adds
+ *     nothing to dk / dv;
+ *   - a key no query sees gets dk = dv = 0;
+ *   - every element of o, lse, dq, dk and dv is written, whatever the mask hides (whole hidden query or key tiles included).
+ *   - The q / dout rows of such query rows and the k / v rows of such keys are still READ and multiplied by exact-zero
+ *     probabilities in the matrix cores: they may hold any finite values (no bit of any other row depends on them), but not
+ *     NaN / Inf -- 0 * NaN = NaN would spread to every row that shares the tile.  The callers keep them finite: an empty row
+ *     leaves attention as o = 0, so the next layer's projections of that row are finite. */
 int ug_attn_fwd(const void* q, const void* k, const void* v, int64_t ldq, void* o,
                 int64_t ldo, float* lse, const uint64_t* bits, const uint8_t* tileany, int64_t B, int64_t L,
                 int64_t Lp, int H, int HKV, int head_dim, float scale, hipStream_t stream);

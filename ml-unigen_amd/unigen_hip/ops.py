@@ -473,15 +473,19 @@ def t2i_assemble(text_ids, image_in, image_labels, max_seq_len, pad_id, soi_id, 
     return ids, attn, labels
 
 
-def attn_fwd(qkv, mb, H, HKV, hd, scale=None):
-    """qkv bf16 [B*L, (H+2*HKV)*hd] (q heads | k heads | v heads, RoPE already applied).  -> (o, lse)"""
+def attn_fwd(qkv, mb, H, HKV, hd, scale=None, out=None):
+    """qkv bf16 [B*L, (H+2*HKV)*hd] (q heads | k heads | v heads, RoPE already applied).  -> (o, lse); out = (o, lse) to write
+    into caller-owned tensors (every element is written)."""
     B, L, Lp = mb.B, mb.L, mb.Lp
     scale = 1.0 / math.sqrt(hd) if scale is None else scale
     q = qkv[:, : H * hd]
     k = qkv[:, H * hd: (H + HKV) * hd]
     v = qkv[:, (H + HKV) * hd:]
-    o = torch.empty((B * L, H * hd), dtype=torch.bfloat16, device=qkv.device)
-    lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
+    if out is not None:
+        o, lse = out
+    else:
+        o = torch.empty((B * L, H * hd), dtype=torch.bfloat16, device=qkv.device)
+        lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
     _l.check(_l.load().ug_attn_fwd(_p(q), _p(k), _p(v), qkv.stride(0), _p(o), o.stride(0), _p(lse), _p(mb.bits),
                                    _p(mb.tileany), B, L, Lp, H, HKV, hd, scale, _stream()), "ug_attn_fwd")
     return o, lse
@@ -499,16 +503,16 @@ def _dkv_workspace(tokens, width, device):
     return _DKV_WS[key]
 
 
-def attn_bwd(qkv, o, lse, dout, mb, H, HKV, hd, scale=None, split_heads=True, rope=None, dbias=None):
+def attn_bwd(qkv, o, lse, dout, mb, H, HKV, hd, scale=None, split_heads=True, rope=None, dbias=None, out=None):
     """-> dqkv bf16 [B*L, (H+2*HKV)*hd]: the gradient w.r.t. the post-RoPE q / k and v, or -- rope = (cos, sin) tables [L, hd/2] --
     w.r.t. the projection's own output (RoPE transposed where dq / dk are stored).  dbias (fp32 [(H+2*HKV)*hd]): += the column
-    sums of dqkv, the bias gradient of the fused projection."""
+    sums of dqkv, the bias gradient of the fused projection.  out: a caller-owned dqkv (every element is written)."""
     B, L, Lp = mb.B, mb.L, mb.Lp
     scale = 1.0 / math.sqrt(hd) if scale is None else scale
     q = qkv[:, : H * hd]
     k = qkv[:, H * hd: (H + HKV) * hd]
     v = qkv[:, (H + HKV) * hd:]
-    dqkv = torch.empty_like(qkv)
+    dqkv = torch.empty_like(qkv) if out is None else out
     dq = dqkv[:, : H * hd]
     dk = dqkv[:, H * hd: (H + HKV) * hd]
     dv = dqkv[:, (H + HKV) * hd:]
@@ -1116,14 +1120,15 @@ def colsum_f32_(x2d, out):
     return out
 
 
-def transpose_f32(x, rows=None, cols=None, *, batch=1, ld_in=None, stride_in=0, pad_to=4):
+def transpose_f32(x, rows=None, cols=None, *, batch=1, ld_in=None, stride_in=0, pad_to=4, out=None):
     """out[z][c][r] = x[z][r][c]; output rows are round_up(rows, pad_to) long with a zero tail.  x: 2-D [rows, cols] (batch 1) or
     any buffer described by (ld_in, stride_in).  -> [batch, cols, ld_out]."""
     rows = x.shape[-2] if rows is None else rows
     cols = x.shape[-1] if cols is None else cols
     ld_in = x.stride(-2) if ld_in is None else ld_in
     ld_out = round_up(rows, pad_to)
-    out = torch.empty((batch, cols, ld_out), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((batch, cols, ld_out), dtype=torch.float32, device=x.device)
     _l.check(_l.load().ug_transpose_f32(_p(x), ld_in, stride_in, _p(out), ld_out, cols * ld_out, rows, cols, batch, _stream()),
              "ug_transpose_f32")
     return out

@@ -74,6 +74,26 @@ def attention_ref(q, k, v, mask_add, scale):
     return torch.matmul(w, v.float())
 
 
+def attention_masked_ref(q, k, v, allow, scale, dtype=torch.float64):
+    """Masked attention with a boolean mask allow [B, L, L] (True = attend), GQA as above, in `dtype` on the inputs' device.
+    -> (o [B,H,L,d], lse [B,H,L]).  A query row that sees no key yields o = 0, lse = +inf and no gradient: blocked scores never
+    enter the differentiated path (torch.where on both sides of the exponential), so autograd returns exact zeros for them,
+    for empty rows and for keys no query sees -- the contract of ug_attn_fwd / ug_attn_bwd (include/unigen_hip.h)."""
+    rep = q.shape[1] // k.shape[1]
+    q, k, v = q.to(dtype), k.to(dtype).repeat_interleave(rep, dim=1), v.to(dtype).repeat_interleave(rep, dim=1)
+    a = allow[:, None]
+    live = a.any(-1, keepdim=True)
+    s = torch.matmul(q, k.transpose(2, 3)) * scale
+    zero, one = torch.zeros((), dtype=dtype, device=s.device), torch.ones((), dtype=dtype, device=s.device)
+    m = torch.where(a, s, torch.full((), float("-inf"), dtype=dtype, device=s.device)).amax(-1, keepdim=True).detach()
+    m = torch.where(live, m, zero)                              # the softmax does not depend on the shift: no gradient through it
+    e = torch.where(a, torch.exp(torch.where(a, s, m) - m), zero)
+    l = torch.where(live, e.sum(-1, keepdim=True), one)
+    o = torch.matmul(e / l, v)
+    lse = torch.where(live, m + torch.log(l), torch.full((), float("inf"), dtype=dtype, device=s.device))
+    return o, lse[..., 0]
+
+
 # F.cross_entropy(..., ignore_index=-100) as called at models/unigen.py:310-338
 def ce_ref(logits, labels, ignore_index=-100):
     return F.cross_entropy(logits.float(), labels, ignore_index=ignore_index)

@@ -415,10 +415,15 @@ def test_gemm_rejects_bad_args(dev):
 
 # ------------------------------------------------------------------ row ops
 def test_rmsnorm_fwd_bwd(dev):
+    """Forward: the register kernel takes widths up to 2048 (4 and 252 / 260 around one float4 per lane; 2048 its last), 2052 and 3584
+    run the two-pass kernel.  Backward: widths up to 2048 (2052 is refused); 7700 rows at 1536 columns leave the floor of 16 rows per
+    workgroup (the formula gives 20), so dw goes through many workgroups' atomics."""
     ops = _ops()
     from oracle.ops_ref import rmsnorm_ref, rmsnorm_bwd_ref
+    from unigen_hip.lib import UniGenHipError
     torch.manual_seed(0)
-    for rows, cols in [(37, 1536), (130, 256)]:
+    shapes = [(37, 1536), (130, 256)] + [(r, c) for c in (4, 252, 260, 2048, 2052, 3584) for r in (1, 5)] + [(7700, 1536)]
+    for rows, cols in shapes:
         x = torch.randn(rows, cols) * 3
         w = torch.randn(cols) * 0.1 + 1
         y, rstd = ops.rmsnorm_fwd(x.to(dev), w.to(dev), 1e-6)
@@ -430,6 +435,10 @@ def test_rmsnorm_fwd_bwd(dev):
         dres0 = torch.randn(rows, cols)
         dres = dres0.clone().to(dev)
         dw = torch.zeros(cols, device=dev)
+        if cols > 2048:
+            with pytest.raises(UniGenHipError):
+                ops.rmsnorm_bwd(dy.to(dev), x.to(dev), rstd, w.to(dev), dres, dw, want_bf16=True)
+            continue
         d16 = ops.rmsnorm_bwd(dy.to(dev), x.to(dev), rstd, w.to(dev), dres, dw, want_bf16=True)
         dx_ref, dw_ref = rmsnorm_bwd_ref(dy.float(), x, w, 1e-6)
         assert _rel(dres, dres0 + dx_ref) < 1e-5
@@ -462,19 +471,30 @@ def test_rope_fwd_bwd(dev):
 
 
 def test_swiglu_fwd_bwd(dev):
+    """(77, 512) as ever; I = 8 (one 16-byte chunk per token); 1031 x 4096: 1031 * 512 = 527 872 work items, past the grid cap of
+    2048 * 256, so the grid-stride loop runs twice for some lanes.  Row 0 starts with the gates that overflow exp(-g) and the zeros."""
     ops = _ops()
     from oracle.ops_ref import swiglu_ref
     torch.manual_seed(2)
-    gu = (torch.randn(77, 2 * 512) * 2).to(torch.bfloat16)
-    act = ops.swiglu_fwd(gu.to(dev))
-    ref = swiglu_ref(gu)                       # bf16 ops on CPU == the reference's autocast arithmetic
-    assert _maxabs(act, ref) <= 0.07 and _rel(act, ref) < 6e-3
-    dact = torch.randn(77, 512).to(torch.bfloat16)
-    dgu = ops.swiglu_bwd(gu.to(dev), dact.to(dev))
-    g32 = gu.float().clone().requires_grad_(True)
-    i = 512
-    (F.silu(g32[:, :i]) * g32[:, i:]).backward(dact.float())
-    assert _rel(dgu, g32.grad) < 8e-3
+    for tokens, i in [(77, 512), (5, 8), (1031, 4096)]:
+        gu = (torch.randn(tokens, 2 * i) * 2).to(torch.bfloat16)
+        if (tokens, i) != (77, 512):
+            gu[0, :8] = torch.tensor([-200.0, -90.0, 90.0, 200.0, 0.0, -0.0, 1e-30, -1e-30]).to(torch.bfloat16)
+        act = ops.swiglu_fwd(gu.to(dev))
+        ref = swiglu_ref(gu)                       # bf16 ops on CPU == the reference's autocast arithmetic
+        assert torch.isfinite(act.float()).all()
+        if (tokens, i) == (77, 512):
+            assert _maxabs(act, ref) <= 0.07
+        # everywhere: silu(g) may round to the neighbouring bf16 (one ulp, carried through the product), then the product rounds
+        # once more: two bf16 ulps, each at most 2^-7 of the magnitude
+        assert ((act.float().cpu() - ref.float()).abs() <= 2.0 ** -6 * ref.float().abs() + 1e-37).all()
+        assert _rel(act, ref) < 6e-3
+        dact = torch.randn(tokens, i).to(torch.bfloat16)
+        dgu = ops.swiglu_bwd(gu.to(dev), dact.to(dev))
+        g32 = gu.float().clone().requires_grad_(True)
+        (F.silu(g32[:, :i]) * g32[:, i:]).backward(dact.float())
+        assert torch.isfinite(dgu.float()).all()
+        assert _rel(dgu, g32.grad) < 8e-3
 
 
 def test_embed_fwd_bwd(dev):
@@ -639,6 +659,57 @@ def test_ce_fwd_bwd(dev):
     assert buf[:, V:].abs().max().item() == 0
 
 
+def test_ce_wide_rows_row_scale_and_all_ignored(dev):
+    """V = 4101: V / 8 = 512 > 256 lanes, so a lane's online max / sum rescales more than once, with a ragged tail of 5; a dominant
+    logit early in one row and late in another (the running maximum changes in the lane's first / last chunk); labels at columns 0 and
+    V - 1; gscale = None; the row_scale form (DPO's per-row upstream gradient); a batch whose labels are all ignore_index."""
+    ops = _ops()
+    torch.manual_seed(6)
+    R, V = 9, 4101
+    ld = (V + 63) // 64 * 64
+    logits = (torch.randn(R, V) * 3).to(torch.bfloat16)
+    logits[1, 3] = 40.0                                   # dominant early
+    logits[2, V - 2] = 40.0                               # dominant late, in the ragged tail
+    logits[3, 2100] = 30.0; logits[3, 7] = 29.0
+    labels = torch.randint(0, V, (R,)); labels[0] = 0; labels[1] = V - 1; labels[2] = V - 2; labels[5] = -100
+
+    def fresh():
+        buf = torch.full((R, ld), 7.0, dtype=torch.bfloat16, device=dev)
+        buf[:, :V] = logits.to(dev)
+        return buf
+    valid = labels != -100
+    buf = fresh()
+    lc, lse, loss_row, logp = ops.ce_fwd(buf, V, labels.to(dev), want_logp=True)
+    ref = F.cross_entropy(logits.double(), labels, ignore_index=-100)
+    assert abs(lc[0].item() - ref.item()) / ref.item() < 1e-5
+    assert lc[1].item() == valid.sum().item()
+    lsm = torch.log_softmax(logits.double(), -1)
+    assert _maxabs(lse, torch.logsumexp(logits.double(), -1)) < 1e-4
+    assert _maxabs(logp[valid], lsm.gather(1, labels.clamp(min=0)[:, None])[:, 0][valid]) < 1e-4
+    ops.ce_bwd_(buf, V, labels.to(dev), lse, lc, None)                       # gscale = None: the plain mean
+    lg = logits.double().clone().requires_grad_(True)
+    F.cross_entropy(lg, labels, ignore_index=-100).backward()
+    assert _rel(buf[:, :V], lg.grad) < 6e-3
+    assert buf[:, V:].abs().max().item() == 0 and buf[5].abs().max().item() == 0
+    # row_scale: d(sum_r row_scale[r] * (-logp[r])) / dlogits
+    rs = torch.randn(R)
+    buf = fresh()
+    ops.ce_bwd_(buf, V, labels.to(dev), lse, None, row_scale=rs.to(dev))
+    lg = logits.double().clone().requires_grad_(True)
+    lp = torch.log_softmax(lg, -1).gather(1, labels.clamp(min=0)[:, None])[:, 0]
+    (-(lp * rs.double())[valid]).sum().backward()
+    assert _rel(buf[:, :V], lg.grad) < 6e-3
+    assert buf[:, V:].abs().max().item() == 0 and buf[5].abs().max().item() == 0
+    # every label ignored: the loss is 0 / 0 like F.cross_entropy, the gradient all zeros and finite
+    none = torch.full((R,), -100)
+    buf = fresh()
+    lc, lse, _, _ = ops.ce_fwd(buf, V, none.to(dev))
+    assert math.isnan(lc[0].item()) and lc[1].item() == 0
+    assert math.isnan(F.cross_entropy(logits.float(), none, ignore_index=-100).item())
+    ops.ce_bwd_(buf, V, none.to(dev), lse, lc, torch.tensor([0.5], device=dev))
+    assert torch.isfinite(buf.float()).all() and buf.abs().max().item() == 0
+
+
 # ------------------------------------------------------------------ attention
 def _ref_masks(B, L, kind, gen):
     """additive masks with the structure the reference builders emit (prompting_utils.py:975-1074)"""
@@ -669,10 +740,13 @@ def _ref_masks(B, L, kind, gen):
 
 @pytest.mark.parametrize("kind", ["causal", "t2i", "mmu", "random"])
 @pytest.mark.parametrize("B,L,H,HKV", [(2, 70, 2, 1), (1, 200, 12, 2), (2, 129, 6, 2), (8, 333, 24, 4), (6, 400, 24, 4),
-                                     (2, 128, 6, 2), (1, 256, 12, 2)])      # (whole 64-key tiles only: no clamped last tile)
+                                     (2, 128, 6, 2), (1, 256, 12, 2),       # (whole 64-key tiles only: no clamped last tile)
+                                     (35, 260, 12, 2)])
 def test_attention_fwd_bwd(dev, kind, B, L, H, HKV):
-    """The last two shapes have >= 512 128-row query tiles, i.e. they run the eight-wave forward kernel (ragged last
-    tile at 333; at 400 the last 128-row tile has no second half)."""
+    """(8, 333, 24, 4) and (6, 400, 24, 4) have >= 512 (128-row tile, head) pairs at 256 <= L <= 4096, i.e. they run the 32-row
+    forward and dQ kernels (end-aligned tiles: the ragged tile is the first; the eight-wave forward is left to L > 4096,
+    test_attention_edges_gpu.py).  (35, 260, 12, 2) adds 5 * 6 * 35 = 1050 >= 1024 dK/dV workgroups: two query heads per workgroup,
+    the benchmark's kernel set, on the four mask kinds against `attention_ref`."""
     ops = _ops()
     from oracle.ops_ref import attention_ref
     hd = 128
