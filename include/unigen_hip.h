@@ -359,6 +359,47 @@ int ug_ar_sample_filtered(float* acc, int64_t ldacc, int64_t bsz, int64_t V, flo
                           int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, int64_t top_k,
                           float top_p, float min_p, float* stats, hipStream_t stream);
 
+/* ---- text decode: the pick over the whole vocabulary (csrc/text_sampler.hip) --------------------- */
+/* One text decode step behind the head, for R <= 32 rows: the token of every row, the stop rule of the host loop
+ * (models/unigen.py: emit_until_stop), the token's slot in the output buffer and the next step's input.
+ * logits: fp32 [R][ld], V <= ld (rows on 16-byte boundaries are read four entries at a time); entries V .. ld-1 are never
+ * candidates.  clear != 0: the V read entries of every row are zeroed on the way out (what the atomic GEMV head needs, as ug_ar_sample has it); nothing else in the buffer is written.
+ * stop_ids: n_stop <= 8 ids in device memory (n_stop == 0: none).  pad_id < 0: none.  embed: fp32 table of embed_rows rows.
+ * state (int32, device memory; the HOST resets it to {0, R, 0, 0, 0 ...} at the start of a call, nothing about the prompt is an
+ * argument): [0] step -- the kernels' own counter, advanced once per call of this entry point; [1] remaining -- rows not yet done;
+ * [2] steps_used; [3] an arrival ticket (0 between calls); [4 + r] done[r].
+ * Per row r:
+ *   1. value = the logit rounded to bf16 (the rounding of the head output the host loop picks from);
+ *   2. token = the LOWEST index attaining the maximum (torch.argmax's documented tie rule);
+ *   3. if done[r] and pad_id >= 0: token = pad_id;
+ *   4. out_tokens[r * nsteps + step] = tok[r] = token;
+ *   5. if token is a stop id and the row was not done: lengths[r] = step + 1 (lengths may be null), done[r] = 1, --remaining, and when
+ *      remaining reaches zero steps_used = step + 1;
+ *   6. x[r] = embed[token] (H floats).
+ * No float atomics; integer atomics only where their order cannot matter: a step is a function of its inputs. */
+int ug_text_pick(float* logits, int64_t ld, int64_t R, int64_t V, int clear, const int64_t* stop_ids, int64_t n_stop, int64_t pad_id,
+                 const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
+                 int* out_tokens, int* lengths, float* x, hipStream_t stream);
+
+/* number of int32 of the workspace ug_text_sample needs for R rows (a negative status for R outside 1..32).  The workspace must be
+ * all zero before the first call; every call leaves it all zero. */
+int ug_text_sample_workspace_ints(int64_t R);
+
+/* ug_text_pick with a sampled token: temperature -> top-k -> top-p -> draw.  v[e] = bf16round(logit[e]) * fp32(1 / temperature),
+ * ex[e] = exp(v[e] - max v).  The kept set is ug_ar_sample_filtered's: {v >= tau}, tau = max(tau_k, tau_p); top_k 0 or >= V: off, every
+ * value tied at tau_k is kept; top_p 1: off, a run of equal values is kept or dropped as a whole.
+ * The draw is an inverse CDF on uniforms[step * R + r] over the kept entries ordered by VALUE DESCENDING and, among equal values, by
+ * index ascending -- not ug_ar_sample's index order: v is a monotone function of a 16-bit pattern, so the selection runs on a
+ * 65 536-bin count histogram of the row (mass of a bin = count x ex) instead of on the 160 000 entries, and the histogram's order is
+ * the value's.  With T the kept mass, the drawn key is the first whose running mass exceeds u * T and the rank inside the key is
+ * min(count - 1, floor(residual / ex)).  Three launches: histogram (integer atomics), selection (one workgroup per row; every float
+ * sum in a fixed order), locate + ug_text_pick's steps 3-6.  A step is a bit-reproducible function of its inputs.
+ * V <= 262 144.  stats (optional, [R][2]): the smallest kept value and the number of kept entries.  NaN logits are no candidates. */
+int ug_text_sample(float* logits, int64_t ld, int64_t R, int64_t V, int clear, float temperature, int64_t top_k, float top_p,
+                   const float* uniforms, int* workspace, float* stats, const int64_t* stop_ids, int64_t n_stop, int64_t pad_id,
+                   const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
+                   int* out_tokens, int* lengths, float* x, hipStream_t stream);
+
 /* ---- loss ------------------------------------------------------------------------------------ */
 /* replaces: F.cross_entropy(ignore_index=-100) x3 in UniGen.forward (models/unigen.py:310-338) and
  * get_batch_logps (training/train_dpo.py:51-90).  logits bf16 [R, ld], ld % 8 == 0.

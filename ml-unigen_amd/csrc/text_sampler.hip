@@ -1,0 +1,446 @@
+// Token pick of a text decode step over the WHOLE vocabulary, on the device (UniGen.generate / mmu_generate / mmu_generate_batch with
+// on_device=True): the head's fp32 logits [R][ld] -> one token per row, the stop rule of models/unigen.py: emit_until_stop, the
+// token's slot in the output buffer and the embedding row that feeds the next step.  Contract: include/unigen_hip.h (ug_text_pick,
+// ug_text_sample).  Plain HIP C++: no inline assembly, no float atomics; integer atomics only where their order cannot change the
+// result (histogram counts, a maximum, a minimum, the count of unfinished rows, the arrival ticket that advances the step counter).
+//
+// State block (int32, device memory, reset by the host at the start of a call to {0, R, 0, 0, 0...}):
+//   [0] step        the kernels' own step counter: read by every workgroup at its start, advanced by the LAST workgroup of the
+//                   finishing launch to arrive (so every workgroup of a step has read it before it moves)
+//   [1] remaining   rows not yet done
+//   [2] steps_used  step + 1 of the step in which `remaining` reached zero (0: not yet)
+//   [3] arrived     the arrival ticket (0 between launches)
+//   [4 + r] done[r]
+#include "common.h"
+#include "unigen_hip.h"
+
+namespace {
+
+constexpr int TXT_T = 1024;            // one workgroup per row
+constexpr int TXT_W = TXT_T / 64;
+constexpr int TXT_MAX_ROWS = 32;
+constexpr int TXT_MAX_STOP = 8;
+constexpr int TXT_BINS = 65536;        // one bin per bf16 pattern
+constexpr int TXT_MAXV = 262144;       // ug_text_sample: launch C keeps one 64-bit match mask per 64 entries in LDS (32 KiB)
+constexpr int TXT_SEG = 8192;          // entries per workgroup of the histogram launch
+constexpr int TXT_HT = 256;
+
+struct TextOut {
+  const int64_t* stop_ids;
+  int n_stop;
+  int64_t pad_id;
+  const float* embed;
+  int64_t lde;
+  int H;
+  int* state;
+  int nsteps;
+  int R;
+  int64_t* tok;
+  int* out_tokens;
+  int* lengths;
+  float* x;
+};
+
+// bf16 pattern -> 16-bit key whose unsigned order is the order of the values (-0 and +0 share a key)
+__device__ __forceinline__ uint32_t txt_key(bf16_t b) {
+  uint32_t k = b;
+  if (k == 0x8000u) k = 0u;
+  return (k ^ ((k >> 15) ? 0xffffu : 0x8000u)) & 0xffffu;
+}
+__device__ __forceinline__ float txt_unkey(uint32_t k) { return bf2f((bf16_t)(k ^ ((k >> 15) ? 0x8000u : 0xffffu))); }
+
+// v of a key: bf16 value x fp32(1 / temperature), ROUNDED (never contracted into the subtraction of the maximum that follows it:
+// v is the fp32 number the contract defines, and every use sees the same one)
+__device__ __forceinline__ float txt_val(uint32_t key, float inv_temp) { return __fmul_rn(txt_unkey(key), inv_temp); }
+
+// The end of a step for row r (every thread of the row's workgroup calls it; `picked` is uniform): pad rule, records, stop rule, next
+// input, then the arrival ticket.  s_token: one int of LDS.
+__device__ __forceinline__ void txt_finish_row(const TextOut& o, int r, int picked, int step, int* s_token) {
+  const int t = threadIdx.x;
+  if (t == 0) {
+    int* done = o.state + 4;
+    const int was = done[r];
+    const int64_t token = (was && o.pad_id >= 0) ? o.pad_id : (int64_t)picked;
+    o.tok[r] = token;
+    if (step < o.nsteps) o.out_tokens[(int64_t)r * o.nsteps + step] = (int)token;
+    bool stop = false;
+    for (int i = 0; i < o.n_stop; ++i) stop |= o.stop_ids[i] == token;
+    if (stop && !was) {
+      if (o.lengths) o.lengths[r] = step + 1;
+      done[r] = 1;
+      if (atomicSub(&o.state[1], 1) == 1) o.state[2] = step + 1;
+    }
+    *s_token = (int)token;
+  }
+  __syncthreads();
+  const int token = *s_token;
+  const float4* er = reinterpret_cast<const float4*>(o.embed + (int64_t)token * o.lde);
+  float4* xr = reinterpret_cast<float4*>(o.x + (int64_t)r * o.H);
+  for (int i = t; i < (o.H >> 2); i += blockDim.x) xr[i] = er[i];
+  if (t == 0) {
+    __threadfence();
+    if (atomicAdd(&o.state[3], 1) == o.R - 1) { o.state[3] = 0; o.state[0] = step + 1; }
+  }
+}
+
+__device__ __forceinline__ int txt_read_step(const int* state, int* s_step) {
+  if (threadIdx.x == 0) *s_step = *reinterpret_cast<const volatile int*>(state);
+  __syncthreads();
+  return *s_step;
+}
+
+// ------------------------------------------------------------------ greedy: argmax of the bf16-rounded logits, lowest index on ties
+// VEC: rows that start on 16-byte boundaries (ld % 4 == 0) are read four entries at a time
+template <bool VEC>
+__global__ __launch_bounds__(TXT_T) void text_pick_kernel(float* __restrict__ logits, int64_t ld, int V, int clear, TextOut o) {
+  __shared__ float red[TXT_W];
+  __shared__ int best_i[TXT_W];
+  __shared__ int s_step, s_token;
+  const int r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int step = txt_read_step(o.state, &s_step);
+  float* row = logits + (int64_t)r * ld;
+  float mx = -INFINITY;
+  int arg = 0x7fffffff;
+  if (VEC) {
+    float4* row4 = reinterpret_cast<float4*>(row);
+    const int n4 = (V + 3) >> 2;                                  // (ld is a multiple of 4: the last vector stays inside the row)
+    for (int i = t; i < n4; i += TXT_T) {                         // ascending indices per thread: `>` keeps the lowest
+      const float4 q = row4[i];
+      const float vv[4] = {q.x, q.y, q.z, q.w};
+      const int e0 = 4 * i;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float v = bf2f(f2bf(vv[j]));
+        if (e0 + j < V && v > mx) { mx = v; arg = e0 + j; }      // (entries V .. ld-1 are read, never candidates)
+      }
+      if (clear) {
+        if (e0 + 3 < V) row4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        else
+          for (int j = 0; e0 + j < V; ++j) row[e0 + j] = 0.f;    // nothing is written past the V read entries
+      }
+    }
+  } else {
+#pragma unroll 8
+    for (int e = t; e < V; e += TXT_T) {
+      const float v = bf2f(f2bf(row[e]));
+      if (v > mx) { mx = v; arg = e; }
+      if (clear) row[e] = 0.f;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float om = __shfl_xor(mx, off, 64);
+    const int oi = __shfl_xor(arg, off, 64);
+    if (om > mx || (om == mx && oi < arg)) { mx = om; arg = oi; }
+  }
+  if (lane == 0) { red[wave] = mx; best_i[wave] = arg; }
+  __syncthreads();
+  float bmx = red[0];
+  int bi = best_i[0];
+#pragma unroll
+  for (int w = 1; w < TXT_W; ++w)
+    if (red[w] > bmx || (red[w] == bmx && best_i[w] < bi)) { bmx = red[w]; bi = best_i[w]; }
+  if (bi >= V) bi = 0;                                            // (no finite candidate: torch.argmax answers 0 for a row of -inf)
+  txt_finish_row(o, r, bi, step, &s_token);
+}
+
+// ------------------------------------------------------------------ sampled pick, launch A: per-row histogram of the 16-bit keys
+// grid (segments, R).  hist [R][65536] int32 and rowmax [R] are zero on entry (launch B leaves them so).
+__global__ __launch_bounds__(TXT_HT) void text_hist_kernel(const float* __restrict__ logits, int64_t ld, int V, int* __restrict__ hist,
+                                                          int* __restrict__ rowmax) {
+  const int r = blockIdx.y, t = threadIdx.x;
+  const float* row = logits + (int64_t)r * ld;
+  int* h = hist + (int64_t)r * TXT_BINS;
+  const int e0 = blockIdx.x * TXT_SEG, e1 = min(V, e0 + TXT_SEG);
+  int mk = 0;
+  for (int e = e0 + t; e < e1; e += TXT_HT) {
+    const float f = row[e];
+    if (f != f) continue;                                          // a NaN logit is no candidate
+    const int k = (int)txt_key(f2bf(f));
+    atomicAdd(&h[k], 1);
+    mk = max(mk, k);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mk = max(mk, __shfl_xor(mk, off, 64));
+  if ((t & 63) == 0) atomicMax(&rowmax[r], mk);
+}
+
+// exclusive prefix of `v` over the workgroup's threads in thread order (wave scan, then a four-level scan of the sixteen wave totals);
+// total = the sum over all threads.  Fixed order: a function of the inputs.  One barrier pair; `wt` is TXT_W slots of LDS.
+template <typename T>
+__device__ __forceinline__ T txt_scan_excl(T v, T* wt, T& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  T incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const T n = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += n;
+  }
+  __syncthreads();
+  if (lane == 63) wt[wave] = incl;
+  __syncthreads();
+  T w = lane < TXT_W ? wt[lane] : (T)0;
+  T winc = w;
+#pragma unroll
+  for (int off = 1; off < TXT_W; off <<= 1) {
+    const T n = __shfl_up(winc, off, 64);
+    if (lane >= off) winc += n;
+  }
+  total = __shfl(winc, TXT_W - 1, 64);
+  const T base = __shfl(winc - w, wave, 64);
+  return base + (incl - v);
+}
+
+// ------------------------------------------------------------------ launch B: the whole selection of one row on its histogram
+// Positions p = 0 .. 65535 run over the keys in DESCENDING order (key = 65535 - p); thread t holds p in [64 t, 64 t + 64).
+// meta (int32): rowmax [32] | sel_key [32] | sel_rank [32].
+__global__ __launch_bounds__(TXT_T) void text_select_kernel(int* __restrict__ hist, int* __restrict__ meta, int V, float inv_temp, int top_k,
+                                                           float top_p, const float* __restrict__ uniforms, const int* __restrict__ state,
+                                                           int nsteps, int R, float* __restrict__ stats) {
+  __shared__ int wt_i[TXT_W];
+  __shared__ float wt_f[TXT_W];
+  __shared__ int s_step, s_pk, s_pc, s_kept, s_hit;
+  __shared__ float s_T;
+  const int r = blockIdx.x, t = threadIdx.x;
+  const int step = min(txt_read_step(state, &s_step), nsteps - 1);
+  int4* h4 = reinterpret_cast<int4*>(hist + (int64_t)r * TXT_BINS);
+  // thread t: keys 65535 - 64 t down to 65535 - 64 t - 63 = the 16 int4 at [16 (1023 - t), +16), read back to front
+  int cnt[64];
+  const int v0 = 16 * (TXT_T - 1 - t);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int4 q = h4[v0 + 15 - j];
+    cnt[4 * j] = q.w; cnt[4 * j + 1] = q.z; cnt[4 * j + 2] = q.y; cnt[4 * j + 3] = q.x;
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) h4[v0 + j] = make_int4(0, 0, 0, 0);                 // the bins are ready for the next step
+  const float vmax = txt_val((uint32_t)meta[r], inv_temp);
+  const float u01 = uniforms[(int64_t)step * R + r];
+  if (t == 0) { s_pk = TXT_BINS - 1; s_pc = 0; s_kept = 0; s_hit = TXT_BINS; }
+  const int p0 = 64 * t;
+  // ---- top-k: the position of the k-th largest entry, duplicates counted (exact: integer sums)
+  int nloc = 0;
+#pragma unroll
+  for (int i = 0; i < 64; ++i) nloc += cnt[i];
+  int ntot;
+  const int nbase = txt_scan_excl<int>(nloc, wt_i, ntot);        // (its barriers also publish the initial values above)
+  if (top_k > 0 && top_k < ntot && nbase < top_k && top_k <= nbase + nloc) {
+    int run = nbase, pk = p0;
+    bool found = false;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {
+      run += cnt[i];
+      if (!found && run >= top_k) { pk = p0 + i; found = true; }
+    }
+    s_pk = pk;
+  }
+  __syncthreads();
+  const int pk = s_pk;
+  // ---- masses over S_k = {p <= pk}: count x exp(v - max), chunk in key order, scan in the wave, wave totals
+  auto mass = [&](int i) -> float {
+    return (float)cnt[i] * expf(txt_val((uint32_t)(TXT_BINS - 1 - (p0 + i)), inv_temp) - vmax);
+  };
+  float mloc = 0.f;
+#pragma unroll
+  for (int i = 0; i < 64; ++i)
+    if (cnt[i] > 0 && p0 + i <= pk) mloc += mass(i);
+  float Z;
+  const float mbase = txt_scan_excl<float>(mloc, wt_f, Z);
+  // ---- top-p: a value is kept iff the mass of the strictly greater values of S_k is <= top_p * Z (a prefix of the positions);
+  // the cut pc = the last kept non-empty position, `kept` = the entries up to it
+  const float lim = top_p * Z;
+  {
+    float run = mbase;
+    int last = -1, kept = 0;
+#pragma unroll
+    for (int i = 0; i < 64; ++i)
+      if (cnt[i] > 0 && p0 + i <= pk) {
+        if (top_p >= 1.f || run <= lim) { last = p0 + i; kept += cnt[i]; }
+        run += mass(i);
+      }
+    if (last >= 0) { atomicMax(&s_pc, last); atomicAdd(&s_kept, kept); }
+  }
+  __syncthreads();
+  const int pc = s_pc;
+  // total kept mass T = the running sum just behind pc, formed by the thread that owns pc exactly as the walk below forms it
+  if (pc >= p0 && pc < p0 + 64) {
+    float run = mbase;
+#pragma unroll
+    for (int i = 0; i < 64; ++i)
+      if (cnt[i] > 0 && p0 + i <= pc) run += mass(i);
+    s_T = run;
+  }
+  __syncthreads();
+  // ---- draw: the first kept position whose running sum passes u * T (value descending); the rank inside the key from the residual
+  const float target = u01 * s_T;
+  {
+    float run = mbase;
+    int hit = TXT_BINS;
+#pragma unroll
+    for (int i = 0; i < 64; ++i)
+      if (cnt[i] > 0 && p0 + i <= pc) {
+        run += mass(i);
+        if (hit == TXT_BINS && target < run) hit = p0 + i;
+      }
+    if (hit < TXT_BINS) atomicMin(&s_hit, hit);
+  }
+  __syncthreads();
+  const int hit = s_hit < TXT_BINS ? s_hit : pc;                   // (rounding left the target behind the last bound: the last kept key)
+  if (hit >= p0 && hit < p0 + 64) {
+    float run = mbase, e = 1.f;
+    int c = 1;
+    bool seen = false;
+#pragma unroll
+    for (int i = 0; i < 64; ++i)
+      if (cnt[i] > 0 && p0 + i <= pc && !seen) {
+        if (p0 + i == hit) {
+          seen = true; c = cnt[i];
+          e = expf(txt_val((uint32_t)(TXT_BINS - 1 - hit), inv_temp) - vmax);
+        } else {
+          run += mass(i);
+        }
+      }
+    int j = s_hit < TXT_BINS ? (int)floorf(fmaxf(target - run, 0.f) / e) : c - 1;
+    j = max(0, min(c - 1, j));
+    meta[32 + r] = TXT_BINS - 1 - hit;
+    meta[64 + r] = j;
+  }
+  if (t == 0) {
+    meta[r] = 0;
+    if (stats) {
+      stats[2 * r] = txt_val((uint32_t)(TXT_BINS - 1 - pc), inv_temp);
+      stats[2 * r + 1] = (float)s_kept;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ launch C: the rank-th index holding the selected key, in index order
+// Wave w owns the contiguous entries [w CW, (w + 1) CW), CW a multiple of 64; iteration i covers 64 consecutive entries.
+__global__ __launch_bounds__(TXT_T) void text_locate_kernel(float* __restrict__ logits, int64_t ld, int V, int clear, int* __restrict__ meta,
+                                                           TextOut o) {
+  __shared__ unsigned long long masks[TXT_MAXV / 64];
+  __shared__ int wtot[TXT_W];
+  __shared__ int s_step, s_token, s_pick;
+  const int r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int step = txt_read_step(o.state, &s_step);
+  const int key = meta[32 + r], rank = meta[64 + r];
+  float* row = logits + (int64_t)r * ld;
+  const int iters = (V + 64 * TXT_W - 1) / (64 * TXT_W);           // per wave
+  const int w0 = wave * iters * 64;
+  int mine = 0;
+  for (int i = 0; i < iters; ++i) {
+    const int e = w0 + i * 64 + lane;
+    bool m = false;
+    if (e < V) {
+      const float f = row[e];
+      m = f == f && (int)txt_key(f2bf(f)) == key;
+      if (clear) row[e] = 0.f;
+    }
+    const unsigned long long b = __ballot(m);
+    if (lane == 0) masks[wave * iters + i] = b;
+    mine += __popcll(b);                                           // (uniform over the wave)
+  }
+  if (lane == 0) wtot[wave] = mine;
+  if (t == 0) s_pick = -1;
+  __syncthreads();
+  int total = 0, wsel = -1, before = 0;
+#pragma unroll
+  for (int w = 0; w < TXT_W; ++w) {
+    const int c = wtot[w];
+    if (wsel < 0 && rank < total + c) { wsel = w; before = total; }
+    total += c;
+  }
+  int want = rank - before;
+  if (wsel < 0) { wsel = -2; }                                     // (fewer holders than the rank: cannot happen on unchanged logits)
+  if (wave == wsel) {
+    int run = 0;
+    for (int c0 = 0; c0 < iters; c0 += 64) {
+      const int i = c0 + lane;
+      const unsigned long long b = i < iters ? masks[wave * iters + i] : 0ull;
+      const int c = __popcll(b);
+      int incl = c;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int n = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += n;
+      }
+      const int excl = run + incl - c;
+      if (excl <= want && want < excl + c) {
+        unsigned long long bb = b;
+        for (int s = want - excl; s > 0; --s) bb &= bb - 1;        // drop the lower set bits
+        s_pick = w0 + i * 64 + (__ffsll((long long)bb) - 1);
+      }
+      run += __shfl(incl, 63, 64);
+    }
+  }
+  __syncthreads();
+  int pick = s_pick;
+  if (pick < 0 || pick >= V) pick = 0;
+  if (t == 0) { meta[32 + r] = 0; meta[64 + r] = 0; }
+  txt_finish_row(o, r, pick, step, &s_token);
+}
+
+int txt_check_out(const char* who, float* logits, int64_t ld, int64_t R, int64_t V, const int64_t* stop_ids, int64_t n_stop, int64_t pad_id,
+                  const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
+                  int* out_tokens, float* x) {
+  UG_REQUIRE(logits && embed && state && tok && out_tokens && x && (n_stop == 0 || stop_ids), "%s: null argument", who);
+  UG_REQUIRE(R > 0 && R <= TXT_MAX_ROWS && V > 0 && ld >= V && R * ld < (1ll << 31) && nsteps > 0 && n_stop >= 0 &&
+                 n_stop <= TXT_MAX_STOP,
+             "%s: bad sizes (R=%ld <= %d, V=%ld <= ld=%ld, R*ld < 2^31, nsteps=%ld, n_stop=%ld <= %d)", who, (long)R,
+             TXT_MAX_ROWS, (long)V, (long)ld, (long)nsteps, (long)n_stop, TXT_MAX_STOP);
+  UG_REQUIRE(H > 0 && H % 4 == 0 && ld_embed % 4 == 0 && ld_embed >= H && embed_rows >= V && pad_id < embed_rows && ug_aligned16(embed) &&
+                 ug_aligned16(x),
+             "%s: bad table (H=%ld, ld_embed=%ld, rows=%ld >= V, pad_id=%ld below rows; 16-byte aligned table / x)", who, (long)H,
+             (long)ld_embed, (long)embed_rows, (long)pad_id);
+  return UG_OK;
+}
+
+}  // namespace
+
+extern "C" int ug_text_pick(float* logits, int64_t ld, int64_t R, int64_t V, int clear, const int64_t* stop_ids, int64_t n_stop,
+                            int64_t pad_id, const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state,
+                            int64_t nsteps, int64_t* tok, int* out_tokens, int* lengths, float* x, hipStream_t st) {
+  const int rc = txt_check_out("ug_text_pick", logits, ld, R, V, stop_ids, n_stop, pad_id, embed, ld_embed, embed_rows, H, state, nsteps, tok,
+                               out_tokens, x);
+  if (rc != UG_OK) return rc;
+  const TextOut o{stop_ids, (int)n_stop, pad_id, embed, ld_embed, (int)H, state, (int)nsteps, (int)R, tok, out_tokens, lengths, x};
+  if (ld % 4 == 0 && ug_aligned16(logits))
+    hipLaunchKernelGGL(text_pick_kernel<true>, dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, o);
+  else
+    hipLaunchKernelGGL(text_pick_kernel<false>, dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, o);
+  UG_CHECK_LAUNCH("ug_text_pick");
+  return UG_OK;
+}
+
+extern "C" int ug_text_sample_workspace_ints(int64_t R) {
+  if (R <= 0 || R > TXT_MAX_ROWS) {
+    ug_set_error("ug_text_sample_workspace_ints: R=%ld must be in 1..%d", (long)R, TXT_MAX_ROWS);
+    return UG_ERR_ARG;
+  }
+  return (int)(R * TXT_BINS + 96);
+}
+
+extern "C" int ug_text_sample(float* logits, int64_t ld, int64_t R, int64_t V, int clear, float temperature, int64_t top_k, float top_p,
+                              const float* uniforms, int* workspace, float* stats, const int64_t* stop_ids, int64_t n_stop,
+                              int64_t pad_id, const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state,
+                              int64_t nsteps, int64_t* tok, int* out_tokens, int* lengths, float* x, hipStream_t st) {
+  const int rc = txt_check_out("ug_text_sample", logits, ld, R, V, stop_ids, n_stop, pad_id, embed, ld_embed, embed_rows, H, state, nsteps,
+                               tok, out_tokens, x);
+  if (rc != UG_OK) return rc;
+  UG_REQUIRE(uniforms && workspace && ug_aligned16(workspace), "ug_text_sample: null or misaligned uniforms / workspace");
+  UG_REQUIRE(V <= TXT_MAXV, "ug_text_sample: V=%ld exceeds the %d entries this build locates a token among", (long)V, TXT_MAXV);
+  UG_REQUIRE(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f,
+             "ug_text_sample: bad filter (temperature=%g > 0, top_k=%ld >= 0, 0 < top_p=%g <= 1)", (double)temperature, (long)top_k,
+             (double)top_p);
+  const TextOut o{stop_ids, (int)n_stop, pad_id, embed, ld_embed, (int)H, state, (int)nsteps, (int)R, tok, out_tokens, lengths, x};
+  int* meta = workspace + R * TXT_BINS;
+  hipLaunchKernelGGL(text_hist_kernel, dim3((unsigned)((V + TXT_SEG - 1) / TXT_SEG), (unsigned)R), dim3(TXT_HT), 0, st, logits, ld, (int)V,
+                     workspace, meta);
+  UG_CHECK_LAUNCH("ug_text_sample(histogram)");
+  hipLaunchKernelGGL(text_select_kernel, dim3((unsigned)R), dim3(TXT_T), 0, st, workspace, meta, (int)V, 1.f / temperature,
+                     top_k >= V ? 0 : (int)top_k, top_p, uniforms, state, (int)nsteps, (int)R, stats);
+  UG_CHECK_LAUNCH("ug_text_sample(select)");
+  hipLaunchKernelGGL(text_locate_kernel, dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, meta, o);
+  UG_CHECK_LAUNCH("ug_text_sample(locate)");
+  return UG_OK;
+}

@@ -173,6 +173,9 @@ class UniGen(ModelMixin, ConfigMixin):
         else:
             self.register_to_config(mask_token_id=vocab_size - 1)
         self._loss_idx_cache = {}
+        # text decode on the device (generate / mmu_generate / mmu_generate_batch: `on_device=None` follows this); opt-in, so that
+        # unchanged callers can turn it on from the environment
+        self.text_decode_on_device = os.environ.get("UNIGEN_TEXT_ON_DEVICE", "0") == "1"
         # Data parallelism (reference: accelerator.prepare wraps the model in DistributedDataParallel, train.py:492).
         # The backbone's parameters are views of one flat buffer whose gradients the kernels write directly and
         # unigen_hip.ddp.FlatGradSync averages, so DDP's reducer must leave them alone (see
@@ -597,6 +600,7 @@ class UniGen(ModelMixin, ConfigMixin):
         eng = getattr(getattr(self, "llm", None), "engine", None)
         if eng is not None:
             eng._ar_session = None
+            eng._text_session = None              # (the on-device text loop keeps one too: _decode_text_on_device)
 
     def train(self, mode: bool = True):
         if mode:
@@ -804,7 +808,7 @@ class UniGen(ModelMixin, ConfigMixin):
     @torch.no_grad()
     def generate(self, input_ids=None, input_embeddings=None, attention_mask=None, max_new_tokens=20, do_sample=False,
                  temperature=1.0, top_k=None, top_p=None, eos_token_id=None, pad_token_id=None, use_cache=True,
-                 generator=None, deterministic=None, **kwargs):
+                 generator=None, deterministic=None, on_device=None, **kwargs):
         """Causal text generation with the conventions of transformers' `generate`, which the reference delegates to
         (models/unigen.py:584-588; caller evaluation/inference_unigen_cot.py:360): prompts as ids [B, L] or as
         `input_embeddings` [B, L, H] with an optional 2-D [B, L] key-validity mask (left padding); greedy when
@@ -813,7 +817,16 @@ class UniGen(ModelMixin, ConfigMixin):
         Returns prompt + continuation [B, L + new] for ids, the continuation alone [B, new] for embeddings (HF rule).
         One prefill into the static KV cache, then one decode step per token (`use_cache` is accepted and ignored: the
         recompute form would return the same tokens).  deterministic: ordered decode kernels (the same tokens on every call for the
-        same inputs and generator); None follows torch.are_deterministic_algorithms_enabled()."""
+        same inputs and generator); None follows torch.are_deterministic_algorithms_enabled().
+        on_device: the token loop on the device (`_decode_text_on_device`: head over the whole vocabulary, pick, stop rule and next
+        input as launches of a captured step kept across calls); None follows `self.text_decode_on_device` (False unless
+        UNIGEN_TEXT_ON_DEVICE=1 at construction).  Greedy tokens are the host loop's wherever the top-2 margin exceeds the two heads'
+        rounding.  SAMPLED tokens differ from the host loop's for the same seed: the uniforms are drawn up front as
+        torch.rand((max_new_tokens, rows), generator=...) and used by an inverse CDF over the kept entries (top-k ties all kept, a
+        run of equal logits kept or dropped whole by top-p), where the host loop calls torch.multinomial -- the feature is opt-in
+        for that reason.  An explicit True on a call the loop cannot serve (more than 32 rows, use_cache=False, more than 8 stop
+        ids, a hidden size below 256 or no multiple of 32) raises; a default-derived True falls back to the host loop.
+        kwargs: use_graph=False runs the on-device steps eagerly; trace=list receives every eager step's fp32 logits."""
         from unigen_hip.qwen2 import DecodeState, resolve_deterministic
         from .sampling import top_k_top_p_filtering
         unsupported = [k for k in ("num_beams", "num_return_sequences", "repetition_penalty", "penalty_alpha") if kwargs.get(k) not in (None, 1, 1.0)]
@@ -835,8 +848,17 @@ class UniGen(ModelMixin, ConfigMixin):
         if eos and pad_token_id is None:
             pad_token_id = eos[0]
         det = resolve_deterministic(deterministic)
-        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         eng.last_decode_deterministic = det
+        eng.last_text_decode_on_device = self._text_on_device(on_device, "generate", R, bool(use_cache), eos, max_new_tokens)
+        if eng.last_text_decode_on_device:
+            sampling = None
+            if do_sample:
+                sampling = (float(1.0 if temperature is None else temperature), int(top_k or 0), float(1.0 if top_p is None else top_p))
+            out, _, _ = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, sampling=sampling, stop=eos,
+                                                    pad_token_id=pad_token_id if eos else None, generator=generator,
+                                                    use_graph=bool(kwargs.get("use_graph", True)), trace=kwargs.get("trace"))
+            return torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
+        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, key_valid)
         eng.check_errors()
         out = torch.full((R, max_new_tokens), int(pad_token_id or 0), dtype=torch.long, device=dev)
@@ -859,18 +881,25 @@ class UniGen(ModelMixin, ConfigMixin):
     # ------------------------------------------------------------------ text decoding for understanding
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
-                     top_k=None, eot_token=None, use_cache=True, deterministic=None):
+                     top_k=None, eot_token=None, use_cache=True, deterministic=None, on_device=None, use_graph=True):
         """Greedy / top-k text continuation (reference models/unigen.py:523-581).  The reference re-runs the whole
         growing sequence every step and extends the additive mask by one row that copies the previous last row;
         here the prompt is prefilled once under its mask into the static KV cache and every new token is one decode
         step that attends to the keys the prompt's last row could see plus everything generated since (the same
         function of the inputs; `use_cache=False` keeps the step-by-step recomputation for comparison).  deterministic: ordered
-        decode kernels for the cached form; None follows torch.are_deterministic_algorithms_enabled()."""
+        decode kernels for the cached form; None follows torch.are_deterministic_algorithms_enabled().
+        on_device / use_graph: the token loop on the device, as in `generate` (temperature 0 is greedy; with temperature > 0 the draw is
+        temperature -> top-k -> inverse CDF on uniforms drawn up front, so sampled tokens differ from the host loop's for the same
+        seed).  Cached form only: an explicit True with use_cache=False raises."""
         from unigen_hip.qwen2 import resolve_deterministic
         det = resolve_deterministic(deterministic)
         self.llm.engine.last_decode_deterministic = det
-        if use_cache and attention_mask is not None and attention_mask.shape[0] == 1:
-            return self._mmu_generate_cached(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det)
+        cached = bool(use_cache and attention_mask is not None and attention_mask.shape[0] == 1)
+        dev_loop = self._text_on_device(on_device, "mmu_generate", 1, cached, eot_token, max_new_tokens)
+        self.llm.engine.last_text_decode_on_device = dev_loop
+        if cached:
+            return self._mmu_generate_cached(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
+                                             on_device=dev_loop, use_graph=use_graph)
         return self._mmu_generate_recompute(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token)
 
     @staticmethod
@@ -883,6 +912,113 @@ class UniGen(ModelMixin, ConfigMixin):
             return torch.multinomial(torch.softmax(last, dim=-1), num_samples=1)
         return torch.argmax(last, dim=-1).reshape(-1, 1)
 
+    @staticmethod
+    def _stop_list(stop):
+        """the stop ids of a call (None, an id, a list, or a 0-d / 1-D tensor of ids) as a list of ints"""
+        if stop is None:
+            return []
+        if torch.is_tensor(stop):
+            return [int(v) for v in stop.reshape(-1).tolist()]
+        if isinstance(stop, (list, tuple)):
+            return [int(v) for v in stop]
+        return [int(stop)]
+
+    def _text_on_device(self, on_device, who, rows, cached, stop, max_new_tokens):
+        """Whether this call runs the on-device token loop.  An explicit bool wins over `self.text_decode_on_device`; the loop serves
+        what the AR path's fused step serves (up to 32 rows, hidden size >= 256 and a multiple of 32, cached path) with up to 8 stop
+        ids.  An explicit True on anything else raises with the reason; a default-derived True falls back to the host loop."""
+        if not (self.text_decode_on_device if on_device is None else bool(on_device)):
+            return False
+        H = self.llm.engine.dims.hidden_size
+        n_stop = len(self._stop_list(stop))          # (read only once the loop is wanted: a device tensor of ids costs a host sync)
+        why = None
+        if not cached:
+            why = "the recompute form (use_cache=False, or several rows / no mask in mmu_generate) has no on-device loop"
+        elif rows > ops.TEXT_MAX_ROWS:
+            why = f"{rows} rows (at most {ops.TEXT_MAX_ROWS})"
+        elif H < 256 or H % 32:
+            why = f"hidden size {H} (at least 256 and a multiple of 32)"
+        elif n_stop > ops.TEXT_MAX_STOP:
+            why = f"{n_stop} stop ids (at most {ops.TEXT_MAX_STOP})"
+        elif max_new_tokens < 1:
+            why = f"max_new_tokens={max_new_tokens}"
+        if why is None:
+            return True
+        if on_device is None:
+            return False
+        raise UniGenHipError(f"{who}: on_device=True cannot serve this call: {why}")
+
+    def _decode_text_on_device(self, prompt, max_new_tokens, det, key_valid=None, mask_bits=None, sampling=None, stop=(), pad_token_id=None,
+                               generator=None, use_graph=True, trace=None):
+        """The token loop of `text_token_loop` + `emit_until_stop` with nothing but launches per token: prefill, token 0 eagerly from
+        the prefill's hidden state (GEMV head + pick), step 1 eagerly (warm-up), step 2 captured (its first replay IS step 2), replays
+        from there.  The pick launch applies the stop rule on the device; with stop ids the host reads `remaining` every 8 tokens and
+        stops replaying at zero.  The result is cut at `steps_used` (the step at which the last row finished), else at
+        max_new_tokens: rows that overshoot a poll interval emit pad ids / have their lengths set exactly as the host loop's rows,
+        so the cut result is the host loop's.  No decode step follows the last token.
+        The session (Qwen2Engine.text_step's buffers + the graph) is kept across calls like the AR path's: reused when rows, the KV
+        capacity (prompt + new tokens rounded up to 128), the token-buffer width (new tokens rounded up to 64), layer form, mode,
+        sampling constants, stop ids, pad id, presence of a key-validity mask and the weight storage agree; `drop_decode_session()`
+        and `train()` drop it, UNIGEN_AR_GRAPH_CACHE=0 turns the reuse off.
+        -> (tokens int64 [R, steps], lengths int64 [R], steps)."""
+        from unigen_hip.qwen2 import TextDecodeSession
+        eng = self.llm.engine
+        dev = eng.device
+        R, L, _ = prompt.shape
+        n, V = int(max_new_tokens), self.config.vocab_size
+        stop = [int(s) for s in stop]
+        if sampling is not None and sampling[1] >= V:
+            sampling = (sampling[0], 0, sampling[2])
+        if sampling is not None and not (sampling[0] > 0 and sampling[1] >= 0 and 0.0 < sampling[2] <= 1.0):
+            raise UniGenHipError(f"on-device sampling needs temperature > 0, top_k >= 0 and 0 < top_p <= 1 (got {sampling})")
+        cap, width = ops.round_up(L + n, 128), ops.round_up(n, 64)
+        pad = None if pad_token_id is None else int(pad_token_id)
+        n_layers = eng.dims.num_hidden_layers
+        key = (R, cap, width, V, eng.decode_form(R, det), det, sampling, tuple(stop), pad, key_valid is None, str(dev),
+               eng.fp.w("embed").data_ptr(), eng.fp.w("l0.wqkv").data_ptr(), eng.fp.p("embed").data_ptr(), eng.fp.p("norm").data_ptr(),
+               eng.fp.w(f"l{n_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(cap)))
+        keep = use_graph and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0"
+        sess = getattr(eng, "_text_session", None) if keep else None
+        if sess is not None and sess.key != key:
+            sess = None
+        eng._text_session = None                     # (put back at the end of a call that completed)
+        if sess is None:
+            sess = TextDecodeSession(eng, R, cap, width, V, deterministic=det, sampling=sampling, stop_ids=stop, pad_id=pad, key_valid=key_valid)
+            sess.key = key
+            sess.begin(n)
+        else:
+            sess.begin(n, key_valid, L)
+        if sampling is not None:
+            u_dev = dev if generator is None else generator.device
+            sess.uniforms[:n].copy_(torch.rand((n, R), device=u_dev, generator=generator))
+        hn = eng.prefill(sess.st, prompt, key_valid, mask_bits=mask_bits)
+        eng.check_errors()
+        eng.text_first_token(sess, hn, trace)
+        emitted = 1
+        while emitted < n:
+            if stop and emitted % 8 == 0 and int(sess.state[1]) == 0:          # (the one host read per 8 tokens)
+                break
+            if sess.graph is None and use_graph and emitted == 2:
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    eng.text_step(sess)
+                sess.graph = graph
+                eng.text_graph_captures = getattr(eng, "text_graph_captures", 0) + 1
+                graph.replay()                       # capture only records: this replay IS step 2
+            elif sess.graph is not None:
+                sess.graph.replay()
+            else:
+                eng.text_step(sess, trace)
+            emitted += 1
+        used = int(sess.state[2]) if stop else 0
+        steps = used if used > 0 else n
+        eng.last_decode_graph = sess.graph is not None
+        tokens, lengths = sess.out_tokens[:, :steps].long(), sess.lengths.long()       # (copies: the next call overwrites the session's)
+        if keep and sess.graph is not None:
+            eng._text_session = sess
+        return tokens, lengths, steps
+
     def _decode_text(self, st, hn, max_new_tokens, pick, emit):
         """text_token_loop on this model's engine from a prefilled state: vocabulary logits, embedding table, decode_step."""
         eng, embed, V = self.llm.engine, self.llm.model.embed_tokens, self.config.vocab_size
@@ -891,7 +1027,8 @@ class UniGen(ModelMixin, ConfigMixin):
                                embed=lambda ids: x.copy_(embed(ids)[:, 0]),
                                step=lambda x: eng.decode_step(st, x))            # (also advances the cache position)
 
-    def _mmu_decode(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det):
+    def _mmu_decode(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det, on_device=False,
+                    use_graph=True):
         """Prefill R left-padded rows under their dense [R, 1, L, L] masks, then decode -> (tokens [R, max_new_tokens] on the device,
         the rows' lengths cut after `eot_token` [R], the number of steps taken)."""
         from unigen_hip.qwen2 import DecodeState
@@ -902,6 +1039,13 @@ class UniGen(ModelMixin, ConfigMixin):
         mb = eng.mask_bits(attention_mask, R, L)
         eng.check_errors()
         key_valid = attention_mask[:, 0, -1, :] == 0
+        if on_device:
+            sampling = (float(temperature), int(top_k or 0), 1.0) if temperature > 0 else None
+            tokens, lengths, steps = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, mask_bits=mb, sampling=sampling,
+                                                                 stop=self._stop_list(eot_token), use_graph=use_graph)
+            if steps < max_new_tokens:              # (the host loop's shapes: the buffer is max_new_tokens wide)
+                tokens = torch.cat([tokens, tokens.new_zeros((R, max_new_tokens - steps))], dim=1)
+            return tokens, lengths, steps
         st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, mask_bits=mb)
         tokens = torch.zeros((R, max_new_tokens), dtype=torch.long, device=dev)
@@ -911,16 +1055,17 @@ class UniGen(ModelMixin, ConfigMixin):
         return tokens, lengths, steps
 
     @torch.no_grad()
-    def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False):
+    def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False,
+                             on_device=False, use_graph=True):
         """The one-row case of the batch path -> list of 0-d device tensors (one row: it ends at its `eot_token`, so every step counts)."""
         L = attention_mask.shape[-1]
         tokens, _, steps = self._mmu_decode(idx, input_embeddings, attention_mask.reshape(1, 1, L, L), max_new_tokens, temperature, top_k,
-                                            eot_token, det)
+                                            eot_token, det, on_device=on_device, use_graph=use_graph)
         return list(tokens[0, :steps])
 
     @torch.no_grad()
     def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=0.0,
-                           top_k=None, eot_token=None, deterministic=None):
+                           top_k=None, eot_token=None, deterministic=None, on_device=None, use_graph=True):
         """`mmu_generate` for up to 32 prompts at once -- the rating loop of CoT-V (reference
         evaluation/inference_unigen_cot.py:308-415 calls mmu_generate once per (image, question) pair; every decode
         step streams the whole backbone whatever the row count, so R pairs cost about one).  Rows are LEFT-padded to a
@@ -928,7 +1073,8 @@ class UniGen(ModelMixin, ConfigMixin):
         the pad columns blocked (the reference's mask builders do that for left-padded rows).  Each row follows the
         procedure of `mmu_generate`: prefill under its mask, then one decode step per token attending to the keys its
         last prompt row could see plus everything generated since.  Returns R lists of tokens, each cut after its
-        `eot_token`.  deterministic: ordered decode kernels; None follows torch.are_deterministic_algorithms_enabled()."""
+        `eot_token`.  deterministic: ordered decode kernels; None follows torch.are_deterministic_algorithms_enabled().
+        on_device / use_graph: the token loop on the device, as in `mmu_generate`."""
         from unigen_hip.qwen2 import resolve_deterministic
         det = resolve_deterministic(deterministic)
         self.llm.engine.last_decode_deterministic = det
@@ -937,7 +1083,10 @@ class UniGen(ModelMixin, ConfigMixin):
             raise ValueError("mmu_generate_batch: at most 32 rows per call")
         if attention_mask is None or tuple(attention_mask.shape) != (R, 1, L, L):
             raise ValueError("mmu_generate_batch: attention_mask must be the rows' dense [R, 1, L, L] additive masks")
-        tokens, lengths, _ = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det)
+        dev_loop = self._text_on_device(on_device, "mmu_generate_batch", R, True, eot_token, max_new_tokens)
+        self.llm.engine.last_text_decode_on_device = dev_loop
+        tokens, lengths, _ = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
+                                              on_device=dev_loop, use_graph=use_graph)
         tokens, lengths = tokens.cpu(), lengths.cpu()
         return [list(tokens[r, :int(lengths[r])]) for r in range(R)]
 

@@ -63,6 +63,9 @@ SIGNATURES = {
     "ug_maskgit_train_mask": [P, P, P, I64, I64, I64, I64, P, P, P],
     "ug_ar_sample": [P, I64, I64, I64, F32, F32, I32, P, P, I64, I64, P, I64, I64, I64, P, P, P, P],
     "ug_ar_sample_filtered": [P, I64, I64, I64, F32, F32, I32, P, P, I64, I64, P, I64, I64, I64, P, P, P, I64, F32, F32, P, P],
+    "ug_text_pick": [P, I64, I64, I64, I32, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P],
+    "ug_text_sample_workspace_ints": [I64],
+    "ug_text_sample": [P, I64, I64, I64, I32, F32, I64, F32, P, P, P, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P],
     "ug_maskgit_step": [P, I64, I64, I64, I64, I32, F32, P, P, P, I64, I64, I64, F32, P, P, P, P, P, P],
     "ug_skinny_finish": [P, P, P, P, I64, I64, I32, P],
     "ug_gemv_bf16_ord": [P, I64, I64, P, I64, P, I64, I64, I64, I64, P],

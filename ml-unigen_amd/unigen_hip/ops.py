@@ -776,6 +776,56 @@ def ar_sample_filtered_(acc, bsz, V, guidance_scale, temperature, greedy, unifor
              "ug_ar_sample_filtered")
 
 
+# ------------------------------------------------------------------------------------ text decode: pick over the whole vocabulary
+TEXT_MAX_ROWS, TEXT_MAX_STOP = 32, 8
+TEXT_STATE_INTS = 4 + TEXT_MAX_ROWS        # step, remaining, steps_used, arrival ticket, done[32] (include/unigen_hip.h: ug_text_pick)
+
+
+def text_state(rows, device):
+    """a fresh state block of ug_text_pick / ug_text_sample for `rows` rows"""
+    return text_state_reset_(torch.empty(TEXT_STATE_INTS, dtype=torch.int32, device=device), rows)
+
+
+def text_state_reset_(state, rows):
+    """the host's reset at the start of a call: step 0, every row unfinished"""
+    state.zero_()
+    state[1:2].fill_(int(rows))
+    return state
+
+
+def text_sample_workspace(rows, device):
+    """the zeroed int32 workspace of ug_text_sample for `rows` rows (every call leaves it zeroed)"""
+    n = _l.load().ug_text_sample_workspace_ints(int(rows))
+    if n <= 0:
+        _l.check(n, "ug_text_sample_workspace_ints")
+    return torch.zeros(n, dtype=torch.int32, device=device)
+
+
+def _text_out(stop_ids, pad_id, embed_master):
+    return (_p(stop_ids), 0 if stop_ids is None else stop_ids.numel(), -1 if pad_id is None else int(pad_id), _p(embed_master),
+            embed_master.stride(0), embed_master.shape[0], embed_master.shape[1])
+
+
+def text_pick_(logits, V, state, nsteps, embed_master, tok, out_tokens, x, clear=False, stop_ids=None, pad_id=None, lengths=None):
+    """Greedy token of every row of fp32 logits [R, ld >= V] + the stop rule, the records and the next input (include/unigen_hip.h:
+    ug_text_pick).  stop_ids: int64 device tensor of up to 8 ids or None; state: ops.text_state; tok int64 [R]; out_tokens int32
+    [R, nsteps]; lengths int32 [R] or None; x fp32 [R, H]."""
+    _need_cuda(logits, state, embed_master, tok, out_tokens, x)
+    _l.check(_l.load().ug_text_pick(_p(logits), logits.stride(0), logits.shape[0], int(V), int(bool(clear)), *_text_out(stop_ids, pad_id, embed_master),
+                                    _p(state), int(nsteps), _p(tok), _p(out_tokens), _p(lengths), _p(x), _stream()), "ug_text_pick")
+
+
+def text_sample_(logits, V, state, nsteps, embed_master, tok, out_tokens, x, uniforms, workspace, temperature=1.0, top_k=0, top_p=1.0,
+                 clear=False, stop_ids=None, pad_id=None, lengths=None, stats=None):
+    """text_pick_ with a sampled token: temperature -> top-k -> top-p -> inverse-CDF draw on uniforms [nsteps, R] over the kept entries in
+    value-descending order (include/unigen_hip.h: ug_text_sample).  workspace: ops.text_sample_workspace; stats: optional fp32 [R, 2]
+    taking the smallest kept value and the kept count."""
+    _need_cuda(logits, state, embed_master, tok, out_tokens, x, uniforms, workspace)
+    _l.check(_l.load().ug_text_sample(_p(logits), logits.stride(0), logits.shape[0], int(V), int(bool(clear)), float(temperature), int(top_k),
+                                      float(top_p), _p(uniforms), _p(workspace), _p(stats), *_text_out(stop_ids, pad_id, embed_master),
+                                      _p(state), int(nsteps), _p(tok), _p(out_tokens), _p(lengths), _p(x), _stream()), "ug_text_sample")
+
+
 # ------------------------------------------------------------------------------------ loss
 def ce_fwd(logits, V, labels, ignore_index=-100, want_logp=False):
     """logits bf16 [R, ld>=V]; -> (loss_and_count [2], lse [R], loss_row [R], logp|None)"""

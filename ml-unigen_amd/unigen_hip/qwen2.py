@@ -240,6 +240,42 @@ class DecodeState:
                 setattr(self, name, make())
 
 
+class TextDecodeSession:
+    """Everything a text decode step on the device reads or writes, kept across calls with the captured step: the decode state (KV
+    cache of `capacity` positions), the pick kernels' state block, the next input `x`, the last token, the token buffer [rows, width],
+    the rows' lengths, the head's fp32 logits, and for sampling the histogram workspace and the uniforms [width, rows].
+    sampling: None (greedy) or (temperature, top_k, top_p).  The logits' leading dimension is the vocabulary rounded up to 8, except in
+    deterministic mode, where the ordered head writes a contiguous [rows, vocab] result."""
+
+    def __init__(self, eng, rows, capacity, width, vocab, deterministic=False, sampling=None, stop_ids=(), pad_id=None, key_valid=None):
+        dev, d = eng.device, eng.dims
+        self.rows, self.width, self.V, self.sampling = rows, width, vocab, sampling
+        self.form = eng.decode_form(rows, deterministic)
+        self.st = DecodeState(d, rows, capacity, dev, key_valid=key_valid, deterministic=deterministic)
+        self.state = ops.text_state(rows, dev)
+        self.x = torch.zeros((rows, d.hidden_size), dtype=torch.float32, device=dev)
+        self.tok = torch.zeros((rows,), dtype=torch.long, device=dev)
+        self.out_tokens = torch.zeros((rows, width), dtype=torch.int32, device=dev)
+        self.lengths = torch.zeros((rows,), dtype=torch.int32, device=dev)
+        self.logits = torch.zeros((rows, vocab if deterministic else ops.round_up(vocab, 8)), dtype=torch.float32, device=dev)
+        self.stop_ids = torch.tensor([int(s) for s in stop_ids], dtype=torch.long, device=dev) if len(stop_ids) else None
+        self.pad_id = pad_id
+        self.workspace = self.uniforms = None
+        if sampling is not None:
+            self.workspace = ops.text_sample_workspace(rows, dev)
+            self.uniforms = torch.zeros((width, rows), dtype=torch.float32, device=dev)
+        self.graph, self.key = None, None
+
+    def begin(self, new_tokens, key_valid=None, prompt_len=0):
+        """the host's part of a call's start: state block reset, lengths, and (a reused session) the key-validity columns -- the
+        prompt's, ones behind them.  The prefill sets position and length."""
+        ops.text_state_reset_(self.state, self.rows)
+        self.lengths.fill_(int(new_tokens))
+        if key_valid is not None:
+            self.st.key_valid[:, :prompt_len].copy_(key_valid)
+            self.st.key_valid[:, prompt_len:].fill_(1)
+
+
 class _Saved:
     __slots__ = ("h", "rstd1", "xn1", "qkv", "o", "lse", "h_mid", "rstd2", "xn2", "gu", "act")
 
@@ -635,6 +671,45 @@ class Qwen2Engine:
             pending = None
         ops.decode_sw_head_(stream, fp.p("norm"), d.rms_norm_eps, w_head, logits, pend=pending, advance=(st.pos, st.len))
         return logits
+
+    # ---- text decode on the device: head + pick over the whole vocabulary, the token loop's state in device memory
+    def text_pick(self, sess):
+        """the pick launch(es) of a text step on sess.logits (include/unigen_hip.h: ug_text_pick / ug_text_sample).  The atomic GEMV
+        head of the splitk and wide forms needs its accumulator back zeroed: clear=1 there."""
+        kw = dict(clear=sess.form in ("splitk", "wide"), stop_ids=sess.stop_ids, pad_id=sess.pad_id, lengths=sess.lengths)
+        emb = self.fp.p("embed")
+        if sess.sampling is None:
+            ops.text_pick_(sess.logits, sess.V, sess.state, sess.width, emb, sess.tok, sess.out_tokens, sess.x, **kw)
+        else:
+            t, k, p = sess.sampling
+            ops.text_sample_(sess.logits, sess.V, sess.state, sess.width, emb, sess.tok, sess.out_tokens, sess.x, sess.uniforms, sess.workspace,
+                             temperature=t, top_k=k, top_p=p, **kw)
+
+    def text_first_token(self, sess, hn, trace=None):
+        """token 0 from the prefill's final-norm hidden state: the GEMV head (ordered in deterministic mode) + the pick"""
+        w_head = self.fp.w("embed")[:sess.V]
+        if sess.st.deterministic:
+            ops.skinny_linear_ord(hn, w_head, out_f32=sess.logits)
+        else:
+            sess.logits.zero_()
+            ops.decode_gemv_(hn, w_head, sess.logits)
+        if trace is not None:
+            trace.append(sess.logits[:, :sess.V].clone())
+        self.text_pick(sess)
+
+    def text_step(self, sess, trace=None):
+        """One text decode step into the session's static buffers: the decoder stack on sess.x, the head over the whole vocabulary and
+        the pick (token, stop rule, records, next sess.x); advances the cache position.  No host sync, no shape depends on the step:
+        capturable.  sw / ord_sw / ord_wide end in decode_step_logits' head launch; splitk and wide run decode_step and the atomic
+        GEMV head into the accumulator the pick leaves zeroed.  trace: optional list taking the step's logits (eager runs only)."""
+        w_head = self.fp.w("embed")[:sess.V]
+        if sess.form in ("splitk", "wide"):
+            ops.decode_gemv_(self.decode_step(sess.st, sess.x), w_head, sess.logits)
+        else:
+            self.decode_step_logits(sess.st, sess.x, w_head, sess.logits)
+        if trace is not None and not torch.cuda.is_current_stream_capturing():
+            trace.append(sess.logits[:, :sess.V].clone())
+        self.text_pick(sess)
 
     def decode_step(self, st, x):
         """x fp32 [rows, H] = embedding of the newest token (updated in place as the residual stream);

@@ -1,0 +1,81 @@
+"""Text decode at full scale on ONE GPU: the host token loop against the on-device loop (on_device=True), alternating in one
+process.  Model and prompts as tools/mmu_bench.py: the 1.5B model, device-side random init, R prompts of 768 tokens under the mmu
+mask; 64 new tokens, no stop id, through mmu_generate_batch.  Rows 1 and 16 (ROWS=1,16).  Per setting: two warm-up calls of each
+loop, then five timed calls of each, alternating.  A call's decode time is its wall time minus the same loop's one-token call
+(prefill + first token, the median of three), over the 63 steps behind the first token.
+
+Settings: greedy; greedy in deterministic mode; sampled (temperature 1.0, top_k 50: the shape of the CoT-V call); greedy with a stop
+id no row produces (prices the on-device loop's poll of `remaining` every 8 tokens against the host loop's sync per token).
+
+One JSON line: per rows and setting, every call's tokens/s and ms per step for both loops, and the ratio of the medians."""
+import json
+import os
+import statistics
+import sys
+import time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "ml-unigen_amd"))
+import torch
+from bench import CODEBOOK, NVQ, TEXT_VOCAB, VOCAB
+from models import UniGen
+
+NEW, L = 64, 768
+SETTINGS = {
+    "greedy": dict(temperature=0.0),
+    "greedy_deterministic": dict(temperature=0.0, deterministic=True),
+    "sampled_t1_k50": dict(temperature=1.0, top_k=50),
+    "greedy_stop_never_hit": dict(temperature=0.0, eot_token=VOCAB - 1),          # (the mask token: the backbone's argmax never lands there)
+}
+
+
+def main():
+    dev = torch.device("cuda:0")
+    rows = [int(r) for r in os.environ.get("ROWS", "1,16").split(",")]
+    only = os.environ.get("SETTINGS")
+    model = UniGen(w_und_encoder=False, vocab_size=VOCAB, llm_vocab_size=TEXT_VOCAB, llm_model_path="Qwen2.5-1.5B-Instruct",
+                   codebook_size=CODEBOOK, num_vq_tokens=NVQ, device=dev, init_seed=-1)
+    model.llm.init_weights_device(1)
+    model.eval()
+    g = torch.Generator(device=dev).manual_seed(2)
+    r = torch.arange(L, device=dev)
+    allow = (r[None, :] <= r[:, None]) | ((r[None, :] >= 20) & (r[None, :] < 749))      # mmu_vit mask: image block visible
+    result = {"prompt": L, "new_tokens": NEW, "rows": {}}
+    for R in rows:
+        idx = torch.randint(0, 151643, (R, L), device=dev, generator=g)
+        mask = torch.where(allow, 0.0, torch.finfo(torch.float32).min)[None, None].expand(R, 1, L, L).contiguous()
+        result["rows"][str(R)] = per_rows = {}
+        for name, kw in SETTINGS.items():
+            if only and name not in only.split(","):
+                continue
+
+            def call(on_device, new=NEW):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = model.mmu_generate_batch(idx=idx, attention_mask=mask, max_new_tokens=new, on_device=on_device, **kw)
+                torch.cuda.synchronize()
+                assert all(len(o) == new for o in out)
+                return time.perf_counter() - t0
+
+            for _ in range(2):
+                call(False), call(True)
+            first = {od: statistics.median(call(od, 1) for _ in range(3)) for od in (False, True)}
+            times = {False: [], True: []}
+            for _ in range(5):
+                for od in (False, True):
+                    times[od].append(call(od))
+            rec = {}
+            for od, tag in ((False, "host"), (True, "device")):
+                step_ms = [1e3 * (t - first[od]) / (NEW - 1) for t in times[od]]
+                rec[tag] = {"call_s": [round(t, 4) for t in times[od]], "first_token_call_s": round(first[od], 4),
+                            "ms_per_step": [round(m, 4) for m in step_ms], "tokens_per_s": [round(1e3 * R / m, 1) for m in step_ms]}
+            med = lambda tag: statistics.median(rec[tag]["ms_per_step"])
+            rec["device_over_host_tokens_per_s"] = round(med("host") / med("device"), 3)
+            rec["call_time_ratio_host_over_device"] = round(statistics.median(times[False]) / statistics.median(times[True]), 3)
+            per_rows[name] = rec
+        model.drop_decode_session()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
