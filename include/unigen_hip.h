@@ -400,6 +400,31 @@ int ug_text_sample(float* logits, int64_t ld, int64_t R, int64_t V, int clear, f
                    const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
                    int* out_tokens, int* lengths, float* x, hipStream_t stream);
 
+/* Logits processor of the on-device text loop: transformers' RepetitionPenaltyLogitsProcessor.  THE RULE: for every token id that
+ * occurs in the row's sequence so far, s <- s * p if s < 0 else s / p; once per distinct id, however often the id occurs; ahead of
+ * temperature / top-k / top-p.  The row's sequence so far = the prompt ids at positions the key-validity mask marks real + the tokens
+ * emitted so far (a prompt given as embeddings has no ids: the emitted tokens only, as transformers has it for inputs_embeds).
+ * p is finite and > 0; p = 1 is off (the callers then launch nothing).
+ *   host loop:   the rule in fp32 on the fp32 copy of the head's bf16 logits (models/sampling.py: apply_repetition_penalty);
+ *   device loop: s = bf16round(logit), the product / quotient in fp32 with round-to-nearest, the fp32 result stored back;
+ *                ug_text_pick / ug_text_sample then read it and round it to bf16 as they round every logit.
+ * So greedy tokens of the two loops can differ only where two processed values fall within one bf16 step of each other.
+ * 0 and -0.0 stay zero, +inf / p = +inf, NaN stays NaN (no candidate downstream).
+ * seen: int32 [R][ld_words], ld_words >= W = ceil(V / 32); bit (e & 31) of word (e >> 5) of row r: id e is in row r's sequence. */
+
+/* sets the bit of every prompt id: ids int64 [R][ld_ids >= L]; valid (nullable) uint8 [R][L], 0 = not a real position; ids outside
+ * [0, V) are ignored.  Integer atomicOr: the order cannot matter.  Once per call, outside the captured step. */
+int ug_text_seen_mark(int* seen, int64_t ld_words, const int64_t* ids, int64_t ld_ids, int64_t R, int64_t L, const uint8_t* valid,
+                      int64_t V, hipStream_t stream);
+
+/* One launch per step between the head and the pick, R <= 32; logits / ld as ug_text_pick has them (no alignment needed).  A thread
+ * owns whole bitmap words of one row: if tok (nullable, int64 [R]: the token the previous step emitted) falls into its word it ORs the
+ * bit in and stores the word (a plain store: nobody else touches the word); for every set bit e < V it then rewrites logits[r][e] by
+ * the device rule above.  Bits at or above V in the last word are never acted on; the logits of unseen ids and entries V .. ld-1 are
+ * neither read nor written.  No atomics, no float reductions: a bit-reproducible function of its inputs. */
+int ug_text_penalize(float* logits, int64_t ld, int64_t R, int64_t V, float penalty, int* seen, int64_t ld_words, const int64_t* tok,
+                     hipStream_t stream);
+
 /* ---- loss ------------------------------------------------------------------------------------ */
 /* replaces: F.cross_entropy(ignore_index=-100) x3 in UniGen.forward (models/unigen.py:310-338) and
  * get_batch_logps (training/train_dpo.py:51-90).  logits bf16 [R, ld], ld % 8 == 0.

@@ -1,8 +1,9 @@
 // Token pick of a text decode step over the WHOLE vocabulary, on the device (UniGen.generate / mmu_generate / mmu_generate_batch with
 // on_device=True): the head's fp32 logits [R][ld] -> one token per row, the stop rule of models/unigen.py: emit_until_stop, the
 // token's slot in the output buffer and the embedding row that feeds the next step.  Contract: include/unigen_hip.h (ug_text_pick,
-// ug_text_sample).  Plain HIP C++: no inline assembly, no float atomics; integer atomics only where their order cannot change the
-// result (histogram counts, a maximum, a minimum, the count of unfinished rows, the arrival ticket that advances the step counter).
+// ug_text_sample; the repetition penalty in front of the pick: ug_text_seen_mark, ug_text_penalize).  Plain HIP C++: no inline assembly,
+// no float atomics; integer atomics only where their order cannot change the result (histogram counts, a maximum, a minimum, the count
+// of unfinished rows, the arrival ticket that advances the step counter, the OR of a prompt id's bit into the seen bitmap).
 //
 // State block (int32, device memory, reset by the host at the start of a call to {0, R, 0, 0, 0...}):
 //   [0] step        the kernels' own step counter: read by every workgroup at its start, advanced by the LAST workgroup of the
@@ -380,6 +381,46 @@ __global__ __launch_bounds__(TXT_T) void text_locate_kernel(float* __restrict__ 
   txt_finish_row(o, r, pick, step, &s_token);
 }
 
+// ------------------------------------------------------------------ repetition penalty: the logits processor in front of the pick
+// seen [R][ld_words]: bit (e & 31) of word (e >> 5) is set iff id e occurs in the row's sequence so far.  Mark: one thread per prompt
+// position; an integer OR, whose order cannot matter.
+__global__ __launch_bounds__(TXT_HT) void text_seen_mark_kernel(int* __restrict__ seen, int64_t ld_words, const int64_t* __restrict__ ids,
+                                                               int64_t ld_ids, int L, const uint8_t* __restrict__ valid, int V) {
+  const int r = blockIdx.y, l = blockIdx.x * TXT_HT + threadIdx.x;
+  if (l >= L) return;
+  if (valid && !valid[(int64_t)r * L + l]) return;
+  const int64_t id = ids[(int64_t)r * ld_ids + l];
+  if (id < 0 || id >= V) return;
+  atomicOr(&seen[(int64_t)r * ld_words + (id >> 5)], (int)(1u << (id & 31)));
+}
+
+// Penalize: grid (word blocks, R); a thread owns ONE bitmap word of one row (a wave reads 256 contiguous bytes of the bitmap) and the up
+// to 32 logits its bits name -- nobody else reads or writes either, so plain loads and stores, no atomics, no reductions: the launch is
+// a function of its inputs.  The logits of unseen ids are never loaded.
+__global__ __launch_bounds__(TXT_HT) void text_penalize_kernel(float* __restrict__ logits, int64_t ld, int V, float penalty, int* __restrict__ seen,
+                                                              int64_t ld_words, const int64_t* __restrict__ tok) {
+  const int r = blockIdx.y, w = blockIdx.x * TXT_HT + threadIdx.x;
+  const int W = (V + 31) >> 5;
+  if (w >= W) return;
+  int* sw = seen + (int64_t)r * ld_words + w;
+  uint32_t word = (uint32_t)*sw;
+  if (tok) {                                                       // the token the previous step emitted joins the row's sequence
+    const int64_t tk = tok[r];
+    if (tk >= 0 && tk < V && (int)(tk >> 5) == w) {
+      word |= 1u << (tk & 31);
+      *sw = (int)word;
+    }
+  }
+  if (w == W - 1 && (V & 31)) word &= (1u << (V & 31)) - 1u;       // bits at or above V are never acted on
+  float* row = logits + (int64_t)r * ld + 32 * w;
+  while (word) {
+    const int b = __ffs((int)word) - 1;
+    word &= word - 1;
+    const float s = bf2f(f2bf(row[b]));                            // the value the pick sees; NaN < 0 is false and NaN / p is NaN
+    row[b] = s < 0.f ? __fmul_rn(s, penalty) : __fdiv_rn(s, penalty);
+  }
+}
+
 int txt_check_out(const char* who, float* logits, int64_t ld, int64_t R, int64_t V, const int64_t* stop_ids, int64_t n_stop, int64_t pad_id,
                   const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
                   int* out_tokens, float* x) {
@@ -442,5 +483,31 @@ extern "C" int ug_text_sample(float* logits, int64_t ld, int64_t R, int64_t V, i
   UG_CHECK_LAUNCH("ug_text_sample(select)");
   hipLaunchKernelGGL(text_locate_kernel, dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, meta, o);
   UG_CHECK_LAUNCH("ug_text_sample(locate)");
+  return UG_OK;
+}
+
+extern "C" int ug_text_seen_mark(int* seen, int64_t ld_words, const int64_t* ids, int64_t ld_ids, int64_t R, int64_t L, const uint8_t* valid,
+                                 int64_t V, hipStream_t st) {
+  UG_REQUIRE(seen && ids, "ug_text_seen_mark: null argument");
+  UG_REQUIRE(R > 0 && R <= TXT_MAX_ROWS && L > 0 && L < (1ll << 31) && ld_ids >= L && V > 0 && V < (1ll << 31) && ld_words >= (V + 31) / 32,
+             "ug_text_seen_mark: bad sizes (R=%ld <= %d, 0 < L=%ld <= ld_ids=%ld, V=%ld, ld_words=%ld >= ceil(V / 32))", (long)R, TXT_MAX_ROWS,
+             (long)L, (long)ld_ids, (long)V, (long)ld_words);
+  hipLaunchKernelGGL(text_seen_mark_kernel, dim3((unsigned)((L + TXT_HT - 1) / TXT_HT), (unsigned)R), dim3(TXT_HT), 0, st, seen, ld_words, ids,
+                     ld_ids, (int)L, valid, (int)V);
+  UG_CHECK_LAUNCH("ug_text_seen_mark");
+  return UG_OK;
+}
+
+extern "C" int ug_text_penalize(float* logits, int64_t ld, int64_t R, int64_t V, float penalty, int* seen, int64_t ld_words,
+                                const int64_t* tok, hipStream_t st) {
+  UG_REQUIRE(logits && seen, "ug_text_penalize: null argument");
+  UG_REQUIRE(R > 0 && R <= TXT_MAX_ROWS && V > 0 && ld >= V && R * ld < (1ll << 31) && ld_words >= (V + 31) / 32,
+             "ug_text_penalize: bad sizes (R=%ld <= %d, V=%ld <= ld=%ld, R*ld < 2^31, ld_words=%ld >= ceil(V / 32))", (long)R, TXT_MAX_ROWS,
+             (long)V, (long)ld, (long)ld_words);
+  UG_REQUIRE(penalty > 0.f && penalty <= 3.402823466e38f, "ug_text_penalize: penalty=%g must be finite and > 0", (double)penalty);
+  const int64_t W = (V + 31) / 32;
+  hipLaunchKernelGGL(text_penalize_kernel, dim3((unsigned)((W + TXT_HT - 1) / TXT_HT), (unsigned)R), dim3(TXT_HT), 0, st, logits, ld, (int)V,
+                     penalty, seen, ld_words, tok);
+  UG_CHECK_LAUNCH("ug_text_penalize");
   return UG_OK;
 }

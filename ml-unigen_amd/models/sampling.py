@@ -137,3 +137,24 @@ def top_k_top_p_filtering(logits, top_k=0, top_p=1.0, filter_value=-float("Inf")
         drop[..., 0] = 0
         logits[drop.scatter(1, order, drop)] = filter_value
     return logits
+
+
+def apply_repetition_penalty(logits, seen_mask, penalty):
+    """transformers' RepetitionPenaltyLogitsProcessor on fp32 [R, V] logits, ahead of temperature / top-k / top-p: every id the bool
+    mask `seen_mask` [R, V] marks (it occurs in the row's sequence so far: real prompt ids + emitted tokens) has its score multiplied
+    by `penalty` if negative, divided by it otherwise -- once per distinct id.  Returns a new tensor.  The host text loops use it; the
+    on-device loop's kernel (include/unigen_hip.h: ug_text_penalize) applies the same rule to the bf16-rounded score."""
+    return torch.where(seen_mask, torch.where(logits < 0, logits * penalty, logits / penalty), logits)
+
+
+def seen_mask_of(ids, valid, rows, vocab, device):
+    """the bool [rows, vocab] mask of apply_repetition_penalty at the start of a call: ids [rows, L] (None: no ids, nothing seen) at
+    the positions `valid` [rows, L] marks real (None: all); ids outside [0, vocab) are ignored"""
+    seen = torch.zeros((rows, vocab + 1), dtype=torch.bool, device=device)
+    if ids is not None:
+        ids = ids.to(device).long()
+        ok = (ids >= 0) & (ids < vocab)
+        if valid is not None:
+            ok &= valid.to(device) != 0
+        seen.scatter_(1, torch.where(ok, ids, torch.full_like(ids, vocab)), True)
+    return seen[:, :vocab]

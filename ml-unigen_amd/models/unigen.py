@@ -18,6 +18,7 @@ Behavioural notes (all mirror the reference unless stated):
     generation; t2i_generate_ar with it raises.
 """
 import json
+import math
 import os
 import time
 import weakref
@@ -100,6 +101,29 @@ def emit_until_stop(out, stop, pad_token_id=None, lengths=None):
         done.logical_or_(hit)
         return nxt, bool(done.all())
     return emit
+
+
+def checked_repetition_penalty(p, who):
+    """a call's `repetition_penalty` as a float (None: 1.0 = off); anything not finite and > 0 raises, before any launch"""
+    if p is None:
+        return 1.0
+    p = float(p)
+    if not (math.isfinite(p) and p > 0.0):
+        raise UniGenHipError(f"{who}: repetition_penalty={p} must be finite and > 0 (1 is off)")
+    return p
+
+
+def with_repetition_penalty(pick, emit, penalty, seen):
+    """`pick` and `emit` of text_token_loop with transformers' repetition penalty in front of the pick (models/sampling.py:
+    apply_repetition_penalty): seen bool [R, V] holds the row's sequence so far and takes every token `emit` feeds back (a finished
+    row's pad id included, as on the device)."""
+    from .sampling import apply_repetition_penalty
+
+    def emit_and_mark(i, nxt):
+        feed, stop = emit(i, nxt)
+        seen.scatter_(1, feed, True)
+        return feed, stop
+    return (lambda last: pick(apply_repetition_penalty(last, seen, penalty))), emit_and_mark
 
 
 class UniGen(ModelMixin, ConfigMixin):
@@ -826,12 +850,33 @@ class UniGen(ModelMixin, ConfigMixin):
         run of equal logits kept or dropped whole by top-p), where the host loop calls torch.multinomial -- the feature is opt-in
         for that reason.  An explicit True on a call the loop cannot serve (more than 32 rows, use_cache=False, more than 8 stop
         ids, a hidden size below 256 or no multiple of 32) raises; a default-derived True falls back to the host loop.
-        kwargs: use_graph=False runs the on-device steps eagerly; trace=list receives every eager step's fp32 logits."""
+        kwargs: use_graph=False runs the on-device steps eagerly; trace=list receives every eager step's raw fp32 head logits.
+        repetition_penalty=p (finite, > 0; None or 1: off): transformers' RepetitionPenaltyLogitsProcessor ahead of temperature /
+        top-k / top-p -- every id in the row's sequence so far (prompt ids at the positions the mask marks real + the tokens emitted;
+        with an `input_embeddings` prompt the emitted tokens only) has its score multiplied by p if negative, divided by p otherwise.
+        The host loop applies it in fp32 to the fp32 copy of the head's bf16 logits, the on-device loop to the bf16-rounded logit with
+        the fp32 result stored back (include/unigen_hip.h: ug_text_penalize), so greedy tokens of the two loops can differ only where
+        two processed values fall within one bf16 step of each other.
+        num_return_sequences=n: every prompt row, with its mask row, is repeated n times consecutively before the prefill
+        (transformers' order); the result has B * n rows.  n > 1 needs do_sample.  On the device the B * n rows draw independent
+        uniforms from the one torch.rand((max_new_tokens, B * n)); the 32-row limit applies to B * n.
+        num_beams and penalty_alpha are refused."""
         from unigen_hip.qwen2 import DecodeState, resolve_deterministic
-        from .sampling import top_k_top_p_filtering
-        unsupported = [k for k in ("num_beams", "num_return_sequences", "repetition_penalty", "penalty_alpha") if kwargs.get(k) not in (None, 1, 1.0)]
+        from .sampling import seen_mask_of, top_k_top_p_filtering
+        unsupported = [k for k in ("num_beams", "penalty_alpha") if kwargs.get(k) not in (None, 1, 1.0)]
         if unsupported:
             raise UniGenHipError(f"generate: {unsupported} are not implemented (greedy / sampling only)")
+        penalty = checked_repetition_penalty(kwargs.get("repetition_penalty"), "generate")
+        n_ret = kwargs.get("num_return_sequences")
+        n_ret = 1 if n_ret is None else int(n_ret)
+        if n_ret < 1:
+            raise UniGenHipError(f"generate: num_return_sequences={n_ret} must be at least 1")
+        if n_ret > 1 and not do_sample:
+            raise UniGenHipError(f"generate: num_return_sequences={n_ret} needs do_sample=True (greedy rows would all be equal)")
+        if n_ret > 1:
+            input_ids = None if input_ids is None else input_ids.repeat_interleave(n_ret, dim=0)
+            input_embeddings = None if input_embeddings is None else input_embeddings.repeat_interleave(n_ret, dim=0)
+            attention_mask = None if attention_mask is None else attention_mask.repeat_interleave(n_ret, dim=0)
         if "max_length" in kwargs and kwargs["max_length"] is not None and input_ids is not None:
             max_new_tokens = int(kwargs["max_length"]) - input_ids.shape[1]
         eng = self.llm.engine
@@ -856,7 +901,8 @@ class UniGen(ModelMixin, ConfigMixin):
                 sampling = (float(1.0 if temperature is None else temperature), int(top_k or 0), float(1.0 if top_p is None else top_p))
             out, _, _ = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, sampling=sampling, stop=eos,
                                                     pad_token_id=pad_token_id if eos else None, generator=generator,
-                                                    use_graph=bool(kwargs.get("use_graph", True)), trace=kwargs.get("trace"))
+                                                    use_graph=bool(kwargs.get("use_graph", True)), trace=kwargs.get("trace"),
+                                                    repetition_penalty=penalty, prompt_ids=None if input_embeddings is not None else input_ids.to(dev))
             return torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
         st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, key_valid)
@@ -873,7 +919,11 @@ class UniGen(ModelMixin, ConfigMixin):
             return torch.multinomial(torch.softmax(last, dim=-1).to(u_dev), num_samples=1, generator=generator).to(dev)
 
         stop = torch.tensor(eos, device=dev) if eos else None
-        out = out[:, :self._decode_text(st, hn, max_new_tokens, pick, emit_until_stop(out, stop, pad_token_id))]
+        emit = emit_until_stop(out, stop, pad_token_id)
+        if penalty != 1.0:
+            seen = seen_mask_of(None if input_embeddings is not None else input_ids, key_valid, R, self.config.vocab_size, dev)
+            pick, emit = with_repetition_penalty(pick, emit, penalty, seen)
+        out = out[:, :self._decode_text(st, hn, max_new_tokens, pick, emit)]
         if input_embeddings is None:
             return torch.cat([input_ids.to(dev), out], dim=1)
         return out
@@ -881,7 +931,7 @@ class UniGen(ModelMixin, ConfigMixin):
     # ------------------------------------------------------------------ text decoding for understanding
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
-                     top_k=None, eot_token=None, use_cache=True, deterministic=None, on_device=None, use_graph=True):
+                     top_k=None, eot_token=None, use_cache=True, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0):
         """Greedy / top-k text continuation (reference models/unigen.py:523-581).  The reference re-runs the whole
         growing sequence every step and extends the additive mask by one row that copies the previous last row;
         here the prompt is prefilled once under its mask into the static KV cache and every new token is one decode
@@ -890,8 +940,11 @@ class UniGen(ModelMixin, ConfigMixin):
         decode kernels for the cached form; None follows torch.are_deterministic_algorithms_enabled().
         on_device / use_graph: the token loop on the device, as in `generate` (temperature 0 is greedy; with temperature > 0 the draw is
         temperature -> top-k -> inverse CDF on uniforms drawn up front, so sampled tokens differ from the host loop's for the same
-        seed).  Cached form only: an explicit True with use_cache=False raises."""
+        seed).  Cached form only: an explicit True with use_cache=False raises.
+        repetition_penalty: as in `generate`, cached form only (both loops); the prompt ids are `idx` at the keys the prompt's last row
+        sees, nothing with an `input_embeddings` prompt.  The recompute form raises for a penalty other than 1."""
         from unigen_hip.qwen2 import resolve_deterministic
+        penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate")
         det = resolve_deterministic(deterministic)
         self.llm.engine.last_decode_deterministic = det
         cached = bool(use_cache and attention_mask is not None and attention_mask.shape[0] == 1)
@@ -899,7 +952,10 @@ class UniGen(ModelMixin, ConfigMixin):
         self.llm.engine.last_text_decode_on_device = dev_loop
         if cached:
             return self._mmu_generate_cached(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
-                                             on_device=dev_loop, use_graph=use_graph)
+                                             on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty)
+        if penalty != 1.0:
+            raise UniGenHipError("mmu_generate: repetition_penalty needs the cached form (use_cache=True and a one-row mask); the recompute "
+                                 "form does not apply it")
         return self._mmu_generate_recompute(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token)
 
     @staticmethod
@@ -949,7 +1005,7 @@ class UniGen(ModelMixin, ConfigMixin):
         raise UniGenHipError(f"{who}: on_device=True cannot serve this call: {why}")
 
     def _decode_text_on_device(self, prompt, max_new_tokens, det, key_valid=None, mask_bits=None, sampling=None, stop=(), pad_token_id=None,
-                               generator=None, use_graph=True, trace=None):
+                               generator=None, use_graph=True, trace=None, repetition_penalty=1.0, prompt_ids=None):
         """The token loop of `text_token_loop` + `emit_until_stop` with nothing but launches per token: prefill, token 0 eagerly from
         the prefill's hidden state (GEMV head + pick), step 1 eagerly (warm-up), step 2 captured (its first replay IS step 2), replays
         from there.  The pick launch applies the stop rule on the device; with stop ids the host reads `remaining` every 8 tokens and
@@ -958,8 +1014,12 @@ class UniGen(ModelMixin, ConfigMixin):
         so the cut result is the host loop's.  No decode step follows the last token.
         The session (Qwen2Engine.text_step's buffers + the graph) is kept across calls like the AR path's: reused when rows, the KV
         capacity (prompt + new tokens rounded up to 128), the token-buffer width (new tokens rounded up to 64), layer form, mode,
-        sampling constants, stop ids, pad id, presence of a key-validity mask and the weight storage agree; `drop_decode_session()`
-        and `train()` drop it, UNIGEN_AR_GRAPH_CACHE=0 turns the reuse off.
+        sampling constants, the repetition penalty (a kernel argument of the captured step), stop ids, pad id, presence of a
+        key-validity mask and the weight storage agree; `drop_decode_session()` and `train()` drop it, UNIGEN_AR_GRAPH_CACHE=0 turns
+        the reuse off.
+        repetition_penalty p != 1: the session's logits processor runs between head and pick of every step (ug_text_penalize); its
+        `seen` bitmap is zeroed here and takes prompt_ids [R, L] (None: no ids) at the positions key_valid marks real, one launch
+        outside the captured step.  p == 1 allocates and launches nothing.
         -> (tokens int64 [R, steps], lengths int64 [R], steps)."""
         from unigen_hip.qwen2 import TextDecodeSession
         eng = self.llm.engine
@@ -974,7 +1034,8 @@ class UniGen(ModelMixin, ConfigMixin):
         cap, width = ops.round_up(L + n, 128), ops.round_up(n, 64)
         pad = None if pad_token_id is None else int(pad_token_id)
         n_layers = eng.dims.num_hidden_layers
-        key = (R, cap, width, V, eng.decode_form(R, det), det, sampling, tuple(stop), pad, key_valid is None, str(dev),
+        penalty = float(repetition_penalty)
+        key = (R, cap, width, V, eng.decode_form(R, det), det, sampling, penalty, tuple(stop), pad, key_valid is None, str(dev),
                eng.fp.w("embed").data_ptr(), eng.fp.w("l0.wqkv").data_ptr(), eng.fp.p("embed").data_ptr(), eng.fp.p("norm").data_ptr(),
                eng.fp.w(f"l{n_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(cap)))
         keep = use_graph and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0"
@@ -983,11 +1044,12 @@ class UniGen(ModelMixin, ConfigMixin):
             sess = None
         eng._text_session = None                     # (put back at the end of a call that completed)
         if sess is None:
-            sess = TextDecodeSession(eng, R, cap, width, V, deterministic=det, sampling=sampling, stop_ids=stop, pad_id=pad, key_valid=key_valid)
+            sess = TextDecodeSession(eng, R, cap, width, V, deterministic=det, sampling=sampling, stop_ids=stop, pad_id=pad, key_valid=key_valid,
+                                     repetition_penalty=penalty)
             sess.key = key
-            sess.begin(n)
+            sess.begin(n, prompt_ids=prompt_ids, prompt_valid=key_valid)
         else:
-            sess.begin(n, key_valid, L)
+            sess.begin(n, key_valid, L, prompt_ids=prompt_ids, prompt_valid=key_valid)
         if sampling is not None:
             u_dev = dev if generator is None else generator.device
             sess.uniforms[:n].copy_(torch.rand((n, R), device=u_dev, generator=generator))
@@ -1028,10 +1090,12 @@ class UniGen(ModelMixin, ConfigMixin):
                                step=lambda x: eng.decode_step(st, x))            # (also advances the cache position)
 
     def _mmu_decode(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det, on_device=False,
-                    use_graph=True):
+                    use_graph=True, repetition_penalty=1.0, trace=None):
         """Prefill R left-padded rows under their dense [R, 1, L, L] masks, then decode -> (tokens [R, max_new_tokens] on the device,
-        the rows' lengths cut after `eot_token` [R], the number of steps taken)."""
+        the rows' lengths cut after `eot_token` [R], the number of steps taken).  repetition_penalty: the prompt ids are `idx` (when the
+        prompt is not given as embeddings) at the keys the prompt's last row sees."""
         from unigen_hip.qwen2 import DecodeState
+        from .sampling import seen_mask_of
         eng = self.llm.engine
         prompt = (self.llm.model.embed_tokens(idx) if input_embeddings is None else input_embeddings).float()
         dev = prompt.device
@@ -1042,7 +1106,9 @@ class UniGen(ModelMixin, ConfigMixin):
         if on_device:
             sampling = (float(temperature), int(top_k or 0), 1.0) if temperature > 0 else None
             tokens, lengths, steps = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, mask_bits=mb, sampling=sampling,
-                                                                 stop=self._stop_list(eot_token), use_graph=use_graph)
+                                                                 stop=self._stop_list(eot_token), use_graph=use_graph, trace=trace,
+                                                                 repetition_penalty=repetition_penalty,
+                                                                 prompt_ids=idx if input_embeddings is None else None)
             if steps < max_new_tokens:              # (the host loop's shapes: the buffer is max_new_tokens wide)
                 tokens = torch.cat([tokens, tokens.new_zeros((R, max_new_tokens - steps))], dim=1)
             return tokens, lengths, steps
@@ -1050,22 +1116,25 @@ class UniGen(ModelMixin, ConfigMixin):
         hn = eng.prefill(st, prompt, mask_bits=mb)
         tokens = torch.zeros((R, max_new_tokens), dtype=torch.long, device=dev)
         lengths = torch.full((R,), max_new_tokens, dtype=torch.long, device=dev)
-        steps = self._decode_text(st, hn, max_new_tokens, lambda last: self._pick_next(last, temperature, top_k),
-                                  emit_until_stop(tokens, eot_token, lengths=lengths))
+        pick, emit = (lambda last: self._pick_next(last, temperature, top_k)), emit_until_stop(tokens, eot_token, lengths=lengths)
+        if repetition_penalty != 1.0:
+            seen = seen_mask_of(idx if input_embeddings is None else None, key_valid, R, self.config.vocab_size, dev)
+            pick, emit = with_repetition_penalty(pick, emit, repetition_penalty, seen)
+        steps = self._decode_text(st, hn, max_new_tokens, pick, emit)
         return tokens, lengths, steps
 
     @torch.no_grad()
     def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False,
-                             on_device=False, use_graph=True):
+                             on_device=False, use_graph=True, repetition_penalty=1.0):
         """The one-row case of the batch path -> list of 0-d device tensors (one row: it ends at its `eot_token`, so every step counts)."""
         L = attention_mask.shape[-1]
         tokens, _, steps = self._mmu_decode(idx, input_embeddings, attention_mask.reshape(1, 1, L, L), max_new_tokens, temperature, top_k,
-                                            eot_token, det, on_device=on_device, use_graph=use_graph)
+                                            eot_token, det, on_device=on_device, use_graph=use_graph, repetition_penalty=repetition_penalty)
         return list(tokens[0, :steps])
 
     @torch.no_grad()
     def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=0.0,
-                           top_k=None, eot_token=None, deterministic=None, on_device=None, use_graph=True):
+                           top_k=None, eot_token=None, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0, trace=None):
         """`mmu_generate` for up to 32 prompts at once -- the rating loop of CoT-V (reference
         evaluation/inference_unigen_cot.py:308-415 calls mmu_generate once per (image, question) pair; every decode
         step streams the whole backbone whatever the row count, so R pairs cost about one).  Rows are LEFT-padded to a
@@ -1074,8 +1143,10 @@ class UniGen(ModelMixin, ConfigMixin):
         procedure of `mmu_generate`: prefill under its mask, then one decode step per token attending to the keys its
         last prompt row could see plus everything generated since.  Returns R lists of tokens, each cut after its
         `eot_token`.  deterministic: ordered decode kernels; None follows torch.are_deterministic_algorithms_enabled().
-        on_device / use_graph: the token loop on the device, as in `mmu_generate`."""
+        on_device / use_graph: the token loop on the device, as in `mmu_generate`.  repetition_penalty: as in `mmu_generate`, both
+        loops.  trace: a list that receives every eager on-device step's raw fp32 head logits (use_graph=False)."""
         from unigen_hip.qwen2 import resolve_deterministic
+        penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate_batch")
         det = resolve_deterministic(deterministic)
         self.llm.engine.last_decode_deterministic = det
         R, L = (idx if input_embeddings is None else input_embeddings).shape[:2]
@@ -1086,7 +1157,7 @@ class UniGen(ModelMixin, ConfigMixin):
         dev_loop = self._text_on_device(on_device, "mmu_generate_batch", R, True, eot_token, max_new_tokens)
         self.llm.engine.last_text_decode_on_device = dev_loop
         tokens, lengths, _ = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
-                                              on_device=dev_loop, use_graph=use_graph)
+                                              on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace)
         tokens, lengths = tokens.cpu(), lengths.cpu()
         return [list(tokens[r, :int(lengths[r])]) for r in range(R)]
 

@@ -826,6 +826,41 @@ def text_sample_(logits, V, state, nsteps, embed_master, tok, out_tokens, x, uni
                                       _p(state), int(nsteps), _p(tok), _p(out_tokens), _p(lengths), _p(x), _stream()), "ug_text_sample")
 
 
+def text_seen(rows, V, device):
+    """the zeroed "seen" bitmap of the repetition penalty for `rows` rows: int32 [rows, ceil(V / 32)], bit (e & 31) of word (e >> 5) = id e
+    occurs in the row's sequence so far (include/unigen_hip.h: ug_text_penalize)"""
+    return torch.zeros((int(rows), (int(V) + 31) // 32), dtype=torch.int32, device=device)
+
+
+def text_seen_mark_(seen, ids, V, valid=None):
+    """sets the bits of the prompt ids int64 [R, L] at the positions `valid` ([R, L], nonzero = real; None: all) marks; ids outside
+    [0, V) are ignored (include/unigen_hip.h: ug_text_seen_mark)"""
+    ids = ids.long()
+    if ids.stride(1) != 1:
+        ids = ids.contiguous()
+    if valid is not None:
+        valid = valid.to(torch.uint8).contiguous()
+        if tuple(valid.shape) != tuple(ids.shape):
+            raise _l.UniGenHipError(f"text_seen_mark_: valid {tuple(valid.shape)} against ids {tuple(ids.shape)}")
+    _need_cuda(seen, ids)
+    if seen.shape[0] != ids.shape[0] or seen.stride(1) != 1:
+        raise _l.UniGenHipError(f"text_seen_mark_: seen {tuple(seen.shape)} against ids {tuple(ids.shape)}")
+    _l.check(_l.load().ug_text_seen_mark(_p(seen), seen.stride(0), _p(ids), ids.stride(0), ids.shape[0], ids.shape[1], _p(valid), int(V),
+                                         _stream()), "ug_text_seen_mark")
+    return seen
+
+
+def text_penalize_(logits, V, penalty, seen, tok=None):
+    """The repetition penalty on fp32 logits [R, ld >= V] in place, between the head and the pick: the token of the previous step (tok
+    int64 [R] or None) joins `seen`, then every seen id's logit becomes bf16round(s) * p if negative else bf16round(s) / p, in fp32
+    (include/unigen_hip.h: ug_text_penalize).  Unseen entries are not touched."""
+    _need_cuda(logits, seen)
+    if seen.shape[0] != logits.shape[0] or seen.stride(1) != 1 or logits.stride(1) != 1:
+        raise _l.UniGenHipError(f"text_penalize_: seen {tuple(seen.shape)} against logits {tuple(logits.shape)}")
+    _l.check(_l.load().ug_text_penalize(_p(logits), logits.stride(0), logits.shape[0], int(V), float(penalty), _p(seen), seen.stride(0),
+                                        _p(tok), _stream()), "ug_text_penalize")
+
+
 # ------------------------------------------------------------------------------------ loss
 def ce_fwd(logits, V, labels, ignore_index=-100, want_logp=False):
     """logits bf16 [R, ld>=V]; -> (loss_and_count [2], lse [R], loss_row [R], logp|None)"""

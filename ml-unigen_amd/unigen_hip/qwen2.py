@@ -245,9 +245,12 @@ class TextDecodeSession:
     cache of `capacity` positions), the pick kernels' state block, the next input `x`, the last token, the token buffer [rows, width],
     the rows' lengths, the head's fp32 logits, and for sampling the histogram workspace and the uniforms [width, rows].
     sampling: None (greedy) or (temperature, top_k, top_p).  The logits' leading dimension is the vocabulary rounded up to 8, except in
-    deterministic mode, where the ordered head writes a contiguous [rows, vocab] result."""
+    deterministic mode, where the ordered head writes a contiguous [rows, vocab] result.
+    repetition_penalty p != 1: the session owns the logits processor's `seen` bitmap [rows, ceil(vocab / 32)] (include/unigen_hip.h:
+    ug_text_penalize) and every step launches the processor between head and pick; p == 1 allocates and launches nothing."""
 
-    def __init__(self, eng, rows, capacity, width, vocab, deterministic=False, sampling=None, stop_ids=(), pad_id=None, key_valid=None):
+    def __init__(self, eng, rows, capacity, width, vocab, deterministic=False, sampling=None, stop_ids=(), pad_id=None, key_valid=None,
+                 repetition_penalty=1.0):
         dev, d = eng.device, eng.dims
         self.rows, self.width, self.V, self.sampling = rows, width, vocab, sampling
         self.form = eng.decode_form(rows, deterministic)
@@ -264,16 +267,24 @@ class TextDecodeSession:
         if sampling is not None:
             self.workspace = ops.text_sample_workspace(rows, dev)
             self.uniforms = torch.zeros((width, rows), dtype=torch.float32, device=dev)
+        self.penalty = float(repetition_penalty)
+        self.seen = ops.text_seen(rows, vocab, dev) if self.penalty != 1.0 else None
         self.graph, self.key = None, None
 
-    def begin(self, new_tokens, key_valid=None, prompt_len=0):
+    def begin(self, new_tokens, key_valid=None, prompt_len=0, prompt_ids=None, prompt_valid=None):
         """the host's part of a call's start: state block reset, lengths, and (a reused session) the key-validity columns -- the
-        prompt's, ones behind them.  The prefill sets position and length."""
+        prompt's, ones behind them.  The prefill sets position and length.  With a repetition penalty: `seen` zeroed, then the bits
+        of prompt_ids [rows, L] (None: a prompt given as embeddings has no ids) at the positions prompt_valid [rows, L] marks real
+        (None: all)."""
         ops.text_state_reset_(self.state, self.rows)
         self.lengths.fill_(int(new_tokens))
         if key_valid is not None:
             self.st.key_valid[:, :prompt_len].copy_(key_valid)
             self.st.key_valid[:, prompt_len:].fill_(1)
+        if self.seen is not None:
+            self.seen.zero_()
+            if prompt_ids is not None and prompt_ids.shape[1] > 0:
+                ops.text_seen_mark_(self.seen, prompt_ids, self.V, prompt_valid)
 
 
 class _Saved:
@@ -685,8 +696,15 @@ class Qwen2Engine:
             ops.text_sample_(sess.logits, sess.V, sess.state, sess.width, emb, sess.tok, sess.out_tokens, sess.x, sess.uniforms, sess.workspace,
                              temperature=t, top_k=k, top_p=p, **kw)
 
+    def text_penalize(self, sess, first=False):
+        """the logits processor of a text step, between head and pick: the session's repetition penalty on sess.logits (nothing without
+        one).  Token 0 has no previous step (tok = null); every later step passes sess.tok, a constant of the captured graph."""
+        if sess.seen is not None:
+            ops.text_penalize_(sess.logits, sess.V, sess.penalty, sess.seen, tok=None if first else sess.tok)
+
     def text_first_token(self, sess, hn, trace=None):
-        """token 0 from the prefill's final-norm hidden state: the GEMV head (ordered in deterministic mode) + the pick"""
+        """token 0 from the prefill's final-norm hidden state: the GEMV head (ordered in deterministic mode) + the logits processor +
+        the pick.  trace takes the RAW head logits."""
         w_head = self.fp.w("embed")[:sess.V]
         if sess.st.deterministic:
             ops.skinny_linear_ord(hn, w_head, out_f32=sess.logits)
@@ -695,13 +713,14 @@ class Qwen2Engine:
             ops.decode_gemv_(hn, w_head, sess.logits)
         if trace is not None:
             trace.append(sess.logits[:, :sess.V].clone())
+        self.text_penalize(sess, first=True)
         self.text_pick(sess)
 
     def text_step(self, sess, trace=None):
         """One text decode step into the session's static buffers: the decoder stack on sess.x, the head over the whole vocabulary and
-        the pick (token, stop rule, records, next sess.x); advances the cache position.  No host sync, no shape depends on the step:
+        the pick (token, stop rule, records, next sess.x), the session's logits processor between them; advances the cache position.  No host sync, no shape depends on the step:
         capturable.  sw / ord_sw / ord_wide end in decode_step_logits' head launch; splitk and wide run decode_step and the atomic
-        GEMV head into the accumulator the pick leaves zeroed.  trace: optional list taking the step's logits (eager runs only)."""
+        GEMV head into the accumulator the pick leaves zeroed.  trace: optional list taking the step's raw head logits (eager runs only)."""
         w_head = self.fp.w("embed")[:sess.V]
         if sess.form in ("splitk", "wide"):
             ops.decode_gemv_(self.decode_step(sess.st, sess.x), w_head, sess.logits)
@@ -709,6 +728,7 @@ class Qwen2Engine:
             self.decode_step_logits(sess.st, sess.x, w_head, sess.logits)
         if trace is not None and not torch.cuda.is_current_stream_capturing():
             trace.append(sess.logits[:, :sess.V].clone())
+        self.text_penalize(sess)
         self.text_pick(sess)
 
     def decode_step(self, st, x):

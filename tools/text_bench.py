@@ -7,7 +7,14 @@ loop, then five timed calls of each, alternating.  A call's decode time is its w
 Settings: greedy; greedy in deterministic mode; sampled (temperature 1.0, top_k 50: the shape of the CoT-V call); greedy with a stop
 id no row produces (prices the on-device loop's poll of `remaining` every 8 tokens against the host loop's sync per token).
 
-One JSON line: per rows and setting, every call's tokens/s and ms per step for both loops, and the ratio of the medians."""
+One JSON line: per rows and setting, every call's tokens/s and ms per step for both loops, and the ratio of the medians.
+
+    python tools/text_bench.py --repetition-penalty P
+
+times the ON-DEVICE loop alone, greedy, with the logits processor (repetition_penalty=P: one ug_text_penalize launch per step, one
+ug_text_seen_mark per call) against the same build without it, alternating in one process.  The penalty is part of the kept
+session's key, so each visit to a mode makes two calls and times the second (it replays the graph the first one captured), then
+one one-token call of the same session for the prefill + first token.  Five visits per mode after one untimed visit each."""
 import json
 import os
 import statistics
@@ -27,6 +34,52 @@ SETTINGS = {
     "sampled_t1_k50": dict(temperature=1.0, top_k=50),
     "greedy_stop_never_hit": dict(temperature=0.0, eot_token=VOCAB - 1),          # (the mask token: the backbone's argmax never lands there)
 }
+
+
+def penalty_pair(penalty, rounds=5):
+    dev = torch.device("cuda:0")
+    rows = [int(r) for r in os.environ.get("ROWS", "1,16").split(",")]
+    model = UniGen(w_und_encoder=False, vocab_size=VOCAB, llm_vocab_size=TEXT_VOCAB, llm_model_path="Qwen2.5-1.5B-Instruct",
+                   codebook_size=CODEBOOK, num_vq_tokens=NVQ, device=dev, init_seed=-1)
+    model.llm.init_weights_device(1)
+    model.eval()
+    g = torch.Generator(device=dev).manual_seed(2)
+    r = torch.arange(L, device=dev)
+    allow = (r[None, :] <= r[:, None]) | ((r[None, :] >= 20) & (r[None, :] < 749))
+    result = {"prompt": L, "new_tokens": NEW, "repetition_penalty": penalty, "loop": "device", "setting": "greedy", "rows": {}}
+    modes = (("off", 1.0), ("on", float(penalty)))
+    for R in rows:
+        idx = torch.randint(0, 151643, (R, L), device=dev, generator=g)
+        mask = torch.where(allow, 0.0, torch.finfo(torch.float32).min)[None, None].expand(R, 1, L, L).contiguous()
+
+        def call(p, new=NEW):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = model.mmu_generate_batch(idx=idx, attention_mask=mask, max_new_tokens=new, temperature=0.0, on_device=True, repetition_penalty=p)
+            torch.cuda.synchronize()
+            assert all(len(o) == new for o in out) and model.llm.engine.last_text_decode_on_device
+            return time.perf_counter() - t0
+
+        times, first = {name: [] for name, _ in modes}, {name: [] for name, _ in modes}
+        for visit in range(rounds + 1):
+            for name, p in modes:
+                call(p)                                  # captures: the other mode's session was the kept one
+                t, t1 = call(p), call(p, 1)
+                if visit:
+                    times[name].append(t)
+                    first[name].append(t1)
+        rec = {}
+        for name, _ in modes:
+            f = statistics.median(first[name])
+            step_ms = [1e3 * (t - f) / (NEW - 1) for t in times[name]]
+            rec[name] = {"call_s": [round(t, 4) for t in times[name]], "first_token_call_s": round(f, 4),
+                         "ms_per_step": [round(m, 4) for m in step_ms], "tokens_per_s": [round(1e3 * R / m, 1) for m in step_ms]}
+        med = lambda name: statistics.median(rec[name]["ms_per_step"])
+        rec["on_over_off_tokens_per_s"] = round(med("off") / med("on"), 4)
+        rec["extra_us_per_step"] = round(1e3 * (med("on") - med("off")), 2)
+        result["rows"][str(R)] = rec
+        model.drop_decode_session()
+    print(json.dumps(result))
 
 
 def main():
@@ -78,4 +131,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 2 and sys.argv[1] == "--repetition-penalty":
+        penalty_pair(float(sys.argv[2]))
+    else:
+        main()
