@@ -359,6 +359,27 @@ int ug_ar_sample_filtered(float* acc, int64_t ldacc, int64_t bsz, int64_t V, flo
                           int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, int64_t top_k,
                           float top_p, float min_p, float* stats, hipStream_t stream);
 
+/* ---- per-token log-probabilities of the AR samplers --------------------------------------------- */
+/* ug_ar_sample / ug_ar_sample_filtered with one more output, logp fp32 [bsz][nsteps][2] (null: an argument error -- callers that want
+ * no output use the entry points above); everything else (token, out_tokens, x, the cleared accumulator, stats) is bit for bit what
+ * those compute on the same inputs.  All values are natural logs, at most 0.  With c~, u~ the bf16-rounded conditional and unconditional
+ * rows, v[e] = (u~[e] + s * (c~[e] - u~[e])) * (1 / temperature) and mx = max v as above, and step = *pos_dev - pos0 (the indexing of
+ * out_tokens: the token drawn from the prefill is step 0):
+ *   logp[(b * nsteps + step) * 2 + 0] = v[tok] - mx - log(sum over the kept e of exp(v[e] - mx)): the log-probability under the
+ *     distribution the token was drawn from, after CFG, temperature and truncation.  Kept = [0, V) for ug_ar_sample_logp, {v >= tau} for
+ *     ug_ar_sample_filtered_logp, and [0, V) at the call's temperature with greedy (the filters are ignored, as for the pick).
+ *   logp[(b * nsteps + step) * 2 + 1] = c~[tok] - max c~ - log(sum over e < V of exp(c~[e] - max c~)): the conditional model's own
+ *     log-softmax -- no CFG, no temperature, no truncation; what a teacher-forced pass would score.
+ * Every float sum runs in a fixed order (chunk in index order, tree over the wave, the sixteen wave partials in wave order) and there
+ * are no float atomics: logp is a bit-reproducible function of the inputs. */
+int ug_ar_sample_logp(float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature, int greedy,
+                      const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps, const float* embed, int64_t ld_embed,
+                      int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, float* logp, hipStream_t stream);
+int ug_ar_sample_filtered_logp(float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature, int greedy,
+                               const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps, const float* embed,
+                               int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, int64_t top_k,
+                               float top_p, float min_p, float* stats, float* logp, hipStream_t stream);
+
 /* ---- text decode: the pick over the whole vocabulary (csrc/text_sampler.hip) --------------------- */
 /* One text decode step behind the head, for R <= 32 rows: the token of every row, the stop rule of the host loop
  * (models/unigen.py: emit_until_stop), the token's slot in the output buffer and the next step's input.
@@ -399,6 +420,27 @@ int ug_text_sample(float* logits, int64_t ld, int64_t R, int64_t V, int clear, f
                    const float* uniforms, int* workspace, float* stats, const int64_t* stop_ids, int64_t n_stop, int64_t pad_id,
                    const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
                    int* out_tokens, int* lengths, float* x, hipStream_t stream);
+
+/* ug_text_pick / ug_text_sample with one more output, logp fp32 [R][nsteps] (null: an argument error -- callers that want no output use
+ * the entry points above); tokens, records, state, x, the cleared logits and the workspace are bit for bit what those leave.  This is
+ * transformers' compute_transition_scores(..., normalize_logits=True): the log-softmax of the PROCESSED scores at the emitted token, a
+ * natural log, at most 0.
+ *   ug_text_pick_logp:   s[e] = the logit rounded to bf16 (behind ug_text_penalize, if the caller runs it; no temperature);
+ *                        logp[r * nsteps + step] = s[tok] - max s - log(sum over e < V of exp(s[e] - max s)).
+ *   ug_text_sample_logp: v, the kept set and T (the kept mass relative to max v) as ug_text_sample defines them;
+ *                        logp[r * nsteps + step] = v[tok] - max v - log T.
+ * A NaN entry contributes nothing (it is no candidate), -inf contributes 0.  A row that was done BEFORE the step records 0.0 (whether it
+ * emits pad_id or, without one, goes on emitting tokens); the step that emits the stop id records its real value.  Nothing is written
+ * for step >= nsteps.  The greedy sum is formed in the pick's single pass over the row (per thread a running maximum and a sum rescaled
+ * to it, then rescaled to the row's maximum, a tree over the wave, the sixteen wave partials in wave order); the sampled form takes T
+ * from the selection launch.  Fixed order, no float atomics: a bit-reproducible function of the inputs. */
+int ug_text_pick_logp(float* logits, int64_t ld, int64_t R, int64_t V, int clear, const int64_t* stop_ids, int64_t n_stop, int64_t pad_id,
+                      const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
+                      int* out_tokens, int* lengths, float* x, float* logp, hipStream_t stream);
+int ug_text_sample_logp(float* logits, int64_t ld, int64_t R, int64_t V, int clear, float temperature, int64_t top_k, float top_p,
+                        const float* uniforms, int* workspace, float* stats, const int64_t* stop_ids, int64_t n_stop, int64_t pad_id,
+                        const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
+                        int* out_tokens, int* lengths, float* x, float* logp, hipStream_t stream);
 
 /* Logits processor of the on-device text loop: transformers' RepetitionPenaltyLogitsProcessor.  THE RULE: for every token id that
  * occurs in the row's sequence so far, s <- s * p if s < 0 else s / p; once per distinct id, however often the id occurs; ahead of

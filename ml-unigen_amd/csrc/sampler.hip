@@ -128,18 +128,73 @@ __device__ __forceinline__ int ar_pad(int e) { return e + (e >> 5); }      // ch
 // 1 024 threads (round 5; was 256 with an O(threads) serial scan of the partial sums: 16.7 us per step): eight loads per row per
 // thread, the inverse CDF through a wave scan (shuffles) + sixteen wave totals, the rest unchanged.
 constexpr int ARS_T = 1024;
+constexpr int AR_PER = AR_MAXV / ARS_T;
+
+// LOGP instantiations (ug_ar_sample_logp / ug_ar_sample_filtered_logp): the conditional model's own log-softmax at the chosen token.
+// Thread t keeps the bf16-rounded conditional values it loaded in pass 1 (entries t + j * ARS_T) in registers: the accumulator rows are
+// cleared by then and `mix` holds the mixed values only.  Per thread (max, sum of exp(value - max)) over those registers; the block
+// maximum through `cmx_w`, the sum rescaled to it through an xor tree over the wave and the sixteen wave partials in wave order: fixed
+// order, no atomics.
+struct ArCond { float mx, sum; };
+__device__ __forceinline__ ArCond ar_cond_local(const float (&cv)[AR_PER], int t, int V) {
+  ArCond c{-INFINITY, 0.f};
+#pragma unroll
+  for (int j = 0; j < AR_PER; ++j)
+    if (t + j * ARS_T < V) c.mx = fmaxf(c.mx, cv[j]);
+#pragma unroll
+  for (int j = 0; j < AR_PER; ++j)
+    if (t + j * ARS_T < V) c.sum += expf(cv[j] - c.mx);
+  return c;
+}
+// behind the barrier that published cmx_w: the block maximum; the wave's partial of the rescaled sum goes to csum_w (read it behind the
+// next barrier with ar_cond_total)
+__device__ __forceinline__ float ar_cond_merge(const ArCond& c, const float* cmx_w, float* csum_w, int lane, int wave) {
+  float cmax = cmx_w[0];
+#pragma unroll
+  for (int w = 1; w < ARS_T / 64; ++w) cmax = fmaxf(cmax, cmx_w[w]);
+  float part = c.sum > 0.f ? __fmul_rn(c.sum, expf(c.mx - cmax)) : 0.f;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+  if (lane == 0) csum_w[wave] = part;
+  return cmax;
+}
+__device__ __forceinline__ float ar_cond_total(const float* csum_w) {
+  float s = 0.f;
+#pragma unroll
+  for (int w = 0; w < ARS_T / 64; ++w) s += csum_w[w];
+  return s;
+}
+// logp[(b * nsteps + step) * 2 + {0, 1}]: thread 0 writes the log-probability under the drawn-from distribution, the thread that loaded
+// the token's conditional value writes the conditional log-softmax
+__device__ __forceinline__ void ar_write_logp(float* __restrict__ logp, int b, int nsteps, int step, int token, float v_tok, float bmx,
+                                              float total, const float (&cv)[AR_PER], float cmax, float ctotal, int t) {
+  float* out = logp + ((int64_t)b * nsteps + step) * 2;
+  if (t == 0) out[0] = (v_tok - bmx) - logf(total);
+  if (t == (token & (ARS_T - 1))) {
+    uint32_t bits = 0u;                                        // (an OR of selected patterns: the values stay in registers, where an
+#pragma unroll                                                 //  indexed read of cv[token >> 10] would move the array to memory)
+    for (int j = 0; j < AR_PER; ++j) bits |= (token >> 10) == j ? __float_as_uint(cv[j]) : 0u;
+    out[1] = (__uint_as_float(bits) - cmax) - logf(ctotal);
+  }
+}
+static_assert(ARS_T == 1024, "ar_write_logp: token >> 10 is the slot of the thread that loaded it");
+
+template <bool LOGP>
 __global__ __launch_bounds__(ARS_T) void ar_sample_kernel(float* __restrict__ acc, int64_t lda, int bsz, int V, float scale,
                                                          float inv_temp, int greedy, const float* __restrict__ uniforms,
                                                          const int* __restrict__ pos_dev, int pos0, int nsteps,
                                                          const float* __restrict__ embed, int64_t lde, int H, int64_t id_offset,
                                                          int64_t* __restrict__ tok, int* __restrict__ out_tokens,
-                                                         float* __restrict__ x) {
+                                                         float* __restrict__ x, float* __restrict__ logp) {
   __shared__ float mix[AR_MAXV + AR_MAXV / 32];
   __shared__ float red[ARS_T / 64];
   __shared__ float wtot[ARS_T / 64];
   __shared__ int hit;
   __shared__ int best_i[ARS_T / 64];
   __shared__ int chosen;
+  __shared__ float cmx_w[LOGP ? ARS_T / 64 : 1], csum_w[LOGP ? ARS_T / 64 : 1];
+  float cvr[AR_PER] = {};                                        // (LOGP: the conditional values this thread loaded)
+  ArCond cl{-INFINITY, 0.f};
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   // the position word (written by the head launch in front of us): a hand-issued SCALAR load (vmem_asm.h: hipcc reads such a word with a
   // vector load and waits vmcnt(0) for it on the spot, a serialised round trip ahead of the logits' loads); used behind pass 1
@@ -167,8 +222,10 @@ __global__ __launch_bounds__(ARS_T) void ar_sample_kernel(float* __restrict__ ac
         const float v = (uv + scale * (cv - uv)) * inv_temp;
         mix[ar_pad(e)] = v;
         if (v > mx) { mx = v; arg = e; }
+        if (LOGP) cvr[j] = cv;
       }
     }
+    if (LOGP) cl = ar_cond_local(cvr, t, V);
   }
   wait_lgkm0();
   tie_s(pos_now);
@@ -180,14 +237,32 @@ __global__ __launch_bounds__(ARS_T) void ar_sample_kernel(float* __restrict__ ac
     const float om = __shfl_xor(mx, o, 64); const int oi = __shfl_xor(arg, o, 64);
     if (om > mx || (om == mx && oi < arg)) { mx = om; arg = oi; }
   }
+  if (LOGP) {
+    float cm = cl.mx;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cm = fmaxf(cm, __shfl_xor(cm, o, 64));
+    if (lane == 0) cmx_w[wave] = cm;
+  }
   if (lane == 0) { red[wave] = mx; best_i[wave] = arg; }
   if (t == 0) hit = ARS_T - 1;
   __syncthreads();
   float bmx = red[0]; int bi = best_i[0];
 #pragma unroll
   for (int w = 1; w < ARS_T / 64; ++w) if (red[w] > bmx || (red[w] == bmx && best_i[w] < bi)) { bmx = red[w]; bi = best_i[w]; }
+  float cmax = 0.f, total_all = 0.f;
+  if (LOGP) cmax = ar_cond_merge(cl, cmx_w, csum_w, lane, wave);
   if (greedy) {
     if (t == 0) chosen = bi;
+    if (LOGP) {
+      // the one block sum the greedy pick skips: the chunk sums of the draw below, an xor tree over the wave, the wave partials in order
+      const int C = (V + ARS_T - 1) / ARS_T;
+      const int lo = t * C, hi = min(V, lo + C);
+      float local = 0.f;
+      for (int e = lo; e < hi; ++e) local += expf(mix[ar_pad(e)] - bmx);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, 64);
+      if (lane == 0) wtot[wave] = local;
+    }
   } else {
     // inverse CDF in index order: thread t owns the contiguous chunk [t*C, (t+1)*C); exclusive prefix of the chunk sums by a
     // wave scan + the totals of the waves in front
@@ -222,10 +297,18 @@ __global__ __launch_bounds__(ARS_T) void ar_sample_kernel(float* __restrict__ ac
       for (int e = lo; e < hi; ++e) { run += expf(mix[ar_pad(e)] - bmx); if (run > target) { idx = e; break; } }
       chosen = min(idx, V - 1);
     }
+    if (LOGP) total_all = total;
   }
   __syncthreads();
   const int token = chosen;
   if (t == 0) { tok[b] = token; out_tokens[(int64_t)b * nsteps + step] = token; }
+  if (LOGP) {
+    if (greedy) {
+#pragma unroll
+      for (int w = 0; w < ARS_T / 64; ++w) total_all += wtot[w];
+    }
+    ar_write_logp(logp, b, nsteps, step, token, mix[ar_pad(token)], bmx, total_all, cvr, cmax, ar_cond_total(csum_w), t);
+  }
   const float4* er = reinterpret_cast<const float4*>(embed + (token + id_offset) * lde);
   float4* x0 = reinterpret_cast<float4*>(x + (int64_t)b * H);
   float4* x1 = reinterpret_cast<float4*>(x + (int64_t)(bsz + b) * H);
@@ -244,7 +327,6 @@ __device__ __forceinline__ uint32_t ar_key(float v) {
 }
 __device__ __forceinline__ float ar_unkey(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
-constexpr int AR_PER = AR_MAXV / ARS_T;
 struct ArProbe { float mass; uint32_t le, gt; };
 // Over the elements with key >= lo: mass = sum of ex over key >= bound; le = the largest key in [lo, bound) (lo if none); gt = the
 // smallest key in [bound, hi] (hi if none).  One barrier; consecutive calls alternate `par` (a wave can be one call ahead, not two).
@@ -274,13 +356,18 @@ __device__ __forceinline__ ArProbe ar_probe(const uint32_t (&key)[AR_PER], const
   return r;
 }
 
+template <bool LOGP>
 __global__ __launch_bounds__(ARS_T) void ar_sample_filtered_kernel(float* __restrict__ acc, int64_t lda, int bsz, int V, float scale,
                                                                   float inv_temp, const float* __restrict__ uniforms,
                                                                   const int* __restrict__ pos_dev, int pos0, int nsteps,
                                                                   const float* __restrict__ embed, int64_t lde, int H,
                                                                   int64_t id_offset, int top_k, float top_p, float log_min_p,
                                                                   int64_t* __restrict__ tok, int* __restrict__ out_tokens,
-                                                                  float* __restrict__ x, float* __restrict__ stats) {
+                                                                  float* __restrict__ x, float* __restrict__ stats,
+                                                                  float* __restrict__ logp) {
+  __shared__ float cmx_w[LOGP ? ARS_T / 64 : 1], csum_w[LOGP ? ARS_T / 64 : 1];
+  float cvr[AR_PER] = {};                                        // (LOGP: the conditional values this thread loaded)
+  ArCond cl{-INFINITY, 0.f};
   __shared__ float mix[AR_MAXV + AR_MAXV / 32];
   __shared__ float red[ARS_T / 64];
   __shared__ float wtot[ARS_T / 64];
@@ -313,8 +400,10 @@ __global__ __launch_bounds__(ARS_T) void ar_sample_filtered_kernel(float* __rest
         const float v = (uv + scale * (cv - uv)) * inv_temp;
         mix[ar_pad(e)] = v;
         mx = fmaxf(mx, v);
+        if (LOGP) cvr[j] = cv;
       }
     }
+    if (LOGP) cl = ar_cond_local(cvr, t, V);
   }
   wait_lgkm0();
   tie_s(pos_now);
@@ -323,12 +412,20 @@ __global__ __launch_bounds__(ARS_T) void ar_sample_filtered_kernel(float* __rest
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
   if (lane == 0) red[wave] = mx;
+  if (LOGP) {
+    float cm = cl.mx;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cm = fmaxf(cm, __shfl_xor(cm, o, 64));
+    if (lane == 0) cmx_w[wave] = cm;
+  }
   (&hist[0][0])[t] = 0;                                         // 4 x 256 digit counters, one per thread
   if (t == 0) { hit = ARS_T; last_el = -1; chosen = 0; }
   __syncthreads();
   float bmx = red[0];
 #pragma unroll
   for (int w = 1; w < ARS_T / 64; ++w) bmx = fmaxf(bmx, red[w]);
+  float cmax = 0.f;
+  if (LOGP) cmax = ar_cond_merge(cl, cmx_w, csum_w, lane, wave);          // (csum_w: published by the barriers below)
   // thread t owns the contiguous chunk [t*C, t*C + nv): keys and exp in registers from here on (slots past nv: key 0, mass 0)
   const int C = (V + ARS_T - 1) / ARS_T;
   const int e0 = t * C, nv = min(max(V - e0, 0), C);
@@ -441,10 +538,68 @@ __global__ __launch_bounds__(ARS_T) void ar_sample_filtered_kernel(float* __rest
   __syncthreads();
   const int token = chosen;
   if (t == 0) { tok[b] = token; out_tokens[(int64_t)b * nsteps + step] = token; }
+  // (total = the kept mass: the drawn token is a kept one, so this is its log-probability under the truncated distribution)
+  if (LOGP) ar_write_logp(logp, b, nsteps, step, token, mix[ar_pad(token)], bmx, total, cvr, cmax, ar_cond_total(csum_w), t);
   const float4* er = reinterpret_cast<const float4*>(embed + (token + id_offset) * lde);
   float4* x0 = reinterpret_cast<float4*>(x + (int64_t)b * H);
   float4* x1 = reinterpret_cast<float4*>(x + (int64_t)(bsz + b) * H);
   for (int i = t; i < (H >> 2); i += ARS_T) { const float4 v = er[i]; x0[i] = v; x1[i] = v; }
+}
+
+// argument checks + launch of ug_ar_sample / ug_ar_sample_logp (logp null: the kernel without the output)
+int ar_sample_launch(const char* who, float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature, int greedy,
+                     const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps, const float* embed, int64_t ld_embed,
+                     int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, float* logp, hipStream_t st) {
+  UG_REQUIRE(acc && pos_dev && embed && tok && out_tokens && x && (greedy || uniforms), "%s: null argument", who);
+  UG_REQUIRE(V <= AR_MAXV, "%s: code-book slice of %ld columns exceeds the %d this build stages in LDS", who, (long)V, AR_MAXV);
+  UG_REQUIRE(bsz > 0 && V > 0 && ldacc >= V && nsteps > 0 && H > 0 && H % 4 == 0 && ld_embed % 4 == 0 && temperature > 0.f &&
+                 ug_aligned16(embed) && ug_aligned16(x),
+             "%s: bad sizes (bsz=%ld V=%ld H=%ld temperature=%g)", who, (long)bsz, (long)V, (long)H, (double)temperature);
+  if (logp)
+    hipLaunchKernelGGL(ar_sample_kernel<true>, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V, guidance_scale,
+                       1.f / temperature, greedy, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, tok,
+                       out_tokens, x, logp);
+  else
+    hipLaunchKernelGGL(ar_sample_kernel<false>, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V, guidance_scale,
+                       1.f / temperature, greedy, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, tok,
+                       out_tokens, x, (float*)nullptr);
+  UG_CHECK_LAUNCH(who);
+  return UG_OK;
+}
+
+int ar_sample_filtered_launch(const char* who, float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature,
+                              int greedy, const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps, const float* embed,
+                              int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, int64_t top_k,
+                              float top_p, float min_p, float* stats, float* logp, hipStream_t st) {
+  UG_REQUIRE(acc && pos_dev && embed && tok && out_tokens && x && (greedy || uniforms), "%s: null argument", who);
+  UG_REQUIRE(V <= AR_MAXV, "%s: code-book slice of %ld columns exceeds the %d this build stages in LDS", who, (long)V, AR_MAXV);
+  UG_REQUIRE(bsz > 0 && V > 0 && ldacc >= V && nsteps > 0 && H > 0 && H % 4 == 0 && ld_embed % 4 == 0 && temperature > 0.f &&
+                 ug_aligned16(embed) && ug_aligned16(x),
+             "%s: bad sizes (bsz=%ld V=%ld H=%ld temperature=%g)", who, (long)bsz, (long)V, (long)H, (double)temperature);
+  UG_REQUIRE(top_k >= 0 && top_p > 0.f && top_p <= 1.f && min_p >= 0.f && min_p <= 1.f,
+             "%s: bad filter (top_k=%ld >= 0, 0 < top_p=%g <= 1, 0 <= min_p=%g <= 1)", who, (long)top_k, (double)top_p, (double)min_p);
+  const int k = top_k >= V ? 0 : (int)top_k;
+  const float lmp = min_p > 0.f ? logf(min_p) : -INFINITY;
+  if (greedy) {                                       // the argmax is always kept: the filters change nothing (stats stay unwritten)
+    if (logp)
+      hipLaunchKernelGGL(ar_sample_kernel<true>, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V, guidance_scale,
+                         1.f / temperature, 1, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, tok,
+                         out_tokens, x, logp);
+    else
+      hipLaunchKernelGGL(ar_sample_kernel<false>, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V, guidance_scale,
+                         1.f / temperature, 1, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, tok,
+                         out_tokens, x, (float*)nullptr);
+  } else if (logp) {
+    hipLaunchKernelGGL(ar_sample_filtered_kernel<true>, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V,
+                       guidance_scale, 1.f / temperature, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, k,
+                       top_p, lmp, tok, out_tokens, x, stats, logp);
+  } else {
+    hipLaunchKernelGGL(ar_sample_filtered_kernel<false>, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V,
+                       guidance_scale, 1.f / temperature, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, k,
+                       top_p, lmp, tok, out_tokens, x, stats, (float*)nullptr);
+  }
+  UG_CHECK_LAUNCH(who);
+  return UG_OK;
 }
 
 }  // namespace
@@ -469,40 +624,33 @@ extern "C" int ug_maskgit_step(const void* logits, int64_t ld, int64_t V, int64_
 extern "C" int ug_ar_sample(float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature, int greedy,
                             const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps, const float* embed,
                             int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, hipStream_t st) {
-  UG_REQUIRE(acc && pos_dev && embed && tok && out_tokens && x && (greedy || uniforms), "ug_ar_sample: null argument");
-  UG_REQUIRE(V <= AR_MAXV, "ug_ar_sample: code-book slice of %ld columns exceeds the %d this build stages in LDS", (long)V, AR_MAXV);
-  UG_REQUIRE(bsz > 0 && V > 0 && ldacc >= V && nsteps > 0 && H > 0 && H % 4 == 0 && ld_embed % 4 == 0 && temperature > 0.f &&
-                 ug_aligned16(embed) && ug_aligned16(x),
-             "ug_ar_sample: bad sizes (bsz=%ld V=%ld H=%ld temperature=%g)", (long)bsz, (long)V, (long)H, (double)temperature);
-  hipLaunchKernelGGL(ar_sample_kernel, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V, guidance_scale,
-                     1.f / temperature, greedy, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, tok,
-                     out_tokens, x);
-  UG_CHECK_LAUNCH("ug_ar_sample");
-  return UG_OK;
+  return ar_sample_launch("ug_ar_sample", acc, ldacc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_dev, pos0, nsteps, embed,
+                          ld_embed, H, id_offset, tok, out_tokens, x, nullptr, st);
+}
+
+extern "C" int ug_ar_sample_logp(float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature, int greedy,
+                                 const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps, const float* embed,
+                                 int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens, float* x, float* logp,
+                                 hipStream_t st) {
+  UG_REQUIRE(logp, "ug_ar_sample_logp: null logp (ug_ar_sample is the entry point without the output)");
+  return ar_sample_launch("ug_ar_sample_logp", acc, ldacc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_dev, pos0, nsteps,
+                          embed, ld_embed, H, id_offset, tok, out_tokens, x, logp, st);
 }
 
 extern "C" int ug_ar_sample_filtered(float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature,
                                      int greedy, const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps,
                                      const float* embed, int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok, int* out_tokens,
                                      float* x, int64_t top_k, float top_p, float min_p, float* stats, hipStream_t st) {
-  UG_REQUIRE(acc && pos_dev && embed && tok && out_tokens && x && (greedy || uniforms), "ug_ar_sample_filtered: null argument");
-  UG_REQUIRE(V <= AR_MAXV, "ug_ar_sample_filtered: code-book slice of %ld columns exceeds the %d this build stages in LDS", (long)V,
-             AR_MAXV);
-  UG_REQUIRE(bsz > 0 && V > 0 && ldacc >= V && nsteps > 0 && H > 0 && H % 4 == 0 && ld_embed % 4 == 0 && temperature > 0.f &&
-                 ug_aligned16(embed) && ug_aligned16(x),
-             "ug_ar_sample_filtered: bad sizes (bsz=%ld V=%ld H=%ld temperature=%g)", (long)bsz, (long)V, (long)H, (double)temperature);
-  UG_REQUIRE(top_k >= 0 && top_p > 0.f && top_p <= 1.f && min_p >= 0.f && min_p <= 1.f,
-             "ug_ar_sample_filtered: bad filter (top_k=%ld >= 0, 0 < top_p=%g <= 1, 0 <= min_p=%g <= 1)", (long)top_k, (double)top_p,
-             (double)min_p);
-  if (greedy) {                                       // the argmax is always kept: the filters change nothing (stats stay unwritten)
-    hipLaunchKernelGGL(ar_sample_kernel, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V, guidance_scale,
-                       1.f / temperature, 1, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset, tok,
-                       out_tokens, x);
-  } else {
-    hipLaunchKernelGGL(ar_sample_filtered_kernel, dim3((unsigned)bsz), dim3(ARS_T), 0, st, acc, ldacc, (int)bsz, (int)V, guidance_scale,
-                       1.f / temperature, uniforms, pos_dev, (int)pos0, (int)nsteps, embed, ld_embed, (int)H, id_offset,
-                       top_k >= V ? 0 : (int)top_k, top_p, min_p > 0.f ? logf(min_p) : -INFINITY, tok, out_tokens, x, stats);
-  }
-  UG_CHECK_LAUNCH("ug_ar_sample_filtered");
-  return UG_OK;
+  return ar_sample_filtered_launch("ug_ar_sample_filtered", acc, ldacc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_dev, pos0,
+                                   nsteps, embed, ld_embed, H, id_offset, tok, out_tokens, x, top_k, top_p, min_p, stats, nullptr, st);
+}
+
+extern "C" int ug_ar_sample_filtered_logp(float* acc, int64_t ldacc, int64_t bsz, int64_t V, float guidance_scale, float temperature,
+                                          int greedy, const float* uniforms, const int* pos_dev, int64_t pos0, int64_t nsteps,
+                                          const float* embed, int64_t ld_embed, int64_t H, int64_t id_offset, int64_t* tok,
+                                          int* out_tokens, float* x, int64_t top_k, float top_p, float min_p, float* stats, float* logp,
+                                          hipStream_t st) {
+  UG_REQUIRE(logp, "ug_ar_sample_filtered_logp: null logp (ug_ar_sample_filtered is the entry point without the output)");
+  return ar_sample_filtered_launch("ug_ar_sample_filtered_logp", acc, ldacc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_dev,
+                                   pos0, nsteps, embed, ld_embed, H, id_offset, tok, out_tokens, x, top_k, top_p, min_p, stats, logp, st);
 }

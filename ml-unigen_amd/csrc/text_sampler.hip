@@ -40,6 +40,7 @@ struct TextOut {
   int* out_tokens;
   int* lengths;
   float* x;
+  float* logp;                         // [R][nsteps] log-probability of every emitted token (the _logp entry points; else null)
 };
 
 // bf16 pattern -> 16-bit key whose unsigned order is the order of the values (-0 and +0 share a key)
@@ -55,8 +56,10 @@ __device__ __forceinline__ float txt_unkey(uint32_t k) { return bf2f((bf16_t)(k 
 __device__ __forceinline__ float txt_val(uint32_t key, float inv_temp) { return __fmul_rn(txt_unkey(key), inv_temp); }
 
 // The end of a step for row r (every thread of the row's workgroup calls it; `picked` is uniform): pad rule, records, stop rule, next
-// input, then the arrival ticket.  s_token: one int of LDS.
-__device__ __forceinline__ void txt_finish_row(const TextOut& o, int r, int picked, int step, int* s_token) {
+// input, then the arrival ticket.  s_token: one int of LDS.  LOGP: lp = the log-probability of `picked` under the step's distribution;
+// a row that had finished before the step records 0.
+template <bool LOGP>
+__device__ __forceinline__ void txt_finish_row(const TextOut& o, int r, int picked, int step, int* s_token, float lp = 0.f) {
   const int t = threadIdx.x;
   if (t == 0) {
     int* done = o.state + 4;
@@ -64,6 +67,7 @@ __device__ __forceinline__ void txt_finish_row(const TextOut& o, int r, int pick
     const int64_t token = (was && o.pad_id >= 0) ? o.pad_id : (int64_t)picked;
     o.tok[r] = token;
     if (step < o.nsteps) o.out_tokens[(int64_t)r * o.nsteps + step] = (int)token;
+    if (LOGP && step < o.nsteps) o.logp[(int64_t)r * o.nsteps + step] = was ? 0.f : lp;
     bool stop = false;
     for (int i = 0; i < o.n_stop; ++i) stop |= o.stop_ids[i] == token;
     if (stop && !was) {
@@ -92,11 +96,17 @@ __device__ __forceinline__ int txt_read_step(const int* state, int* s_step) {
 
 // ------------------------------------------------------------------ greedy: argmax of the bf16-rounded logits, lowest index on ties
 // VEC: rows that start on 16-byte boundaries (ld % 4 == 0) are read four entries at a time
-template <bool VEC>
+// LOGP: the log-softmax of the bf16 values at the picked token, formed in the same single pass (the row is cleared on the way): thread t
+// keeps sum = the sum of exp(value - mx) over the candidates it has seen, rescaled whenever its running maximum mx moves; -inf adds 0, a
+// NaN is no candidate.  Behind the block maximum: every thread's sum rescaled to it, an xor tree over the wave, the sixteen wave partials
+// in wave order -- a fixed order.  The picked token holds the maximum, so its log-probability is -log(total).
+template <bool VEC, bool LOGP>
 __global__ __launch_bounds__(TXT_T) void text_pick_kernel(float* __restrict__ logits, int64_t ld, int V, int clear, TextOut o) {
   __shared__ float red[TXT_W];
   __shared__ int best_i[TXT_W];
   __shared__ int s_step, s_token;
+  __shared__ float sum_w[LOGP ? TXT_W : 1];
+  float sum = 0.f;
   const int r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int step = txt_read_step(o.state, &s_step);
   float* row = logits + (int64_t)r * ld;
@@ -112,7 +122,12 @@ __global__ __launch_bounds__(TXT_T) void text_pick_kernel(float* __restrict__ lo
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float v = bf2f(f2bf(vv[j]));
-        if (e0 + j < V && v > mx) { mx = v; arg = e0 + j; }      // (entries V .. ld-1 are read, never candidates)
+        if (LOGP) {
+          if (e0 + j < V) {
+            if (v > mx) { sum = __fmaf_rn(sum, expf(mx - v), 1.f); mx = v; arg = e0 + j; }
+            else if (v > -INFINITY) sum += expf(v - mx);
+          }
+        } else if (e0 + j < V && v > mx) { mx = v; arg = e0 + j; }      // (entries V .. ld-1 are read, never candidates)
       }
       if (clear) {
         if (e0 + 3 < V) row4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -124,10 +139,12 @@ __global__ __launch_bounds__(TXT_T) void text_pick_kernel(float* __restrict__ lo
 #pragma unroll 8
     for (int e = t; e < V; e += TXT_T) {
       const float v = bf2f(f2bf(row[e]));
-      if (v > mx) { mx = v; arg = e; }
+      if (v > mx) { if (LOGP) sum = __fmaf_rn(sum, expf(mx - v), 1.f); mx = v; arg = e; }
+      else if (LOGP && v > -INFINITY) sum += expf(v - mx);
       if (clear) row[e] = 0.f;
     }
   }
+  const float mx_t = mx;                                          // (LOGP: this thread's own maximum, before the wave's replaces it)
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const float om = __shfl_xor(mx, off, 64);
@@ -142,7 +159,19 @@ __global__ __launch_bounds__(TXT_T) void text_pick_kernel(float* __restrict__ lo
   for (int w = 1; w < TXT_W; ++w)
     if (red[w] > bmx || (red[w] == bmx && best_i[w] < bi)) { bmx = red[w]; bi = best_i[w]; }
   if (bi >= V) bi = 0;                                            // (no finite candidate: torch.argmax answers 0 for a row of -inf)
-  txt_finish_row(o, r, bi, step, &s_token);
+  float lp = 0.f;
+  if (LOGP) {
+    float part = sum > 0.f ? __fmul_rn(sum, expf(mx_t - bmx)) : 0.f;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+    if (lane == 0) sum_w[wave] = part;
+    __syncthreads();
+    float total = 0.f;
+#pragma unroll
+    for (int w = 0; w < TXT_W; ++w) total += sum_w[w];
+    lp = -logf(total);
+  }
+  txt_finish_row<LOGP>(o, r, bi, step, &s_token, lp);
 }
 
 // ------------------------------------------------------------------ sampled pick, launch A: per-row histogram of the 16-bit keys
@@ -195,6 +224,9 @@ __device__ __forceinline__ T txt_scan_excl(T v, T* wt, T& total) {
 // ------------------------------------------------------------------ launch B: the whole selection of one row on its histogram
 // Positions p = 0 .. 65535 run over the keys in DESCENDING order (key = 65535 - p); thread t holds p in [64 t, 64 t + 64).
 // meta (int32): rowmax [32] | sel_key [32] | sel_rank [32].
+// LOGP: the drawn token's log-probability (v of the drawn key - max v - log T, T the kept mass formed below) travels to the locate launch
+// as the bits of rowmax[r], which that launch zeroes again.
+template <bool LOGP>
 __global__ __launch_bounds__(TXT_T) void text_select_kernel(int* __restrict__ hist, int* __restrict__ meta, int V, float inv_temp, int top_k,
                                                            float top_p, const float* __restrict__ uniforms, const int* __restrict__ state,
                                                            int nsteps, int R, float* __restrict__ stats) {
@@ -307,7 +339,7 @@ __global__ __launch_bounds__(TXT_T) void text_select_kernel(int* __restrict__ hi
     meta[64 + r] = j;
   }
   if (t == 0) {
-    meta[r] = 0;
+    meta[r] = LOGP ? __float_as_int((txt_val((uint32_t)(TXT_BINS - 1 - hit), inv_temp) - vmax) - logf(s_T)) : 0;
     if (stats) {
       stats[2 * r] = txt_val((uint32_t)(TXT_BINS - 1 - pc), inv_temp);
       stats[2 * r + 1] = (float)s_kept;
@@ -317,6 +349,7 @@ __global__ __launch_bounds__(TXT_T) void text_select_kernel(int* __restrict__ hi
 
 // ------------------------------------------------------------------ launch C: the rank-th index holding the selected key, in index order
 // Wave w owns the contiguous entries [w CW, (w + 1) CW), CW a multiple of 64; iteration i covers 64 consecutive entries.
+template <bool LOGP>
 __global__ __launch_bounds__(TXT_T) void text_locate_kernel(float* __restrict__ logits, int64_t ld, int V, int clear, int* __restrict__ meta,
                                                            TextOut o) {
   __shared__ unsigned long long masks[TXT_MAXV / 64];
@@ -325,6 +358,7 @@ __global__ __launch_bounds__(TXT_T) void text_locate_kernel(float* __restrict__ 
   const int r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int step = txt_read_step(o.state, &s_step);
   const int key = meta[32 + r], rank = meta[64 + r];
+  const float lp = LOGP ? __int_as_float(meta[r]) : 0.f;           // (read by every thread ahead of the barriers; zeroed behind them)
   float* row = logits + (int64_t)r * ld;
   const int iters = (V + 64 * TXT_W - 1) / (64 * TXT_W);           // per wave
   const int w0 = wave * iters * 64;
@@ -377,8 +411,8 @@ __global__ __launch_bounds__(TXT_T) void text_locate_kernel(float* __restrict__ 
   __syncthreads();
   int pick = s_pick;
   if (pick < 0 || pick >= V) pick = 0;
-  if (t == 0) { meta[32 + r] = 0; meta[64 + r] = 0; }
-  txt_finish_row(o, r, pick, step, &s_token);
+  if (t == 0) { meta[32 + r] = 0; meta[64 + r] = 0; if (LOGP) meta[r] = 0; }
+  txt_finish_row<LOGP>(o, r, pick, step, &s_token, lp);
 }
 
 // ------------------------------------------------------------------ repetition penalty: the logits processor in front of the pick
@@ -444,12 +478,28 @@ extern "C" int ug_text_pick(float* logits, int64_t ld, int64_t R, int64_t V, int
   const int rc = txt_check_out("ug_text_pick", logits, ld, R, V, stop_ids, n_stop, pad_id, embed, ld_embed, embed_rows, H, state, nsteps, tok,
                                out_tokens, x);
   if (rc != UG_OK) return rc;
-  const TextOut o{stop_ids, (int)n_stop, pad_id, embed, ld_embed, (int)H, state, (int)nsteps, (int)R, tok, out_tokens, lengths, x};
+  const TextOut o{stop_ids, (int)n_stop, pad_id, embed, ld_embed, (int)H, state, (int)nsteps, (int)R, tok, out_tokens, lengths, x, nullptr};
   if (ld % 4 == 0 && ug_aligned16(logits))
-    hipLaunchKernelGGL(text_pick_kernel<true>, dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, o);
+    hipLaunchKernelGGL((text_pick_kernel<true, false>), dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, o);
   else
-    hipLaunchKernelGGL(text_pick_kernel<false>, dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, o);
+    hipLaunchKernelGGL((text_pick_kernel<false, false>), dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, o);
   UG_CHECK_LAUNCH("ug_text_pick");
+  return UG_OK;
+}
+
+extern "C" int ug_text_pick_logp(float* logits, int64_t ld, int64_t R, int64_t V, int clear, const int64_t* stop_ids, int64_t n_stop,
+                                 int64_t pad_id, const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state,
+                                 int64_t nsteps, int64_t* tok, int* out_tokens, int* lengths, float* x, float* logp, hipStream_t st) {
+  UG_REQUIRE(logp, "ug_text_pick_logp: null logp (ug_text_pick is the entry point without the output)");
+  const int rc = txt_check_out("ug_text_pick_logp", logits, ld, R, V, stop_ids, n_stop, pad_id, embed, ld_embed, embed_rows, H, state, nsteps,
+                               tok, out_tokens, x);
+  if (rc != UG_OK) return rc;
+  const TextOut o{stop_ids, (int)n_stop, pad_id, embed, ld_embed, (int)H, state, (int)nsteps, (int)R, tok, out_tokens, lengths, x, logp};
+  if (ld % 4 == 0 && ug_aligned16(logits))
+    hipLaunchKernelGGL((text_pick_kernel<true, true>), dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, o);
+  else
+    hipLaunchKernelGGL((text_pick_kernel<false, true>), dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, o);
+  UG_CHECK_LAUNCH("ug_text_pick_logp");
   return UG_OK;
 }
 
@@ -461,29 +511,55 @@ extern "C" int ug_text_sample_workspace_ints(int64_t R) {
   return (int)(R * TXT_BINS + 96);
 }
 
+namespace {
+// argument checks + the three launches of ug_text_sample / ug_text_sample_logp (logp null: the kernels without the output)
+int txt_sample_launch(const char* who, float* logits, int64_t ld, int64_t R, int64_t V, int clear, float temperature, int64_t top_k, float top_p,
+                      const float* uniforms, int* workspace, float* stats, const int64_t* stop_ids, int64_t n_stop, int64_t pad_id,
+                      const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
+                      int* out_tokens, int* lengths, float* x, float* logp, hipStream_t st) {
+  const int rc = txt_check_out(who, logits, ld, R, V, stop_ids, n_stop, pad_id, embed, ld_embed, embed_rows, H, state, nsteps, tok, out_tokens, x);
+  if (rc != UG_OK) return rc;
+  UG_REQUIRE(uniforms && workspace && ug_aligned16(workspace), "%s: null or misaligned uniforms / workspace", who);
+  UG_REQUIRE(V <= TXT_MAXV, "%s: V=%ld exceeds the %d entries this build locates a token among", who, (long)V, TXT_MAXV);
+  UG_REQUIRE(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f,
+             "%s: bad filter (temperature=%g > 0, top_k=%ld >= 0, 0 < top_p=%g <= 1)", who, (double)temperature, (long)top_k, (double)top_p);
+  const TextOut o{stop_ids, (int)n_stop, pad_id, embed, ld_embed, (int)H, state, (int)nsteps, (int)R, tok, out_tokens, lengths, x, logp};
+  int* meta = workspace + R * TXT_BINS;
+  const int k = top_k >= V ? 0 : (int)top_k;
+  hipLaunchKernelGGL(text_hist_kernel, dim3((unsigned)((V + TXT_SEG - 1) / TXT_SEG), (unsigned)R), dim3(TXT_HT), 0, st, logits, ld, (int)V,
+                     workspace, meta);
+  UG_CHECK_LAUNCH(who);
+  if (logp)
+    hipLaunchKernelGGL(text_select_kernel<true>, dim3((unsigned)R), dim3(TXT_T), 0, st, workspace, meta, (int)V, 1.f / temperature, k, top_p,
+                       uniforms, state, (int)nsteps, (int)R, stats);
+  else
+    hipLaunchKernelGGL(text_select_kernel<false>, dim3((unsigned)R), dim3(TXT_T), 0, st, workspace, meta, (int)V, 1.f / temperature, k, top_p,
+                       uniforms, state, (int)nsteps, (int)R, stats);
+  UG_CHECK_LAUNCH(who);
+  if (logp)
+    hipLaunchKernelGGL(text_locate_kernel<true>, dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, meta, o);
+  else
+    hipLaunchKernelGGL(text_locate_kernel<false>, dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, meta, o);
+  UG_CHECK_LAUNCH(who);
+  return UG_OK;
+}
+}  // namespace
+
 extern "C" int ug_text_sample(float* logits, int64_t ld, int64_t R, int64_t V, int clear, float temperature, int64_t top_k, float top_p,
                               const float* uniforms, int* workspace, float* stats, const int64_t* stop_ids, int64_t n_stop,
                               int64_t pad_id, const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state,
                               int64_t nsteps, int64_t* tok, int* out_tokens, int* lengths, float* x, hipStream_t st) {
-  const int rc = txt_check_out("ug_text_sample", logits, ld, R, V, stop_ids, n_stop, pad_id, embed, ld_embed, embed_rows, H, state, nsteps,
-                               tok, out_tokens, x);
-  if (rc != UG_OK) return rc;
-  UG_REQUIRE(uniforms && workspace && ug_aligned16(workspace), "ug_text_sample: null or misaligned uniforms / workspace");
-  UG_REQUIRE(V <= TXT_MAXV, "ug_text_sample: V=%ld exceeds the %d entries this build locates a token among", (long)V, TXT_MAXV);
-  UG_REQUIRE(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f,
-             "ug_text_sample: bad filter (temperature=%g > 0, top_k=%ld >= 0, 0 < top_p=%g <= 1)", (double)temperature, (long)top_k,
-             (double)top_p);
-  const TextOut o{stop_ids, (int)n_stop, pad_id, embed, ld_embed, (int)H, state, (int)nsteps, (int)R, tok, out_tokens, lengths, x};
-  int* meta = workspace + R * TXT_BINS;
-  hipLaunchKernelGGL(text_hist_kernel, dim3((unsigned)((V + TXT_SEG - 1) / TXT_SEG), (unsigned)R), dim3(TXT_HT), 0, st, logits, ld, (int)V,
-                     workspace, meta);
-  UG_CHECK_LAUNCH("ug_text_sample(histogram)");
-  hipLaunchKernelGGL(text_select_kernel, dim3((unsigned)R), dim3(TXT_T), 0, st, workspace, meta, (int)V, 1.f / temperature,
-                     top_k >= V ? 0 : (int)top_k, top_p, uniforms, state, (int)nsteps, (int)R, stats);
-  UG_CHECK_LAUNCH("ug_text_sample(select)");
-  hipLaunchKernelGGL(text_locate_kernel, dim3((unsigned)R), dim3(TXT_T), 0, st, logits, ld, (int)V, clear, meta, o);
-  UG_CHECK_LAUNCH("ug_text_sample(locate)");
-  return UG_OK;
+  return txt_sample_launch("ug_text_sample", logits, ld, R, V, clear, temperature, top_k, top_p, uniforms, workspace, stats, stop_ids, n_stop,
+                           pad_id, embed, ld_embed, embed_rows, H, state, nsteps, tok, out_tokens, lengths, x, nullptr, st);
+}
+
+extern "C" int ug_text_sample_logp(float* logits, int64_t ld, int64_t R, int64_t V, int clear, float temperature, int64_t top_k, float top_p,
+                                   const float* uniforms, int* workspace, float* stats, const int64_t* stop_ids, int64_t n_stop,
+                                   int64_t pad_id, const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state,
+                                   int64_t nsteps, int64_t* tok, int* out_tokens, int* lengths, float* x, float* logp, hipStream_t st) {
+  UG_REQUIRE(logp, "ug_text_sample_logp: null logp (ug_text_sample is the entry point without the output)");
+  return txt_sample_launch("ug_text_sample_logp", logits, ld, R, V, clear, temperature, top_k, top_p, uniforms, workspace, stats, stop_ids,
+                           n_stop, pad_id, embed, ld_embed, embed_rows, H, state, nsteps, tok, out_tokens, lengths, x, logp, st);
 }
 
 extern "C" int ug_text_seen_mark(int* seen, int64_t ld_words, const int64_t* ids, int64_t ld_ids, int64_t R, int64_t L, const uint8_t* valid,

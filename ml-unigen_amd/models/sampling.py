@@ -158,3 +158,19 @@ def seen_mask_of(ids, valid, rows, vocab, device):
             ok &= valid.to(device) != 0
         seen.scatter_(1, torch.where(ok, ids, torch.full_like(ids, vocab)), True)
     return seen[:, :vocab]
+
+
+def token_logprobs(scores, tokens, done=None):
+    """The log-probability of every row's picked token under the distribution it was picked from: the log-softmax of the PROCESSED
+    scores [R, V] (after the repetition penalty, the temperature and top-k / top-p / min-p written as -inf -- whatever the pick saw) at
+    tokens [R] or [R, 1], in fp32: s[tok] - max s - log(sum of exp(s - max s)).  This is transformers' compute_transition_scores(...,
+    normalize_logits=True) for one step.  -inf entries add 0 and a NaN entry adds nothing (it is no candidate).  done (bool [R], optional):
+    rows that had finished BEFORE the step get exactly 0.0.  The host text loops and the unfused branch of t2i_generate_ar use it; the
+    sampler kernels compute the same formula on the device (include/unigen_hip.h: ug_text_pick_logp, ug_ar_sample_logp).  -> fp32 [R]."""
+    s = scores.float()
+    s = torch.where(torch.isnan(s), torch.full_like(s, float("-inf")), s)
+    d = s - s.max(-1, keepdim=True).values
+    lp = (d.gather(-1, tokens.reshape(-1, 1).long().to(s.device)) - torch.log(torch.exp(d).sum(-1, keepdim=True)))[:, 0]
+    if done is not None:
+        lp = torch.where(done.to(lp.device), torch.zeros_like(lp), lp)
+    return lp

@@ -100,6 +100,7 @@ def emit_until_stop(out, stop, pad_token_id=None, lengths=None):
             lengths.masked_fill_(hit, i + 1)
         done.logical_or_(hit)
         return nxt, bool(done.all())
+    emit.done = done                               # (with_logprobs reads which rows had finished before a step)
     return emit
 
 
@@ -111,6 +112,26 @@ def checked_repetition_penalty(p, who):
     if not (math.isfinite(p) and p > 0.0):
         raise UniGenHipError(f"{who}: repetition_penalty={p} must be finite and > 0 (1 is off)")
     return p
+
+
+def with_logprobs(process, choose, emit, logp):
+    """`pick` and `emit` of text_token_loop that also record every emitted token's log-probability into logp fp32 [R, new]
+    (models/sampling.py: token_logprobs): pick = choose(process(last)), where `process` turns the scores it is handed (behind the
+    repetition penalty, if any) into the ones `choose` picks from (temperature, top-k / top-p as -inf).  `emit` is emit_until_stop's: a
+    row that had finished before the step records 0.0.  Wrap the result in with_repetition_penalty, not the other way round."""
+    from .sampling import token_logprobs
+    last_lp = [None]
+
+    def pick(last):
+        scores = process(last)
+        nxt = choose(scores)
+        last_lp[0] = token_logprobs(scores, nxt)
+        return nxt
+
+    def emit_and_record(i, nxt):
+        logp[:, i] = torch.where(emit.done, torch.zeros_like(last_lp[0]), last_lp[0])          # (done BEFORE this step)
+        return emit(i, nxt)
+    return pick, emit_and_record
 
 
 def with_repetition_penalty(pick, emit, penalty, seen):
@@ -648,6 +669,7 @@ class UniGen(ModelMixin, ConfigMixin):
             top_k: Optional[int] = 0,
             top_p: Optional[float] = 1.0,
             min_p: Optional[float] = 0.0,
+            return_logprobs: bool = False,
             **kwargs,
     ):
         """Token-by-token image generation with CFG (reference models/unigen.py:457-521).  The reference
@@ -659,9 +681,17 @@ class UniGen(ModelMixin, ConfigMixin):
         off).  Each is a value threshold (models/sampling.py: truncate_logits; in the captured step the fused sampler kernel finds
         it on the device): values tied at the top-k threshold are all kept, and top-p keeps or drops a run of equal logits as a
         whole, where a sorted cut would split it by the sort's order of equal keys.  `greedy` ignores them (the argmax is always
-        kept)."""
+        kept).
+        return_logprobs: returns (tokens [bsz, n], logprobs [bsz, n], cond_logprobs [bsz, n]), the last two fp32 on the device
+        (include/unigen_hip.h: ug_ar_sample_logp).  logprobs[b, i] is the natural-log probability of token i under the distribution it
+        was drawn from -- after CFG, temperature and truncation (greedy: the untruncated softmax at the call's temperature);
+        cond_logprobs[b, i] is the conditional model's own log-softmax at that token, what a teacher-forced pass would score.  The
+        captured step's sampler launch writes both (no extra pass over the logits, no host work per token); the unfused branch uses
+        models/sampling.py: token_logprobs.  The flag is part of the kept session: a call with it never replays the graph of a call
+        without it, nor the reverse."""
         from unigen_hip.qwen2 import DecodeState, resolve_deterministic
-        from .sampling import truncate_logits
+        from .sampling import token_logprobs, truncate_logits
+        want_lp = bool(return_logprobs)
         top_k = 0 if top_k is None else top_k
         top_p = 1.0 if top_p is None else float(top_p)
         min_p = 0.0 if min_p is None else float(min_p)
@@ -708,6 +738,8 @@ class UniGen(ModelMixin, ConfigMixin):
                     # RoPE tables stand in for "nothing was reallocated in between")
                     eng.fp.w(f"l{eng.dims.num_hidden_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(P + n)),
                     filt)                                    # (the filter constants are kernel arguments of the captured sampler)
+        if want_lp:
+            sess_key += ("logprobs",)                        # (another sampler entry point and one more buffer in the captured step)
         sess = getattr(eng, "_ar_session", None) if (use_graph and fused and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0") else None
         if sess is not None and sess["key"] != sess_key:
             sess = None
@@ -721,6 +753,8 @@ class UniGen(ModelMixin, ConfigMixin):
             out_tokens = torch.zeros((bsz, n), dtype=torch.int, device=dev)
             x = torch.empty((R, eng.dims.hidden_size), dtype=torch.float32, device=dev)      # static: next token's embedding
             tok = torch.zeros((bsz, 1), dtype=torch.long, device=dev)                        # static: last sampled token
+        # static: (logprobs, cond_logprobs) of every token, written by the sampler launch (fused) or copied from lp_now per step
+        logp = (sess["logp"] if sess is not None else torch.zeros((bsz, n, 2), dtype=torch.float32, device=dev)) if want_lp else None
         if fused:
             # lm-head as a weight-streaming GEMV into a raw fp32 accumulator + ONE sampling kernel per step (CFG mix,
             # temperature, softmax, inverse-CDF draw on uniforms taken from `generator` up front, next input embedding)
@@ -743,10 +777,10 @@ class UniGen(ModelMixin, ConfigMixin):
             def draw():                            # the step's one sampling launch
                 if filt is None:
                     ops.ar_sample_(acc_head, bsz, V, guidance_scale, temperature, greedy, uniforms, st.pos, P, n, w_embed,
-                                   text_vocab_size, tok, out_tokens, x)
+                                   text_vocab_size, tok, out_tokens, x, logp=logp)
                 else:
                     ops.ar_sample_filtered_(acc_head, bsz, V, guidance_scale, temperature, greedy, uniforms, st.pos, P, n, w_embed,
-                                            text_vocab_size, tok, out_tokens, x, top_k=filt[0], top_p=filt[1], min_p=filt[2])
+                                            text_vocab_size, tok, out_tokens, x, top_k=filt[0], top_p=filt[1], min_p=filt[2], logp=logp)
 
             def sample(hn):
                 if det:
@@ -756,18 +790,27 @@ class UniGen(ModelMixin, ConfigMixin):
                 keep_logits()
                 draw()
         else:
+            lp_now = torch.zeros((bsz, 2), dtype=torch.float32, device=dev) if want_lp else None     # static: the step's pair
+
             def sample(hn):
                 # (gen path: the reference mixes the bf16 img_head outputs in bf16 under autocast, :498-500)
                 lg = self._img_head(hn) if gen else eng.head_slice(hn, code_lo, code_hi).float()
                 cond, uncond = lg[:bsz], lg[bsz:]
                 lg = (uncond + guidance_scale * (cond - uncond)).float()
+                if logit_trace is not None and want_lp and not torch.cuda.is_current_stream_capturing():
+                    logit_trace.append(torch.cat([cond, uncond]).float())
                 if greedy:
                     nxt = lg.argmax(-1, keepdim=True)
+                    if want_lp:
+                        lg = lg / temperature              # (the greedy log-probability is taken at the call's temperature)
                 else:
                     lg = lg / temperature
                     if filt is not None:
                         lg = truncate_logits(lg, top_k=filt[0], top_p=filt[1], min_p=filt[2])
                     nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1, generator=generator)
+                if want_lp:
+                    lp_now[:, 0].copy_(token_logprobs(lg, nxt))
+                    lp_now[:, 1].copy_(token_logprobs(cond, nxt))
                 tok.copy_(nxt)
                 if gen:
                     x.copy_(self.get_gen_embed(torch.cat([nxt, nxt]))[:, 0])
@@ -789,6 +832,8 @@ class UniGen(ModelMixin, ConfigMixin):
         mark("prefill")
         if not fused:
             out_tokens[:, 0] = tok[:, 0]
+            if want_lp:
+                logp[:, 0] = lp_now
 
         # single-writer layer (csrc/decode_sw.hip): the final RMSNorm and the head slice are ONE launch behind the last layer
         sw_head = fused and form in ("sw", "ord_sw")
@@ -819,20 +864,27 @@ class UniGen(ModelMixin, ConfigMixin):
                 step()
             if not fused:
                 out_tokens[:, i] = tok[:, 0]
+                if want_lp:
+                    logp[:, i] = lp_now
         mark("replay")
         eng.last_decode_graph = graph is not None
         eng.last_decode_deterministic = det
         if graph is not None and fused and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0":
             eng._ar_session = {"key": sess_key, "st": st, "out_tokens": out_tokens, "x": x, "tok": tok, "acc_head": acc_head,
                                "uniforms": uniforms, "graph": graph}
+            if want_lp:
+                eng._ar_session["logp"] = logp
+                return out_tokens.clone(), logp[..., 0].clone(), logp[..., 1].clone()
             return out_tokens.clone()                # (the session's buffer is overwritten by the next call)
+        if want_lp:
+            return out_tokens, logp[..., 0].clone(), logp[..., 1].clone()
         return out_tokens
 
     # ------------------------------------------------------------------ plain causal generation
     @torch.no_grad()
     def generate(self, input_ids=None, input_embeddings=None, attention_mask=None, max_new_tokens=20, do_sample=False,
                  temperature=1.0, top_k=None, top_p=None, eos_token_id=None, pad_token_id=None, use_cache=True,
-                 generator=None, deterministic=None, on_device=None, **kwargs):
+                 generator=None, deterministic=None, on_device=None, return_logprobs=False, **kwargs):
         """Causal text generation with the conventions of transformers' `generate`, which the reference delegates to
         (models/unigen.py:584-588; caller evaluation/inference_unigen_cot.py:360): prompts as ids [B, L] or as
         `input_embeddings` [B, L, H] with an optional 2-D [B, L] key-validity mask (left padding); greedy when
@@ -860,6 +912,13 @@ class UniGen(ModelMixin, ConfigMixin):
         num_return_sequences=n: every prompt row, with its mask row, is repeated n times consecutively before the prefill
         (transformers' order); the result has B * n rows.  n > 1 needs do_sample.  On the device the B * n rows draw independent
         uniforms from the one torch.rand((max_new_tokens, B * n)); the 32-row limit applies to B * n.
+        return_logprobs: returns (sequences, logprobs fp32 [B * n, new]) -- transformers' compute_transition_scores(...,
+        normalize_logits=True): the natural-log softmax of the PROCESSED scores (behind the repetition penalty, and when sampling the
+        temperature and top-k / top-p) at every emitted token, aligned with the continuation columns and cut at the same step; a row
+        that had finished before a step has 0.0 there (its pad ids), the step that emits the stop id its real value.  Greedy applies
+        no temperature.  The host loop computes it in fp32 on the scores it picks from (models/sampling.py: token_logprobs), the
+        on-device loop in its pick launches (include/unigen_hip.h: ug_text_pick_logp, ug_text_sample_logp) on the bf16-rounded
+        scores; each is exact to its own formula, the two heads round differently.
         num_beams and penalty_alpha are refused."""
         from unigen_hip.qwen2 import DecodeState, resolve_deterministic
         from .sampling import seen_mask_of, top_k_top_p_filtering
@@ -899,39 +958,54 @@ class UniGen(ModelMixin, ConfigMixin):
             sampling = None
             if do_sample:
                 sampling = (float(1.0 if temperature is None else temperature), int(top_k or 0), float(1.0 if top_p is None else top_p))
-            out, _, _ = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, sampling=sampling, stop=eos,
-                                                    pad_token_id=pad_token_id if eos else None, generator=generator,
-                                                    use_graph=bool(kwargs.get("use_graph", True)), trace=kwargs.get("trace"),
-                                                    repetition_penalty=penalty, prompt_ids=None if input_embeddings is not None else input_ids.to(dev))
-            return torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
+            res = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, sampling=sampling, stop=eos,
+                                              pad_token_id=pad_token_id if eos else None, generator=generator,
+                                              use_graph=bool(kwargs.get("use_graph", True)), trace=kwargs.get("trace"),
+                                              repetition_penalty=penalty, prompt_ids=None if input_embeddings is not None else input_ids.to(dev),
+                                              return_logprobs=bool(return_logprobs))
+            out = res[0]
+            seqs = torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
+            return (seqs, res[3]) if return_logprobs else seqs
         st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, key_valid)
         eng.check_errors()
         out = torch.full((R, max_new_tokens), int(pad_token_id or 0), dtype=torch.long, device=dev)
 
-        def pick(last):
+        def process(last):                           # the scores the pick chooses from (greedy: no temperature, no filter)
             if not do_sample:
-                return last.argmax(-1, keepdim=True)
+                return last
             if temperature is not None and temperature != 1.0:
                 last = last / temperature
-            last = top_k_top_p_filtering(last, top_k=int(top_k or 0), top_p=float(1.0 if top_p is None else top_p))
+            return top_k_top_p_filtering(last, top_k=int(top_k or 0), top_p=float(1.0 if top_p is None else top_p))
+
+        def choose(scores):
+            if not do_sample:
+                return scores.argmax(-1, keepdim=True)
             u_dev = dev if generator is None else generator.device
-            return torch.multinomial(torch.softmax(last, dim=-1).to(u_dev), num_samples=1, generator=generator).to(dev)
+            return torch.multinomial(torch.softmax(scores, dim=-1).to(u_dev), num_samples=1, generator=generator).to(dev)
+
+        def pick(last):
+            return choose(process(last))
 
         stop = torch.tensor(eos, device=dev) if eos else None
         emit = emit_until_stop(out, stop, pad_token_id)
+        logp = None
+        if return_logprobs:
+            logp = torch.zeros((R, max_new_tokens), dtype=torch.float32, device=dev)
+            pick, emit = with_logprobs(process, choose, emit, logp)
         if penalty != 1.0:
             seen = seen_mask_of(None if input_embeddings is not None else input_ids, key_valid, R, self.config.vocab_size, dev)
             pick, emit = with_repetition_penalty(pick, emit, penalty, seen)
-        out = out[:, :self._decode_text(st, hn, max_new_tokens, pick, emit)]
-        if input_embeddings is None:
-            return torch.cat([input_ids.to(dev), out], dim=1)
-        return out
+        steps = self._decode_text(st, hn, max_new_tokens, pick, emit)
+        out = out[:, :steps]
+        seqs = torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
+        return (seqs, logp[:, :steps]) if return_logprobs else seqs
 
     # ------------------------------------------------------------------ text decoding for understanding
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
-                     top_k=None, eot_token=None, use_cache=True, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0):
+                     top_k=None, eot_token=None, use_cache=True, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0,
+                     return_logprobs=False, trace=None):
         """Greedy / top-k text continuation (reference models/unigen.py:523-581).  The reference re-runs the whole
         growing sequence every step and extends the additive mask by one row that copies the previous last row;
         here the prompt is prefilled once under its mask into the static KV cache and every new token is one decode
@@ -942,7 +1016,10 @@ class UniGen(ModelMixin, ConfigMixin):
         temperature -> top-k -> inverse CDF on uniforms drawn up front, so sampled tokens differ from the host loop's for the same
         seed).  Cached form only: an explicit True with use_cache=False raises.
         repetition_penalty: as in `generate`, cached form only (both loops); the prompt ids are `idx` at the keys the prompt's last row
-        sees, nothing with an `input_embeddings` prompt.  The recompute form raises for a penalty other than 1."""
+        sees, nothing with an `input_embeddings` prompt.  The recompute form raises for a penalty other than 1.
+        return_logprobs: returns (token list, fp32 1-D device tensor of the same length): every token's log-probability as in `generate`
+        (temperature 0: the greedy form; temperature > 0: behind temperature and top-k).  Cached form only.
+        trace: a list that receives every eager on-device step's raw fp32 head logits (use_graph=False)."""
         from unigen_hip.qwen2 import resolve_deterministic
         penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate")
         det = resolve_deterministic(deterministic)
@@ -952,21 +1029,34 @@ class UniGen(ModelMixin, ConfigMixin):
         self.llm.engine.last_text_decode_on_device = dev_loop
         if cached:
             return self._mmu_generate_cached(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
-                                             on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty)
+                                             on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty,
+                                             return_logprobs=bool(return_logprobs), trace=trace)
+        if return_logprobs:
+            raise UniGenHipError("mmu_generate: return_logprobs needs the cached form (use_cache=True and a one-row mask)")
         if penalty != 1.0:
             raise UniGenHipError("mmu_generate: repetition_penalty needs the cached form (use_cache=True and a one-row mask); the recompute "
                                  "form does not apply it")
         return self._mmu_generate_recompute(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token)
 
     @staticmethod
-    def _pick_next(last, temperature, top_k):
+    def _process_next(last, temperature, top_k):
+        """the scores `_choose_next` picks from: temperature, then top-k as -inf (temperature 0: greedy, the scores as they are)"""
         if temperature > 0:
             last = last / temperature
             if top_k is not None:
                 v, _ = torch.topk(last, min(top_k, last.size(-1)))
                 last[last < v[:, [-1]]] = -float('Inf')
-            return torch.multinomial(torch.softmax(last, dim=-1), num_samples=1)
-        return torch.argmax(last, dim=-1).reshape(-1, 1)
+        return last
+
+    @staticmethod
+    def _choose_next(scores, temperature):
+        if temperature > 0:
+            return torch.multinomial(torch.softmax(scores, dim=-1), num_samples=1)
+        return torch.argmax(scores, dim=-1).reshape(-1, 1)
+
+    @staticmethod
+    def _pick_next(last, temperature, top_k):
+        return UniGen._choose_next(UniGen._process_next(last, temperature, top_k), temperature)
 
     @staticmethod
     def _stop_list(stop):
@@ -1005,7 +1095,7 @@ class UniGen(ModelMixin, ConfigMixin):
         raise UniGenHipError(f"{who}: on_device=True cannot serve this call: {why}")
 
     def _decode_text_on_device(self, prompt, max_new_tokens, det, key_valid=None, mask_bits=None, sampling=None, stop=(), pad_token_id=None,
-                               generator=None, use_graph=True, trace=None, repetition_penalty=1.0, prompt_ids=None):
+                               generator=None, use_graph=True, trace=None, repetition_penalty=1.0, prompt_ids=None, return_logprobs=False):
         """The token loop of `text_token_loop` + `emit_until_stop` with nothing but launches per token: prefill, token 0 eagerly from
         the prefill's hidden state (GEMV head + pick), step 1 eagerly (warm-up), step 2 captured (its first replay IS step 2), replays
         from there.  The pick launch applies the stop rule on the device; with stop ids the host reads `remaining` every 8 tokens and
@@ -1020,6 +1110,8 @@ class UniGen(ModelMixin, ConfigMixin):
         repetition_penalty p != 1: the session's logits processor runs between head and pick of every step (ug_text_penalize); its
         `seen` bitmap is zeroed here and takes prompt_ids [R, L] (None: no ids) at the positions key_valid marks real, one launch
         outside the captured step.  p == 1 allocates and launches nothing.
+        return_logprobs: the session owns a log-probability buffer and its pick launches are the entry points that fill it (part of the
+        session key: such a call never replays the graph of a call without it, nor the reverse); a fourth result, fp32 [R, steps].
         -> (tokens int64 [R, steps], lengths int64 [R], steps)."""
         from unigen_hip.qwen2 import TextDecodeSession
         eng = self.llm.engine
@@ -1038,6 +1130,8 @@ class UniGen(ModelMixin, ConfigMixin):
         key = (R, cap, width, V, eng.decode_form(R, det), det, sampling, penalty, tuple(stop), pad, key_valid is None, str(dev),
                eng.fp.w("embed").data_ptr(), eng.fp.w("l0.wqkv").data_ptr(), eng.fp.p("embed").data_ptr(), eng.fp.p("norm").data_ptr(),
                eng.fp.w(f"l{n_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(cap)))
+        if return_logprobs:
+            key += ("logprobs",)
         keep = use_graph and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0"
         sess = getattr(eng, "_text_session", None) if keep else None
         if sess is not None and sess.key != key:
@@ -1045,7 +1139,7 @@ class UniGen(ModelMixin, ConfigMixin):
         eng._text_session = None                     # (put back at the end of a call that completed)
         if sess is None:
             sess = TextDecodeSession(eng, R, cap, width, V, deterministic=det, sampling=sampling, stop_ids=stop, pad_id=pad, key_valid=key_valid,
-                                     repetition_penalty=penalty)
+                                     repetition_penalty=penalty, logprobs=bool(return_logprobs))
             sess.key = key
             sess.begin(n, prompt_ids=prompt_ids, prompt_valid=key_valid)
         else:
@@ -1077,9 +1171,10 @@ class UniGen(ModelMixin, ConfigMixin):
         steps = used if used > 0 else n
         eng.last_decode_graph = sess.graph is not None
         tokens, lengths = sess.out_tokens[:, :steps].long(), sess.lengths.long()       # (copies: the next call overwrites the session's)
+        logp = sess.logp[:, :steps].clone() if return_logprobs else None
         if keep and sess.graph is not None:
             eng._text_session = sess
-        return tokens, lengths, steps
+        return (tokens, lengths, steps, logp) if return_logprobs else (tokens, lengths, steps)
 
     def _decode_text(self, st, hn, max_new_tokens, pick, emit):
         """text_token_loop on this model's engine from a prefilled state: vocabulary logits, embedding table, decode_step."""
@@ -1090,10 +1185,11 @@ class UniGen(ModelMixin, ConfigMixin):
                                step=lambda x: eng.decode_step(st, x))            # (also advances the cache position)
 
     def _mmu_decode(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det, on_device=False,
-                    use_graph=True, repetition_penalty=1.0, trace=None):
+                    use_graph=True, repetition_penalty=1.0, trace=None, return_logprobs=False):
         """Prefill R left-padded rows under their dense [R, 1, L, L] masks, then decode -> (tokens [R, max_new_tokens] on the device,
         the rows' lengths cut after `eot_token` [R], the number of steps taken).  repetition_penalty: the prompt ids are `idx` (when the
-        prompt is not given as embeddings) at the keys the prompt's last row sees."""
+        prompt is not given as embeddings) at the keys the prompt's last row sees.  return_logprobs: a fourth result, the tokens'
+        log-probabilities fp32 [R, max_new_tokens] (0.0 behind a row's `eot_token` and behind the last step taken)."""
         from unigen_hip.qwen2 import DecodeState
         from .sampling import seen_mask_of
         eng = self.llm.engine
@@ -1105,36 +1201,49 @@ class UniGen(ModelMixin, ConfigMixin):
         key_valid = attention_mask[:, 0, -1, :] == 0
         if on_device:
             sampling = (float(temperature), int(top_k or 0), 1.0) if temperature > 0 else None
-            tokens, lengths, steps = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, mask_bits=mb, sampling=sampling,
-                                                                 stop=self._stop_list(eot_token), use_graph=use_graph, trace=trace,
-                                                                 repetition_penalty=repetition_penalty,
-                                                                 prompt_ids=idx if input_embeddings is None else None)
+            res = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, mask_bits=mb, sampling=sampling,
+                                              stop=self._stop_list(eot_token), use_graph=use_graph, trace=trace,
+                                              repetition_penalty=repetition_penalty,
+                                              prompt_ids=idx if input_embeddings is None else None, return_logprobs=return_logprobs)
+            tokens, lengths, steps = res[:3]
+            logp = res[3] if return_logprobs else None
             if steps < max_new_tokens:              # (the host loop's shapes: the buffer is max_new_tokens wide)
                 tokens = torch.cat([tokens, tokens.new_zeros((R, max_new_tokens - steps))], dim=1)
-            return tokens, lengths, steps
+                if return_logprobs:
+                    logp = torch.cat([logp, logp.new_zeros((R, max_new_tokens - steps))], dim=1)
+            return (tokens, lengths, steps, logp) if return_logprobs else (tokens, lengths, steps)
         st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, mask_bits=mb)
         tokens = torch.zeros((R, max_new_tokens), dtype=torch.long, device=dev)
         lengths = torch.full((R,), max_new_tokens, dtype=torch.long, device=dev)
         pick, emit = (lambda last: self._pick_next(last, temperature, top_k)), emit_until_stop(tokens, eot_token, lengths=lengths)
+        logp = None
+        if return_logprobs:
+            logp = torch.zeros((R, max_new_tokens), dtype=torch.float32, device=dev)
+            pick, emit = with_logprobs(lambda last: self._process_next(last, temperature, top_k),
+                                       lambda scores: self._choose_next(scores, temperature), emit, logp)
         if repetition_penalty != 1.0:
             seen = seen_mask_of(idx if input_embeddings is None else None, key_valid, R, self.config.vocab_size, dev)
             pick, emit = with_repetition_penalty(pick, emit, repetition_penalty, seen)
         steps = self._decode_text(st, hn, max_new_tokens, pick, emit)
-        return tokens, lengths, steps
+        return (tokens, lengths, steps, logp) if return_logprobs else (tokens, lengths, steps)
 
     @torch.no_grad()
     def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False,
-                             on_device=False, use_graph=True, repetition_penalty=1.0):
-        """The one-row case of the batch path -> list of 0-d device tensors (one row: it ends at its `eot_token`, so every step counts)."""
+                             on_device=False, use_graph=True, repetition_penalty=1.0, return_logprobs=False, trace=None):
+        """The one-row case of the batch path -> list of 0-d device tensors (one row: it ends at its `eot_token`, so every step counts);
+        return_logprobs: (that list, the tokens' log-probabilities fp32 [steps])."""
         L = attention_mask.shape[-1]
-        tokens, _, steps = self._mmu_decode(idx, input_embeddings, attention_mask.reshape(1, 1, L, L), max_new_tokens, temperature, top_k,
-                                            eot_token, det, on_device=on_device, use_graph=use_graph, repetition_penalty=repetition_penalty)
-        return list(tokens[0, :steps])
+        res = self._mmu_decode(idx, input_embeddings, attention_mask.reshape(1, 1, L, L), max_new_tokens, temperature, top_k,
+                               eot_token, det, on_device=on_device, use_graph=use_graph, repetition_penalty=repetition_penalty,
+                               trace=trace, return_logprobs=return_logprobs)
+        tokens, steps = res[0], res[2]
+        return (list(tokens[0, :steps]), res[3][0, :steps].clone()) if return_logprobs else list(tokens[0, :steps])
 
     @torch.no_grad()
     def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=0.0,
-                           top_k=None, eot_token=None, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0, trace=None):
+                           top_k=None, eot_token=None, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0, trace=None,
+                           return_logprobs=False):
         """`mmu_generate` for up to 32 prompts at once -- the rating loop of CoT-V (reference
         evaluation/inference_unigen_cot.py:308-415 calls mmu_generate once per (image, question) pair; every decode
         step streams the whole backbone whatever the row count, so R pairs cost about one).  Rows are LEFT-padded to a
@@ -1144,7 +1253,9 @@ class UniGen(ModelMixin, ConfigMixin):
         last prompt row could see plus everything generated since.  Returns R lists of tokens, each cut after its
         `eot_token`.  deterministic: ordered decode kernels; None follows torch.are_deterministic_algorithms_enabled().
         on_device / use_graph: the token loop on the device, as in `mmu_generate`.  repetition_penalty: as in `mmu_generate`, both
-        loops.  trace: a list that receives every eager on-device step's raw fp32 head logits (use_graph=False)."""
+        loops.  trace: a list that receives every eager on-device step's raw fp32 head logits (use_graph=False).
+        return_logprobs: returns (the token lists, a list of fp32 1-D device tensors, row r's cut at its length): every token's
+        log-probability as in `mmu_generate`."""
         from unigen_hip.qwen2 import resolve_deterministic
         penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate_batch")
         det = resolve_deterministic(deterministic)
@@ -1156,10 +1267,14 @@ class UniGen(ModelMixin, ConfigMixin):
             raise ValueError("mmu_generate_batch: attention_mask must be the rows' dense [R, 1, L, L] additive masks")
         dev_loop = self._text_on_device(on_device, "mmu_generate_batch", R, True, eot_token, max_new_tokens)
         self.llm.engine.last_text_decode_on_device = dev_loop
-        tokens, lengths, _ = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
-                                              on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace)
-        tokens, lengths = tokens.cpu(), lengths.cpu()
-        return [list(tokens[r, :int(lengths[r])]) for r in range(R)]
+        res = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
+                               on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace,
+                               return_logprobs=bool(return_logprobs))
+        tokens, lengths = res[0].cpu(), res[1].cpu()
+        lists = [list(tokens[r, :int(lengths[r])]) for r in range(R)]
+        if return_logprobs:
+            return lists, [res[3][r, :int(lengths[r])].clone() for r in range(R)]
+        return lists
 
     def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token):
         device = idx.device if idx is not None else input_embeddings.device

@@ -66,6 +66,10 @@ SIGNATURES = {
     "ug_text_pick": [P, I64, I64, I64, I32, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P],
     "ug_text_sample_workspace_ints": [I64],
     "ug_text_sample": [P, I64, I64, I64, I32, F32, I64, F32, P, P, P, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P],
+    "ug_ar_sample_logp": [P, I64, I64, I64, F32, F32, I32, P, P, I64, I64, P, I64, I64, I64, P, P, P, P, P],
+    "ug_ar_sample_filtered_logp": [P, I64, I64, I64, F32, F32, I32, P, P, I64, I64, P, I64, I64, I64, P, P, P, I64, F32, F32, P, P, P],
+    "ug_text_pick_logp": [P, I64, I64, I64, I32, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P, P],
+    "ug_text_sample_logp": [P, I64, I64, I64, I32, F32, I64, F32, P, P, P, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P, P],
     "ug_text_seen_mark": [P, I64, P, I64, I64, I64, P, I64, P],
     "ug_text_penalize": [P, I64, I64, I64, F32, P, I64, P, P],
     "ug_maskgit_step": [P, I64, I64, I64, I64, I32, F32, P, P, P, I64, I64, I64, F32, P, P, P, P, P, P],

@@ -757,23 +757,40 @@ def maskgit_train_mask(tokens, scores, num_masked, mask_id, ignore_id=-100):
 
 
 def ar_sample_(acc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_dev, pos0, nsteps, embed_master, id_offset, tok,
-               out_tokens, x):
-    """Fused AR sampling step on the raw lm-head accumulator (see include/unigen_hip.h: ug_ar_sample)."""
-    _l.check(_l.load().ug_ar_sample(_p(acc), acc.stride(0), bsz, V, float(guidance_scale), float(temperature), int(bool(greedy)),
-                                    _p(uniforms), _p(pos_dev), int(pos0), int(nsteps), _p(embed_master), embed_master.stride(0),
-                                    embed_master.shape[1], int(id_offset), _p(tok), _p(out_tokens), _p(x), _stream()),
-             "ug_ar_sample")
+               out_tokens, x, logp=None):
+    """Fused AR sampling step on the raw lm-head accumulator (see include/unigen_hip.h: ug_ar_sample).  logp: optional fp32
+    [bsz, nsteps, 2] taking the step's (log-probability under the drawn-from distribution, conditional log-softmax) of the token
+    (ug_ar_sample_logp; None launches ug_ar_sample itself)."""
+    args = (_p(acc), acc.stride(0), bsz, V, float(guidance_scale), float(temperature), int(bool(greedy)), _p(uniforms), _p(pos_dev),
+            int(pos0), int(nsteps), _p(embed_master), embed_master.stride(0), embed_master.shape[1], int(id_offset), _p(tok),
+            _p(out_tokens), _p(x))
+    if logp is None:
+        _l.check(_l.load().ug_ar_sample(*args, _stream()), "ug_ar_sample")
+    else:
+        _l.check(_l.load().ug_ar_sample_logp(*args, _p(_logp_buffer(logp, (bsz, int(nsteps), 2))), _stream()), "ug_ar_sample_logp")
 
 
 def ar_sample_filtered_(acc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_dev, pos0, nsteps, embed_master, id_offset, tok,
-                        out_tokens, x, top_k=0, top_p=1.0, min_p=0.0, stats=None):
+                        out_tokens, x, top_k=0, top_p=1.0, min_p=0.0, stats=None, logp=None):
     """ar_sample_ with top-k / top-p / min-p truncation as value thresholds (see include/unigen_hip.h: ug_ar_sample_filtered);
-    stats: optional fp32 [bsz, 2] taking the smallest kept value and the kept count per image."""
-    _l.check(_l.load().ug_ar_sample_filtered(_p(acc), acc.stride(0), bsz, V, float(guidance_scale), float(temperature), int(bool(greedy)),
-                                             _p(uniforms), _p(pos_dev), int(pos0), int(nsteps), _p(embed_master),
-                                             embed_master.stride(0), embed_master.shape[1], int(id_offset), _p(tok), _p(out_tokens),
-                                             _p(x), int(top_k), float(top_p), float(min_p), _p(stats), _stream()),
-             "ug_ar_sample_filtered")
+    stats: optional fp32 [bsz, 2] taking the smallest kept value and the kept count per image.  logp: as in ar_sample_
+    (ug_ar_sample_filtered_logp; None launches ug_ar_sample_filtered itself)."""
+    args = (_p(acc), acc.stride(0), bsz, V, float(guidance_scale), float(temperature), int(bool(greedy)), _p(uniforms), _p(pos_dev),
+            int(pos0), int(nsteps), _p(embed_master), embed_master.stride(0), embed_master.shape[1], int(id_offset), _p(tok),
+            _p(out_tokens), _p(x), int(top_k), float(top_p), float(min_p), _p(stats))
+    if logp is None:
+        _l.check(_l.load().ug_ar_sample_filtered(*args, _stream()), "ug_ar_sample_filtered")
+    else:
+        _l.check(_l.load().ug_ar_sample_filtered_logp(*args, _p(_logp_buffer(logp, (bsz, int(nsteps), 2))), _stream()),
+                 "ug_ar_sample_filtered_logp")
+
+
+def _logp_buffer(logp, shape):
+    """the log-probability output of a sampler launch: fp32, contiguous, on the device, of exactly `shape` (the kernels index it by
+    row and step, so anything else would be written out of bounds)"""
+    if not (torch.is_tensor(logp) and logp.is_cuda and logp.dtype == torch.float32 and logp.is_contiguous() and tuple(logp.shape) == tuple(shape)):
+        raise _l.UniGenHipError(f"logp must be a contiguous fp32 device tensor of shape {tuple(shape)}")
+    return logp
 
 
 # ------------------------------------------------------------------------------------ text decode: pick over the whole vocabulary
@@ -806,24 +823,34 @@ def _text_out(stop_ids, pad_id, embed_master):
             embed_master.stride(0), embed_master.shape[0], embed_master.shape[1])
 
 
-def text_pick_(logits, V, state, nsteps, embed_master, tok, out_tokens, x, clear=False, stop_ids=None, pad_id=None, lengths=None):
+def text_pick_(logits, V, state, nsteps, embed_master, tok, out_tokens, x, clear=False, stop_ids=None, pad_id=None, lengths=None, logp=None):
     """Greedy token of every row of fp32 logits [R, ld >= V] + the stop rule, the records and the next input (include/unigen_hip.h:
     ug_text_pick).  stop_ids: int64 device tensor of up to 8 ids or None; state: ops.text_state; tok int64 [R]; out_tokens int32
-    [R, nsteps]; lengths int32 [R] or None; x fp32 [R, H]."""
+    [R, nsteps]; lengths int32 [R] or None; x fp32 [R, H].  logp: optional fp32 [R, nsteps] taking the log-softmax of the bf16 scores at
+    the emitted token, 0.0 for a row that had finished (ug_text_pick_logp; None launches ug_text_pick itself)."""
     _need_cuda(logits, state, embed_master, tok, out_tokens, x)
-    _l.check(_l.load().ug_text_pick(_p(logits), logits.stride(0), logits.shape[0], int(V), int(bool(clear)), *_text_out(stop_ids, pad_id, embed_master),
-                                    _p(state), int(nsteps), _p(tok), _p(out_tokens), _p(lengths), _p(x), _stream()), "ug_text_pick")
+    args = (_p(logits), logits.stride(0), logits.shape[0], int(V), int(bool(clear)), *_text_out(stop_ids, pad_id, embed_master), _p(state),
+            int(nsteps), _p(tok), _p(out_tokens), _p(lengths), _p(x))
+    if logp is None:
+        _l.check(_l.load().ug_text_pick(*args, _stream()), "ug_text_pick")
+    else:
+        _l.check(_l.load().ug_text_pick_logp(*args, _p(_logp_buffer(logp, (logits.shape[0], int(nsteps)))), _stream()), "ug_text_pick_logp")
 
 
 def text_sample_(logits, V, state, nsteps, embed_master, tok, out_tokens, x, uniforms, workspace, temperature=1.0, top_k=0, top_p=1.0,
-                 clear=False, stop_ids=None, pad_id=None, lengths=None, stats=None):
+                 clear=False, stop_ids=None, pad_id=None, lengths=None, stats=None, logp=None):
     """text_pick_ with a sampled token: temperature -> top-k -> top-p -> inverse-CDF draw on uniforms [nsteps, R] over the kept entries in
     value-descending order (include/unigen_hip.h: ug_text_sample).  workspace: ops.text_sample_workspace; stats: optional fp32 [R, 2]
-    taking the smallest kept value and the kept count."""
+    taking the smallest kept value and the kept count.  logp: optional fp32 [R, nsteps] taking the token's log-probability under the
+    truncated distribution it was drawn from (ug_text_sample_logp; None launches ug_text_sample itself)."""
     _need_cuda(logits, state, embed_master, tok, out_tokens, x, uniforms, workspace)
-    _l.check(_l.load().ug_text_sample(_p(logits), logits.stride(0), logits.shape[0], int(V), int(bool(clear)), float(temperature), int(top_k),
-                                      float(top_p), _p(uniforms), _p(workspace), _p(stats), *_text_out(stop_ids, pad_id, embed_master),
-                                      _p(state), int(nsteps), _p(tok), _p(out_tokens), _p(lengths), _p(x), _stream()), "ug_text_sample")
+    args = (_p(logits), logits.stride(0), logits.shape[0], int(V), int(bool(clear)), float(temperature), int(top_k), float(top_p),
+            _p(uniforms), _p(workspace), _p(stats), *_text_out(stop_ids, pad_id, embed_master), _p(state), int(nsteps), _p(tok),
+            _p(out_tokens), _p(lengths), _p(x))
+    if logp is None:
+        _l.check(_l.load().ug_text_sample(*args, _stream()), "ug_text_sample")
+    else:
+        _l.check(_l.load().ug_text_sample_logp(*args, _p(_logp_buffer(logp, (logits.shape[0], int(nsteps)))), _stream()), "ug_text_sample_logp")
 
 
 def text_seen(rows, V, device):

@@ -247,10 +247,12 @@ class TextDecodeSession:
     sampling: None (greedy) or (temperature, top_k, top_p).  The logits' leading dimension is the vocabulary rounded up to 8, except in
     deterministic mode, where the ordered head writes a contiguous [rows, vocab] result.
     repetition_penalty p != 1: the session owns the logits processor's `seen` bitmap [rows, ceil(vocab / 32)] (include/unigen_hip.h:
-    ug_text_penalize) and every step launches the processor between head and pick; p == 1 allocates and launches nothing."""
+    ug_text_penalize) and every step launches the processor between head and pick; p == 1 allocates and launches nothing.
+    logprobs: the session owns `logp` fp32 [rows, width] and every pick launch is the entry point that also writes the emitted token's
+    log-probability into it (ug_text_pick_logp / ug_text_sample_logp); off: no buffer, the entry points without the output."""
 
     def __init__(self, eng, rows, capacity, width, vocab, deterministic=False, sampling=None, stop_ids=(), pad_id=None, key_valid=None,
-                 repetition_penalty=1.0):
+                 repetition_penalty=1.0, logprobs=False):
         dev, d = eng.device, eng.dims
         self.rows, self.width, self.V, self.sampling = rows, width, vocab, sampling
         self.form = eng.decode_form(rows, deterministic)
@@ -269,6 +271,7 @@ class TextDecodeSession:
             self.uniforms = torch.zeros((width, rows), dtype=torch.float32, device=dev)
         self.penalty = float(repetition_penalty)
         self.seen = ops.text_seen(rows, vocab, dev) if self.penalty != 1.0 else None
+        self.logp = torch.zeros((rows, width), dtype=torch.float32, device=dev) if logprobs else None
         self.graph, self.key = None, None
 
     def begin(self, new_tokens, key_valid=None, prompt_len=0, prompt_ids=None, prompt_valid=None):
@@ -278,6 +281,8 @@ class TextDecodeSession:
         (None: all)."""
         ops.text_state_reset_(self.state, self.rows)
         self.lengths.fill_(int(new_tokens))
+        if self.logp is not None:
+            self.logp.zero_()
         if key_valid is not None:
             self.st.key_valid[:, :prompt_len].copy_(key_valid)
             self.st.key_valid[:, prompt_len:].fill_(1)
@@ -688,6 +693,8 @@ class Qwen2Engine:
         """the pick launch(es) of a text step on sess.logits (include/unigen_hip.h: ug_text_pick / ug_text_sample).  The atomic GEMV
         head of the splitk and wide forms needs its accumulator back zeroed: clear=1 there."""
         kw = dict(clear=sess.form in ("splitk", "wide"), stop_ids=sess.stop_ids, pad_id=sess.pad_id, lengths=sess.lengths)
+        if sess.logp is not None:
+            kw["logp"] = sess.logp                  # (the _logp entry points; without the buffer the launches are what they were)
         emb = self.fp.p("embed")
         if sess.sampling is None:
             ops.text_pick_(sess.logits, sess.V, sess.state, sess.width, emb, sess.tok, sess.out_tokens, sess.x, **kw)

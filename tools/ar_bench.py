@@ -49,11 +49,13 @@ def run(n_img=8, prefix=138, n_tok=256, use_graph=True, reps=3):
 MODES = {   # name of the second mode -> the arguments of t2i_generate_ar that select it (the first mode is always the default call)
     "deterministic": {"deterministic": True},
     "truncated": {"top_k": 50, "top_p": 0.95},
+    "logprobs": {"return_logprobs": True},
 }
 
 
 def run_modes(second="deterministic", n_img=8, prefix=138, n_tok=256, rounds=5):
-    """Default vs a second mode (MODES: deterministic decode, or truncated sampling with top_k=50, top_p=0.95) in ONE process at the
+    """Default vs a second mode (MODES: deterministic decode, truncated sampling with top_k=50, top_p=0.95, or per-token
+    log-probabilities from the sampler launch) in ONE process at the
     bench shape, captured graph, the two modes alternating.  One kept session exists at a time and the mode is part of its key, so
     each visit to a mode makes two calls and times the second (it replays the session the first one captured).  Prints both medians
     and their ratio."""
@@ -80,6 +82,9 @@ def run_modes(second="deterministic", n_img=8, prefix=138, n_tok=256, rounds=5):
                 torch.cuda.synchronize()
                 if k == 1:
                     times[name].append(time.perf_counter() - t0)
+                if isinstance(toks, tuple):                      # (return_logprobs: tokens, logprobs, cond_logprobs)
+                    assert all(t.shape == (n_img, n_tok) and float(t.max()) <= 0.0 for t in toks[1:])
+                    toks = toks[0]
             assert model.llm.engine.last_decode_deterministic == kw["deterministic"] and model.llm.engine.last_decode_graph
             assert toks.shape == (n_img, n_tok) and int(toks.min()) >= 0 and int(toks.max()) < CODEBOOK
     out = {}
@@ -93,7 +98,7 @@ def run_modes(second="deterministic", n_img=8, prefix=138, n_tok=256, rounds=5):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("--deterministic", "--truncated"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("--deterministic", "--truncated", "--logprobs"):
         print(json.dumps(run_modes(sys.argv[1][2:])), flush=True)
     elif len(sys.argv) > 1 and sys.argv[1] == "graph":          # profiling runs: the captured path only, one repetition after the warm-up
         print(json.dumps(run(use_graph=True, reps=3)), flush=True)
