@@ -689,8 +689,7 @@ class UniGen(ModelMixin, ConfigMixin):
         captured step's sampler launch writes both (no extra pass over the logits, no host work per token); the unfused branch uses
         models/sampling.py: token_logprobs.  The flag is part of the kept session: a call with it never replays the graph of a call
         without it, nor the reverse."""
-        from unigen_hip.qwen2 import DecodeState, resolve_deterministic
-        from .sampling import token_logprobs, truncate_logits
+        from unigen_hip.qwen2 import ArDecodeSession, decode_loop, put_session, resolve_deterministic, take_session
         want_lp = bool(return_logprobs)
         top_k = 0 if top_k is None else top_k
         top_p = 1.0 if top_p is None else float(top_p)
@@ -719,104 +718,31 @@ class UniGen(ModelMixin, ConfigMixin):
         greedy = bool(kwargs.get("greedy", False))          # argmax instead of multinomial: deterministic parity tests
         logit_trace = kwargs.get("trace")                   # optional list: fp32 [rows, V] head logits of every eager step
         use_graph = bool(kwargs.get("use_graph", True))
-        code_lo, code_hi = text_vocab_size, self.vocab_size - 1          # logits[..., text_vocab_size:-1]
-        V = code_hi - code_lo
+        V = self.vocab_size - 1 - text_vocab_size                        # logits[..., text_vocab_size:-1]
         if top_k >= V:
             top_k = 0
         filt = (top_k, top_p, min_p) if not greedy and (top_k > 0 or top_p < 1.0 or min_p > 0.0) else None
+        # fused: the lm-head as a weight-streaming GEMV into a raw fp32 accumulator + ONE sampling kernel per step
+        # (Qwen2Engine.ar_step); otherwise the host sampler on the bf16 head slice (_ar_host_token)
         fused = (R <= 32 and eng.dims.hidden_size >= 256 and eng.dims.hidden_size % 32 == 0 and not kwargs.get("torch_sampler", False)
                  and not gen)
         # The captured decode step is kept ACROSS calls (round 5): Best-of-N generation calls this method once per prompt with the
         # same shapes (evaluation/inference_unigen_cot.py:318-331), and capturing costs ~6 ms of a 330 ms call (an eager warm-up
-        # step + the capture).  A session = every buffer the graph reads or writes (cache, position, accumulators, token /
-        # embedding slots, uniforms) + the graph; it is reused only when every size, every sampling constant baked into a kernel
-        # argument and the weight storage are the same (UNIGEN_AR_GRAPH_CACHE=0 turns the reuse off), and dropped on any error.
+        # step + the capture).  A session (unigen_hip/qwen2.py: ArDecodeSession) = every buffer the graph reads or writes + the
+        # graph; it is reused only when every size, every sampling constant baked into a kernel argument and the weight storage
+        # are the same (UNIGEN_AR_GRAPH_CACHE=0 turns the reuse off), and dropped on any error.  Only the fused branch keeps one.
         form = eng.decode_form(R, det)               # (a captured step belongs to one layer form: its launches and scratch differ)
-        sess_key = (R, P, n, bsz, V, int(text_vocab_size), greedy, float(guidance_scale), float(temperature), key_valid is None, str(dev), form,
-                    eng.fp.w("embed").data_ptr(), eng.fp.w("l0.wqkv").data_ptr(), eng.fp.p("embed").data_ptr(), eng.fp.p("norm").data_ptr(),
-                    # (every other pointer the captured step bakes in lives in the same two flat buffers; the last layer's weights and the
-                    # RoPE tables stand in for "nothing was reallocated in between")
-                    eng.fp.w(f"l{eng.dims.num_hidden_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(P + n)),
-                    filt)                                    # (the filter constants are kernel arguments of the captured sampler)
+        sess_key = (R, P, n, bsz, V, int(text_vocab_size), greedy, float(guidance_scale), float(temperature), key_valid is None, str(dev),
+                    form) + eng.storage_key(P + n) + (filt,)     # (the filter constants are kernel arguments of the captured sampler)
         if want_lp:
             sess_key += ("logprobs",)                        # (another sampler entry point and one more buffer in the captured step)
-        sess = getattr(eng, "_ar_session", None) if (use_graph and fused and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0") else None
-        if sess is not None and sess["key"] != sess_key:
-            sess = None
-        eng._ar_session = None                       # (put back at the end of a call that completed)
+        sess = take_session(eng, "_ar_session", sess_key, use_graph and fused)
         if sess is not None:
-            st, out_tokens, x, tok = sess["st"], sess["out_tokens"], sess["x"], sess["tok"]
-            if key_valid is not None:
-                st.key_valid[:, :P].copy_(key_valid)
+            sess.begin(key_valid, generator)
         else:
-            st = DecodeState(eng.dims, R, P + n, dev, key_valid=key_valid, deterministic=det)
-            out_tokens = torch.zeros((bsz, n), dtype=torch.int, device=dev)
-            x = torch.empty((R, eng.dims.hidden_size), dtype=torch.float32, device=dev)      # static: next token's embedding
-            tok = torch.zeros((bsz, 1), dtype=torch.long, device=dev)                        # static: last sampled token
-        # static: (logprobs, cond_logprobs) of every token, written by the sampler launch (fused) or copied from lp_now per step
-        logp = (sess["logp"] if sess is not None else torch.zeros((bsz, n, 2), dtype=torch.float32, device=dev)) if want_lp else None
-        if fused:
-            # lm-head as a weight-streaming GEMV into a raw fp32 accumulator + ONE sampling kernel per step (CFG mix,
-            # temperature, softmax, inverse-CDF draw on uniforms taken from `generator` up front, next input embedding)
-            u_dev = dev if generator is None else generator.device
-            fresh = None if greedy else torch.rand((n, bsz), device=u_dev, generator=generator).to(dev)
-            if sess is not None:
-                acc_head, uniforms = sess["acc_head"], sess["uniforms"]
-                if uniforms is not None:
-                    uniforms.copy_(fresh)
-            else:
-                acc_head = torch.zeros((R, V), dtype=torch.float32, device=dev)
-                uniforms = fresh
-            w_head = eng.fp.w("embed")[code_lo:code_hi]
-            w_embed = eng.fp.p("embed")
-
-            def keep_logits():                     # parity tests follow the head's raw logits step by step (eager runs only)
-                if logit_trace is not None and not torch.cuda.is_current_stream_capturing():
-                    logit_trace.append(acc_head.clone())
-
-            def draw():                            # the step's one sampling launch
-                if filt is None:
-                    ops.ar_sample_(acc_head, bsz, V, guidance_scale, temperature, greedy, uniforms, st.pos, P, n, w_embed,
-                                   text_vocab_size, tok, out_tokens, x, logp=logp)
-                else:
-                    ops.ar_sample_filtered_(acc_head, bsz, V, guidance_scale, temperature, greedy, uniforms, st.pos, P, n, w_embed,
-                                            text_vocab_size, tok, out_tokens, x, top_k=filt[0], top_p=filt[1], min_p=filt[2], logp=logp)
-
-            def sample(hn):
-                if det:
-                    ops.skinny_linear_ord(hn, w_head, out_f32=acc_head)
-                else:
-                    ops.decode_gemv_(hn, w_head, acc_head)
-                keep_logits()
-                draw()
-        else:
-            lp_now = torch.zeros((bsz, 2), dtype=torch.float32, device=dev) if want_lp else None     # static: the step's pair
-
-            def sample(hn):
-                # (gen path: the reference mixes the bf16 img_head outputs in bf16 under autocast, :498-500)
-                lg = self._img_head(hn) if gen else eng.head_slice(hn, code_lo, code_hi).float()
-                cond, uncond = lg[:bsz], lg[bsz:]
-                lg = (uncond + guidance_scale * (cond - uncond)).float()
-                if logit_trace is not None and want_lp and not torch.cuda.is_current_stream_capturing():
-                    logit_trace.append(torch.cat([cond, uncond]).float())
-                if greedy:
-                    nxt = lg.argmax(-1, keepdim=True)
-                    if want_lp:
-                        lg = lg / temperature              # (the greedy log-probability is taken at the call's temperature)
-                else:
-                    lg = lg / temperature
-                    if filt is not None:
-                        lg = truncate_logits(lg, top_k=filt[0], top_p=filt[1], min_p=filt[2])
-                    nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1, generator=generator)
-                if want_lp:
-                    lp_now[:, 0].copy_(token_logprobs(lg, nxt))
-                    lp_now[:, 1].copy_(token_logprobs(cond, nxt))
-                tok.copy_(nxt)
-                if gen:
-                    x.copy_(self.get_gen_embed(torch.cat([nxt, nxt]))[:, 0])
-                else:
-                    x.copy_(embed(torch.cat([nxt, nxt]) + text_vocab_size)[:, 0])
-
+            sess = ArDecodeSession(eng, R, bsz, P, n, V, text_vocab_size, guidance_scale, temperature, greedy, filt, deterministic=det,
+                                   key_valid=key_valid, generator=generator, logprobs=want_lp, fused=fused)
+            sess.key = sess_key
         timing = kwargs.get("timing")               # optional dict: wall seconds per phase (adds host syncs; measurement runs only)
 
         def mark(name, t0=[None]):
@@ -827,58 +753,60 @@ class UniGen(ModelMixin, ConfigMixin):
                     timing[name] = timing.get(name, 0.0) + now - t0[0]
                 t0[0] = now
 
+        def record(i):                              # the host sampler's token and pair of step i (outside the captured step)
+            sess.out_tokens[:, i] = sess.tok[:, 0]
+            if want_lp:
+                sess.logp[:, i] = sess.lp_now
+
         mark("setup")
-        sample(eng.prefill(st, prefix, key_valid))         # (capturing the prefill too was measured: 10.3 vs 10.6 ms, it is GPU-bound at 2 208 tokens)
-        mark("prefill")
-        if not fused:
-            out_tokens[:, 0] = tok[:, 0]
-            if want_lp:
-                logp[:, 0] = lp_now
-
-        # single-writer layer (csrc/decode_sw.hip): the final RMSNorm and the head slice are ONE launch behind the last layer
-        sw_head = fused and form in ("sw", "ord_sw")
-
-        def step():
-            if sw_head:
-                eng.decode_step_logits(st, x, w_head, acc_head)            # (also advances the cache position)
-                keep_logits()
-                draw()
-                return
-            hn = eng.decode_step(st, x)            # (also advances the cache position)
-            sample(hn)
-
-        graph = sess["graph"] if sess is not None else None
-        for i in range(1, n):
-            if graph is None and use_graph and (generator is None or fused) and i == 2:
-                # step 1 ran eagerly (warm-up: allocations, lazy inits); capture step 2 and replay it from then on
-                mark("eager_step")
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    step()
-                mark("capture")
-                graph.replay()                      # capture only records: this replay IS step 2
-            elif graph is not None:
-                graph.replay()
-            else:
-                step()
-            if not fused:
-                out_tokens[:, i] = tok[:, 0]
-                if want_lp:
-                    logp[:, i] = lp_now
-        mark("replay")
-        eng.last_decode_graph = graph is not None
+        hn = eng.prefill(sess.st, prefix, key_valid)       # (capturing the prefill too was measured: 10.3 vs 10.6 ms, it is GPU-bound at 2 208 tokens)
+        if fused:
+            eng.ar_first_token(sess, hn, logit_trace)
+            mark("prefill")
+            decode_loop(sess, lambda: eng.ar_step(sess, logit_trace), range(1, n), use_graph, mark=mark)
+        else:
+            self._ar_host_token(sess, hn, generator, logit_trace)
+            mark("prefill")
+            record(0)
+            # (the host sampler draws from `generator` on the host side of every step: a captured step could not)
+            decode_loop(sess, lambda: self._ar_host_token(sess, eng.decode_step(sess.st, sess.x), generator, logit_trace), range(1, n),
+                        use_graph and generator is None, mark=mark, after=record)
+        eng.last_decode_graph = sess.graph is not None
         eng.last_decode_deterministic = det
-        if graph is not None and fused and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0":
-            eng._ar_session = {"key": sess_key, "st": st, "out_tokens": out_tokens, "x": x, "tok": tok, "acc_head": acc_head,
-                               "uniforms": uniforms, "graph": graph}
-            if want_lp:
-                eng._ar_session["logp"] = logp
-                return out_tokens.clone(), logp[..., 0].clone(), logp[..., 1].clone()
-            return out_tokens.clone()                # (the session's buffer is overwritten by the next call)
-        if want_lp:
-            return out_tokens, logp[..., 0].clone(), logp[..., 1].clone()
-        return out_tokens
+        kept = put_session(eng, "_ar_session", sess, use_graph and fused)
+        tokens = sess.out_tokens.clone() if kept else sess.out_tokens        # (a kept session's buffer is overwritten by the next call)
+        return (tokens, sess.logp[..., 0].clone(), sess.logp[..., 1].clone()) if want_lp else tokens
+
+    def _ar_host_token(self, sess, hn, generator, trace=None):
+        """The host sampler's step of `t2i_generate_ar` (more than 32 rows, torch_sampler=True, the gen_projector path, hidden sizes the
+        fused kernels refuse): from the final-norm hidden state `hn`, the bf16 head slice, CFG mix, temperature, truncation and
+        torch.multinomial (greedy: argmax) -> sess.tok, the next input sess.x and, with log-probabilities, the step's pair sess.lp_now
+        (models/sampling.py: token_logprobs).  Capturable when `generator` is None."""
+        from .sampling import token_logprobs, truncate_logits
+        gen, bsz = self._use_gen(), sess.bsz
+        # (gen path: the reference mixes the bf16 img_head outputs in bf16 under autocast, :498-500)
+        lg = self._img_head(hn) if gen else self.llm.engine.head_slice(hn, sess.code_lo, sess.code_lo + sess.V).float()
+        cond, uncond = lg[:bsz], lg[bsz:]
+        lg = (uncond + sess.guidance_scale * (cond - uncond)).float()
+        if trace is not None and sess.lp_now is not None and not torch.cuda.is_current_stream_capturing():
+            trace.append(torch.cat([cond, uncond]).float())
+        if sess.greedy:
+            nxt = lg.argmax(-1, keepdim=True)
+            if sess.lp_now is not None:
+                lg = lg / sess.temperature              # (the greedy log-probability is taken at the call's temperature)
+        else:
+            lg = lg / sess.temperature
+            if sess.filt is not None:
+                lg = truncate_logits(lg, top_k=sess.filt[0], top_p=sess.filt[1], min_p=sess.filt[2])
+            nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1, generator=generator)
+        if sess.lp_now is not None:
+            sess.lp_now[:, 0].copy_(token_logprobs(lg, nxt))
+            sess.lp_now[:, 1].copy_(token_logprobs(cond, nxt))
+        sess.tok.copy_(nxt)
+        if gen:
+            sess.x.copy_(self.get_gen_embed(torch.cat([nxt, nxt]))[:, 0])
+        else:
+            sess.x.copy_(self.llm.model.embed_tokens(torch.cat([nxt, nxt]) + sess.code_lo)[:, 0])
 
     # ------------------------------------------------------------------ plain causal generation
     @torch.no_grad()
@@ -958,14 +886,12 @@ class UniGen(ModelMixin, ConfigMixin):
             sampling = None
             if do_sample:
                 sampling = (float(1.0 if temperature is None else temperature), int(top_k or 0), float(1.0 if top_p is None else top_p))
-            res = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, sampling=sampling, stop=eos,
-                                              pad_token_id=pad_token_id if eos else None, generator=generator,
-                                              use_graph=bool(kwargs.get("use_graph", True)), trace=kwargs.get("trace"),
-                                              repetition_penalty=penalty, prompt_ids=None if input_embeddings is not None else input_ids.to(dev),
-                                              return_logprobs=bool(return_logprobs))
-            out = res[0]
+            out, _, _, logp = self._decode_text_on_device(
+                prompt, max_new_tokens, det, key_valid=key_valid, sampling=sampling, stop=eos, pad_token_id=pad_token_id if eos else None,
+                generator=generator, use_graph=bool(kwargs.get("use_graph", True)), trace=kwargs.get("trace"), repetition_penalty=penalty,
+                prompt_ids=None if input_embeddings is not None else input_ids.to(dev), return_logprobs=bool(return_logprobs))
             seqs = torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
-            return (seqs, res[3]) if return_logprobs else seqs
+            return (seqs, logp) if return_logprobs else seqs
         st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, key_valid)
         eng.check_errors()
@@ -1097,8 +1023,8 @@ class UniGen(ModelMixin, ConfigMixin):
     def _decode_text_on_device(self, prompt, max_new_tokens, det, key_valid=None, mask_bits=None, sampling=None, stop=(), pad_token_id=None,
                                generator=None, use_graph=True, trace=None, repetition_penalty=1.0, prompt_ids=None, return_logprobs=False):
         """The token loop of `text_token_loop` + `emit_until_stop` with nothing but launches per token: prefill, token 0 eagerly from
-        the prefill's hidden state (GEMV head + pick), step 1 eagerly (warm-up), step 2 captured (its first replay IS step 2), replays
-        from there.  The pick launch applies the stop rule on the device; with stop ids the host reads `remaining` every 8 tokens and
+        the prefill's hidden state (GEMV head + pick), then unigen_hip/qwen2.py: decode_loop (step 1 eagerly, step 2 captured, replays
+        from there).  The pick launch applies the stop rule on the device; with stop ids the host reads `remaining` every 8 tokens and
         stops replaying at zero.  The result is cut at `steps_used` (the step at which the last row finished), else at
         max_new_tokens: rows that overshoot a poll interval emit pad ids / have their lengths set exactly as the host loop's rows,
         so the cut result is the host loop's.  No decode step follows the last token.
@@ -1111,9 +1037,9 @@ class UniGen(ModelMixin, ConfigMixin):
         `seen` bitmap is zeroed here and takes prompt_ids [R, L] (None: no ids) at the positions key_valid marks real, one launch
         outside the captured step.  p == 1 allocates and launches nothing.
         return_logprobs: the session owns a log-probability buffer and its pick launches are the entry points that fill it (part of the
-        session key: such a call never replays the graph of a call without it, nor the reverse); a fourth result, fp32 [R, steps].
-        -> (tokens int64 [R, steps], lengths int64 [R], steps)."""
-        from unigen_hip.qwen2 import TextDecodeSession
+        session key: such a call never replays the graph of a call without it, nor the reverse).
+        -> (tokens int64 [R, steps], lengths int64 [R], steps, log-probabilities fp32 [R, steps] or None)."""
+        from unigen_hip.qwen2 import TextDecodeSession, decode_loop, put_session, take_session
         eng = self.llm.engine
         dev = eng.device
         R, L, _ = prompt.shape
@@ -1125,18 +1051,12 @@ class UniGen(ModelMixin, ConfigMixin):
             raise UniGenHipError(f"on-device sampling needs temperature > 0, top_k >= 0 and 0 < top_p <= 1 (got {sampling})")
         cap, width = ops.round_up(L + n, 128), ops.round_up(n, 64)
         pad = None if pad_token_id is None else int(pad_token_id)
-        n_layers = eng.dims.num_hidden_layers
         penalty = float(repetition_penalty)
-        key = (R, cap, width, V, eng.decode_form(R, det), det, sampling, penalty, tuple(stop), pad, key_valid is None, str(dev),
-               eng.fp.w("embed").data_ptr(), eng.fp.w("l0.wqkv").data_ptr(), eng.fp.p("embed").data_ptr(), eng.fp.p("norm").data_ptr(),
-               eng.fp.w(f"l{n_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in eng.rope(cap)))
+        key = (R, cap, width, V, eng.decode_form(R, det), det, sampling, penalty, tuple(stop), pad, key_valid is None,
+               str(dev)) + eng.storage_key(cap)
         if return_logprobs:
             key += ("logprobs",)
-        keep = use_graph and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0"
-        sess = getattr(eng, "_text_session", None) if keep else None
-        if sess is not None and sess.key != key:
-            sess = None
-        eng._text_session = None                     # (put back at the end of a call that completed)
+        sess = take_session(eng, "_text_session", key, use_graph)
         if sess is None:
             sess = TextDecodeSession(eng, R, cap, width, V, deterministic=det, sampling=sampling, stop_ids=stop, pad_id=pad, key_valid=key_valid,
                                      repetition_penalty=penalty, logprobs=bool(return_logprobs))
@@ -1150,31 +1070,16 @@ class UniGen(ModelMixin, ConfigMixin):
         hn = eng.prefill(sess.st, prompt, key_valid, mask_bits=mask_bits)
         eng.check_errors()
         eng.text_first_token(sess, hn, trace)
-        emitted = 1
-        while emitted < n:
-            if stop and emitted % 8 == 0 and int(sess.state[1]) == 0:          # (the one host read per 8 tokens)
-                break
-            if sess.graph is None and use_graph and emitted == 2:
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    eng.text_step(sess)
-                sess.graph = graph
-                eng.text_graph_captures = getattr(eng, "text_graph_captures", 0) + 1
-                graph.replay()                       # capture only records: this replay IS step 2
-            elif sess.graph is not None:
-                sess.graph.replay()
-            else:
-                eng.text_step(sess, trace)
-            emitted += 1
+        done = (lambda emitted: emitted % 8 == 0 and int(sess.state[1]) == 0) if stop else None    # (the one host read per 8 tokens)
+        if decode_loop(sess, lambda: eng.text_step(sess, trace), range(1, n), use_graph, stop=done):
+            eng.text_graph_captures = getattr(eng, "text_graph_captures", 0) + 1
         used = int(sess.state[2]) if stop else 0
         steps = used if used > 0 else n
         eng.last_decode_graph = sess.graph is not None
         tokens, lengths = sess.out_tokens[:, :steps].long(), sess.lengths.long()       # (copies: the next call overwrites the session's)
         logp = sess.logp[:, :steps].clone() if return_logprobs else None
-        if keep and sess.graph is not None:
-            eng._text_session = sess
-        return (tokens, lengths, steps, logp) if return_logprobs else (tokens, lengths, steps)
+        put_session(eng, "_text_session", sess, use_graph)
+        return tokens, lengths, steps, logp
 
     def _decode_text(self, st, hn, max_new_tokens, pick, emit):
         """text_token_loop on this model's engine from a prefilled state: vocabulary logits, embedding table, decode_step."""
@@ -1187,9 +1092,9 @@ class UniGen(ModelMixin, ConfigMixin):
     def _mmu_decode(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det, on_device=False,
                     use_graph=True, repetition_penalty=1.0, trace=None, return_logprobs=False):
         """Prefill R left-padded rows under their dense [R, 1, L, L] masks, then decode -> (tokens [R, max_new_tokens] on the device,
-        the rows' lengths cut after `eot_token` [R], the number of steps taken).  repetition_penalty: the prompt ids are `idx` (when the
-        prompt is not given as embeddings) at the keys the prompt's last row sees.  return_logprobs: a fourth result, the tokens'
-        log-probabilities fp32 [R, max_new_tokens] (0.0 behind a row's `eot_token` and behind the last step taken)."""
+        the rows' lengths cut after `eot_token` [R], the number of steps taken, and with return_logprobs the tokens' log-probabilities fp32
+        [R, max_new_tokens] (0.0 behind a row's `eot_token` and behind the last step taken), else None).  repetition_penalty: the prompt
+        ids are `idx` (when the prompt is not given as embeddings) at the keys the prompt's last row sees."""
         from unigen_hip.qwen2 import DecodeState
         from .sampling import seen_mask_of
         eng = self.llm.engine
@@ -1201,17 +1106,15 @@ class UniGen(ModelMixin, ConfigMixin):
         key_valid = attention_mask[:, 0, -1, :] == 0
         if on_device:
             sampling = (float(temperature), int(top_k or 0), 1.0) if temperature > 0 else None
-            res = self._decode_text_on_device(prompt, max_new_tokens, det, key_valid=key_valid, mask_bits=mb, sampling=sampling,
-                                              stop=self._stop_list(eot_token), use_graph=use_graph, trace=trace,
-                                              repetition_penalty=repetition_penalty,
-                                              prompt_ids=idx if input_embeddings is None else None, return_logprobs=return_logprobs)
-            tokens, lengths, steps = res[:3]
-            logp = res[3] if return_logprobs else None
+            tokens, lengths, steps, logp = self._decode_text_on_device(
+                prompt, max_new_tokens, det, key_valid=key_valid, mask_bits=mb, sampling=sampling, stop=self._stop_list(eot_token),
+                use_graph=use_graph, trace=trace, repetition_penalty=repetition_penalty,
+                prompt_ids=idx if input_embeddings is None else None, return_logprobs=return_logprobs)
             if steps < max_new_tokens:              # (the host loop's shapes: the buffer is max_new_tokens wide)
                 tokens = torch.cat([tokens, tokens.new_zeros((R, max_new_tokens - steps))], dim=1)
                 if return_logprobs:
                     logp = torch.cat([logp, logp.new_zeros((R, max_new_tokens - steps))], dim=1)
-            return (tokens, lengths, steps, logp) if return_logprobs else (tokens, lengths, steps)
+            return tokens, lengths, steps, logp
         st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
         hn = eng.prefill(st, prompt, mask_bits=mb)
         tokens = torch.zeros((R, max_new_tokens), dtype=torch.long, device=dev)
@@ -1226,7 +1129,7 @@ class UniGen(ModelMixin, ConfigMixin):
             seen = seen_mask_of(idx if input_embeddings is None else None, key_valid, R, self.config.vocab_size, dev)
             pick, emit = with_repetition_penalty(pick, emit, repetition_penalty, seen)
         steps = self._decode_text(st, hn, max_new_tokens, pick, emit)
-        return (tokens, lengths, steps, logp) if return_logprobs else (tokens, lengths, steps)
+        return tokens, lengths, steps, logp
 
     @torch.no_grad()
     def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False,
@@ -1234,11 +1137,10 @@ class UniGen(ModelMixin, ConfigMixin):
         """The one-row case of the batch path -> list of 0-d device tensors (one row: it ends at its `eot_token`, so every step counts);
         return_logprobs: (that list, the tokens' log-probabilities fp32 [steps])."""
         L = attention_mask.shape[-1]
-        res = self._mmu_decode(idx, input_embeddings, attention_mask.reshape(1, 1, L, L), max_new_tokens, temperature, top_k,
-                               eot_token, det, on_device=on_device, use_graph=use_graph, repetition_penalty=repetition_penalty,
-                               trace=trace, return_logprobs=return_logprobs)
-        tokens, steps = res[0], res[2]
-        return (list(tokens[0, :steps]), res[3][0, :steps].clone()) if return_logprobs else list(tokens[0, :steps])
+        tokens, _, steps, logp = self._mmu_decode(idx, input_embeddings, attention_mask.reshape(1, 1, L, L), max_new_tokens, temperature, top_k,
+                                                  eot_token, det, on_device=on_device, use_graph=use_graph,
+                                                  repetition_penalty=repetition_penalty, trace=trace, return_logprobs=return_logprobs)
+        return (list(tokens[0, :steps]), logp[0, :steps].clone()) if return_logprobs else list(tokens[0, :steps])
 
     @torch.no_grad()
     def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=0.0,
@@ -1267,13 +1169,13 @@ class UniGen(ModelMixin, ConfigMixin):
             raise ValueError("mmu_generate_batch: attention_mask must be the rows' dense [R, 1, L, L] additive masks")
         dev_loop = self._text_on_device(on_device, "mmu_generate_batch", R, True, eot_token, max_new_tokens)
         self.llm.engine.last_text_decode_on_device = dev_loop
-        res = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
-                               on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace,
-                               return_logprobs=bool(return_logprobs))
-        tokens, lengths = res[0].cpu(), res[1].cpu()
+        tokens, lengths, _, logp = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
+                                                    on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace,
+                                                    return_logprobs=bool(return_logprobs))
+        tokens, lengths = tokens.cpu(), lengths.cpu()
         lists = [list(tokens[r, :int(lengths[r])]) for r in range(R)]
         if return_logprobs:
-            return lists, [res[3][r, :int(lengths[r])].clone() for r in range(R)]
+            return lists, [logp[r, :int(lengths[r])].clone() for r in range(R)]
         return lists
 
     def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token):

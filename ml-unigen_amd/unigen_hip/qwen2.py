@@ -292,8 +292,104 @@ class TextDecodeSession:
                 ops.text_seen_mark_(self.seen, prompt_ids, self.V, prompt_valid)
 
 
+class ArDecodeSession:
+    """Everything an AR image decode step reads or writes, kept across `t2i_generate_ar` calls with the captured step: the decode state
+    (KV cache of prefix + steps positions), the next input `x` (static: next token's embedding), the last sampled token `tok`, the token
+    buffer [bsz, steps], and the constants the sampler launch takes as kernel arguments (rows = conditional then unconditional,
+    vocabulary slice [code_lo, code_lo + V), CFG scale, temperature, greedy, filt = None or (top_k, top_p, min_p)).
+    fused: the head's raw fp32 accumulator `acc_head` [rows, V] (the sampler launch leaves it zeroed) and, unless greedy, the
+    `uniforms` [steps, bsz] of the call, drawn from `generator` up front.  Not fused (the host sampler, UniGen._ar_host_token): neither.
+    logprobs: `logp` fp32 [bsz, steps, 2] = (logprobs, cond_logprobs) of every token, written by the sampler launch (fused) or copied
+    per step from `lp_now` [bsz, 2], the host sampler's pair of the step."""
+
+    def __init__(self, eng, rows, bsz, prefix_len, steps, V, code_lo, guidance_scale, temperature, greedy=False, filt=None, deterministic=False,
+                 key_valid=None, generator=None, logprobs=False, fused=True):
+        dev = eng.device
+        self.fused = fused
+        self.bsz, self.P, self.n, self.V, self.code_lo = bsz, prefix_len, steps, V, code_lo
+        self.guidance_scale, self.temperature, self.greedy, self.filt = guidance_scale, temperature, greedy, filt
+        self.form = eng.decode_form(rows, deterministic)
+        self.st = DecodeState(eng.dims, rows, prefix_len + steps, dev, key_valid=key_valid, deterministic=deterministic)
+        self.out_tokens = torch.zeros((bsz, steps), dtype=torch.int, device=dev)
+        self.x = torch.empty((rows, eng.dims.hidden_size), dtype=torch.float32, device=dev)
+        self.tok = torch.zeros((bsz, 1), dtype=torch.long, device=dev)
+        self.logp = torch.zeros((bsz, steps, 2), dtype=torch.float32, device=dev) if logprobs else None
+        self.uniforms = self.draw_uniforms(generator)
+        self.acc_head = torch.zeros((rows, V), dtype=torch.float32, device=dev) if fused else None
+        self.lp_now = torch.zeros((bsz, 2), dtype=torch.float32, device=dev) if logprobs and not fused else None
+        self.graph, self.key = None, None
+
+    def draw_uniforms(self, generator):
+        """the call's uniforms for the fused sampler's inverse-CDF draw, on the generator's device (default: the engine's) and then
+        here: once per call, ahead of the prefill; None when greedy or not fused (the host sampler draws by itself)"""
+        if self.greedy or not self.fused:
+            return None
+        dev = self.st.pos.device
+        return torch.rand((self.n, self.bsz), device=dev if generator is None else generator.device, generator=generator).to(dev)
+
+    def begin(self, key_valid=None, generator=None):
+        """what a reused session needs at a call's start: the new prompt's key-validity columns and the call's uniforms in the buffer
+        the graph reads.  The prefill sets position and length."""
+        if key_valid is not None:
+            self.st.key_valid[:, :self.P].copy_(key_valid)
+        if self.uniforms is not None:
+            self.uniforms.copy_(self.draw_uniforms(generator))
+
+
+def _keeping(wanted):
+    """the keep policy of both decode sessions: a call that asks for it keeps its session unless UNIGEN_AR_GRAPH_CACHE=0"""
+    return bool(wanted) and os.environ.get("UNIGEN_AR_GRAPH_CACHE", "1") != "0"
+
+
+def take_session(eng, attr, key, wanted):
+    """The session kept on eng.<attr> if this call may reuse one and `key` is its key, else None.  The attribute is cleared either
+    way: put_session puts the session back at the end of a call that completed, so a call that raises leaves none."""
+    sess = getattr(eng, attr, None) if _keeping(wanted) else None
+    setattr(eng, attr, None)
+    return sess if sess is not None and sess.key == key else None
+
+
+def put_session(eng, attr, sess, wanted):
+    """at the end of a completed call: keep the session if it has a captured step -> whether it was kept (the results then have to be
+    copies: the next call overwrites the session's buffers)"""
+    kept = _keeping(wanted) and sess.graph is not None
+    if kept:
+        setattr(eng, attr, sess)
+    return kept
+
+
+def decode_loop(sess, step, steps, use_graph, stop=None, mark=None, after=None):
+    """The token loop of both on-device decodes behind the first token: for every i of `steps` (1, 2, ...), `step()` eagerly, except
+    that with use_graph step 1 alone runs eagerly (warm-up: allocations, lazy inits), step 2 is captured into sess.graph -- capture
+    only records, so its first replay IS step 2 -- and every later step, and every step of a session that comes with a graph, is a
+    replay.  stop(i), asked before step i, ends the loop early; after(i) runs behind step i, outside the captured step; mark(name)
+    closes the timing phases eager_step / capture / replay.  -> whether this call captured."""
+    mark = mark or (lambda name: None)
+    captured = False
+    for i in steps:
+        if stop is not None and stop(i):
+            break
+        if sess.graph is None and use_graph and i == 2:
+            mark("eager_step")
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                step()
+            sess.graph, captured = graph, True
+            mark("capture")
+            graph.replay()
+        elif sess.graph is not None:
+            sess.graph.replay()
+        else:
+            step()
+        if after is not None:
+            after(i)
+    mark("replay")
+    return captured
+
+
 class _Saved:
-    __slots__ = ("h", "rstd1", "xn1", "qkv", "o", "lse", "h_mid", "rstd2", "xn2", "gu", "act")
+    __slots__ =("h", "rstd1", "xn1", "qkv", "o", "lse", "h_mid", "rstd2", "xn2", "gu", "act")
 
 
 class Qwen2Engine:
@@ -688,6 +784,62 @@ class Qwen2Engine:
         ops.decode_sw_head_(stream, fp.p("norm"), d.rms_norm_eps, w_head, logits, pend=pending, advance=(st.pos, st.len))
         return logits
 
+    def decode_step_head(self, form, st, x, w_head, logits):
+        """One decode step on (st, x) that leaves the fp32 head logits for the rows `w_head` of the tied embedding in `logits`; advances
+        the cache position.  The ONE statement of which layer forms end in a head launch: sw, ord_sw and ord_wide do
+        (decode_step_logits); splitk and wide run decode_step and the atomic GEMV head, which ADDS into `logits` -- the consumer
+        (sampler or pick launch) leaves it zeroed."""
+        if form in ("splitk", "wide"):
+            return ops.decode_gemv_(self.decode_step(st, x), w_head, logits)
+        return self.decode_step_logits(st, x, w_head, logits)
+
+    def first_head(self, st, hn, w_head, logits):
+        """The first token's head, from the prefill's final-norm hidden state: the ordered skinny linear on a deterministic state, else
+        the atomic GEMV, which adds into `logits` (zeroed by the caller or left zeroed by the previous sampler launch)."""
+        if st.deterministic:
+            return ops.skinny_linear_ord(hn, w_head, out_f32=logits)
+        return ops.decode_gemv_(hn, w_head, logits)
+
+    def storage_key(self, capacity):
+        """What both decode sessions' keys end in, standing for "the weights were not reallocated": every pointer a captured step bakes
+        in lives in the two flat buffers, so their first tensors, the last layer's weights and the RoPE tables for `capacity` serve."""
+        fp = self.fp
+        return (fp.w("embed").data_ptr(), fp.w("l0.wqkv").data_ptr(), fp.p("embed").data_ptr(), fp.p("norm").data_ptr(),
+                fp.w(f"l{self.dims.num_hidden_layers - 1}.wdown").data_ptr(), tuple(t.data_ptr() for t in self.rope(capacity)))
+
+    # ---- AR image decode on the device: head slice into a raw accumulator + ONE sampler launch per token (CFG mix, temperature,
+    # softmax, truncation, inverse-CDF draw on the call's uniforms, log-probabilities, next input embedding)
+    def ar_draw(self, sess):
+        """the sampler launch of an AR step on sess.acc_head (include/unigen_hip.h: ug_ar_sample / ug_ar_sample_filtered and their
+        _logp entry points); leaves the accumulator zeroed"""
+        args = (sess.acc_head, sess.bsz, sess.V, sess.guidance_scale, sess.temperature, sess.greedy, sess.uniforms, sess.st.pos, sess.P,
+                sess.n, self.fp.p("embed"), sess.code_lo, sess.tok, sess.out_tokens, sess.x)
+        if sess.filt is None:
+            ops.ar_sample_(*args, logp=sess.logp)
+        else:
+            ops.ar_sample_filtered_(*args, top_k=sess.filt[0], top_p=sess.filt[1], min_p=sess.filt[2], logp=sess.logp)
+
+    def _ar_head_rows(self, sess):
+        return self.fp.w("embed")[sess.code_lo:sess.code_lo + sess.V]
+
+    def _ar_trace(self, sess, trace):
+        # parity tests follow the head's raw logits step by step (eager runs only)
+        if trace is not None and not torch.cuda.is_current_stream_capturing():
+            trace.append(sess.acc_head.clone())
+
+    def ar_first_token(self, sess, hn, trace=None):
+        """token 0 from the prefill's final-norm hidden state: first_head into the accumulator + the sampler launch"""
+        self.first_head(sess.st, hn, self._ar_head_rows(sess), sess.acc_head)
+        self._ar_trace(sess, trace)
+        self.ar_draw(sess)
+
+    def ar_step(self, sess, trace=None):
+        """One AR decode step into the session's static buffers: decode_step_head on sess.x into the accumulator, then the sampler
+        launch (token, record, next sess.x).  No host sync, no shape depends on the step: capturable."""
+        self.decode_step_head(sess.form, sess.st, sess.x, self._ar_head_rows(sess), sess.acc_head)
+        self._ar_trace(sess, trace)
+        self.ar_draw(sess)
+
     # ---- text decode on the device: head + pick over the whole vocabulary, the token loop's state in device memory
     def text_pick(self, sess):
         """the pick launch(es) of a text step on sess.logits (include/unigen_hip.h: ug_text_pick / ug_text_sample).  The atomic GEMV
@@ -712,12 +864,9 @@ class Qwen2Engine:
     def text_first_token(self, sess, hn, trace=None):
         """token 0 from the prefill's final-norm hidden state: the GEMV head (ordered in deterministic mode) + the logits processor +
         the pick.  trace takes the RAW head logits."""
-        w_head = self.fp.w("embed")[:sess.V]
-        if sess.st.deterministic:
-            ops.skinny_linear_ord(hn, w_head, out_f32=sess.logits)
-        else:
-            sess.logits.zero_()
-            ops.decode_gemv_(hn, w_head, sess.logits)
+        if not sess.st.deterministic:
+            sess.logits.zero_()                     # (the atomic GEMV adds into it)
+        self.first_head(sess.st, hn, self.fp.w("embed")[:sess.V], sess.logits)
         if trace is not None:
             trace.append(sess.logits[:, :sess.V].clone())
         self.text_penalize(sess, first=True)
@@ -726,13 +875,9 @@ class Qwen2Engine:
     def text_step(self, sess, trace=None):
         """One text decode step into the session's static buffers: the decoder stack on sess.x, the head over the whole vocabulary and
         the pick (token, stop rule, records, next sess.x), the session's logits processor between them; advances the cache position.  No host sync, no shape depends on the step:
-        capturable.  sw / ord_sw / ord_wide end in decode_step_logits' head launch; splitk and wide run decode_step and the atomic
-        GEMV head into the accumulator the pick leaves zeroed.  trace: optional list taking the step's raw head logits (eager runs only)."""
-        w_head = self.fp.w("embed")[:sess.V]
-        if sess.form in ("splitk", "wide"):
-            ops.decode_gemv_(self.decode_step(sess.st, sess.x), w_head, sess.logits)
-        else:
-            self.decode_step_logits(sess.st, sess.x, w_head, sess.logits)
+        capturable.  The head is decode_step_head's, into the logits the pick leaves zeroed where the form's head adds.  trace: optional
+        list taking the step's raw head logits (eager runs only)."""
+        self.decode_step_head(sess.form, sess.st, sess.x, self.fp.w("embed")[:sess.V], sess.logits)
         if trace is not None and not torch.cuda.is_current_stream_capturing():
             trace.append(sess.logits[:, :sess.V].clone())
         self.text_penalize(sess)

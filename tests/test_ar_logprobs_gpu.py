@@ -207,19 +207,19 @@ def test_ar_generation_logprobs_eager_graph_and_session(dev, setup, mode):
     # the captured step, then the kept session: the eager run's bits
     first = run(seed=11, use_graph=True, return_logprobs=True, **kw)
     sess = eng._ar_session
-    assert sess is not None and eng.last_decode_graph and sess["key"][-1] == "logprobs"
+    assert sess is not None and eng.last_decode_graph and sess.key[-1] == "logprobs"
     second = run(seed=11, use_graph=True, return_logprobs=True, **kw)
-    assert eng._ar_session["graph"] is sess["graph"]
+    assert eng._ar_session.graph is sess.graph
     for got in (first, second):
         assert torch.equal(got[0], tokens) and torch.equal(got[1], lp) and torch.equal(got[2], clp)
-    assert second[1].data_ptr() != eng._ar_session["logp"].data_ptr()            # clones: the next call overwrites the session's buffer
+    assert second[1].data_ptr() != eng._ar_session.logp.data_ptr()            # clones: the next call overwrites the session's buffer
     # a flag-off call in between takes no part in the flag-on session, and the next flag-on call still returns the same bits
     off = run(seed=11, use_graph=True, **kw)
     s_off = eng._ar_session
     assert torch.is_tensor(off) and torch.equal(off, tokens)
-    assert s_off["graph"] is not sess["graph"] and "logp" not in s_off and s_off["key"] == sess["key"][:-1]
+    assert s_off.graph is not sess.graph and s_off.logp is None and s_off.key == sess.key[:-1]
     third = run(seed=11, use_graph=True, return_logprobs=True, **kw)
-    assert eng._ar_session["graph"] is not s_off["graph"]
+    assert eng._ar_session.graph is not s_off.graph
     assert torch.equal(third[0], tokens) and torch.equal(third[1], lp) and torch.equal(third[2], clp)
     model.drop_decode_session()
 

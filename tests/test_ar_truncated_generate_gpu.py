@@ -67,14 +67,14 @@ def test_truncated_ar_generation_eager_graph_and_session(dev, setup, monkeypatch
     sess = eng._ar_session
     assert sess is not None and eng.last_decode_graph
     second = run(seed=11, use_graph=True, **kw)
-    assert eng._ar_session["graph"] is sess["graph"]
+    assert eng._ar_session.graph is sess.graph
     assert torch.equal(first, eager) and torch.equal(second, eager)
     # another filter constant: a new graph, and back again gives what a fresh capture gives
     run(seed=11, use_graph=True, deterministic=True, top_k=4, top_p=0.7)
     s4 = eng._ar_session
-    assert s4["graph"] is not sess["graph"]
+    assert s4.graph is not sess.graph
     back = run(seed=11, use_graph=True, **kw)
-    assert eng._ar_session["graph"] is not s4["graph"]
+    assert eng._ar_session.graph is not s4.graph
     kept = run(seed=11, use_graph=True, **kw)
     monkeypatch.setenv("UNIGEN_AR_GRAPH_CACHE", "0")
     fresh = run(seed=11, use_graph=True, **kw)

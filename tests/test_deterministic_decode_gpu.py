@@ -252,9 +252,9 @@ def test_ar_generation_deterministic_on_golden_g9(dev):
     assert eng.last_decode_deterministic and not eng.last_decode_graph
     captured = run(deterministic=True)
     sess = eng._ar_session
-    assert sess is not None and sess["st"].deterministic and eng.last_decode_graph
+    assert sess is not None and sess.st.deterministic and eng.last_decode_graph
     kept = run(deterministic=True)
-    assert eng._ar_session["graph"] is sess["graph"]
+    assert eng._ar_session.graph is sess.graph
     assert torch.equal(eager, captured) and torch.equal(eager, kept)
     want, margin = ar["bf16"]["tokens"], ar["bf16"]["margin"]
     compared = 0
@@ -273,14 +273,14 @@ def test_ar_generation_deterministic_on_golden_g9(dev):
     try:
         torch.use_deterministic_algorithms(True, warn_only=True)
         run()
-        assert eng.last_decode_deterministic and eng._ar_session["st"].deterministic
-        det_graph = eng._ar_session["graph"]
+        assert eng.last_decode_deterministic and eng._ar_session.st.deterministic
+        det_graph = eng._ar_session.graph
         run(deterministic=False)
-        assert not eng.last_decode_deterministic and not eng._ar_session["st"].deterministic
-        assert eng._ar_session["graph"] is not det_graph
-        def_graph = eng._ar_session["graph"]
+        assert not eng.last_decode_deterministic and not eng._ar_session.st.deterministic
+        assert eng._ar_session.graph is not det_graph
+        def_graph = eng._ar_session.graph
         again = run(deterministic=None)
-        assert eng._ar_session["st"].deterministic and eng._ar_session["graph"] is not def_graph
+        assert eng._ar_session.st.deterministic and eng._ar_session.graph is not def_graph
         assert torch.equal(again, captured)
     finally:
         torch.use_deterministic_algorithms(was)

@@ -73,12 +73,12 @@ def test_ar_decode_session_is_reused_across_calls_and_never_stale(dev, monkeypat
     sess = eng._ar_session
     assert sess is not None
     again = run(ar["cond"], ar["uncond"], ar["attention_mask"], ar["scale"])
-    assert eng._ar_session["graph"] is sess["graph"] and torch.equal(first, again)
+    assert eng._ar_session.graph is sess.graph and torch.equal(first, again)
     # other prompts and another padding pattern through the SAME session vs a fresh capture of that call
     cond2, am2 = ar["cond"].flip(0).clone(), ar["attention_mask"].clone()
     am2[:, :3] = 0
     reused = run(cond2, ar["uncond"], am2, ar["scale"])
-    assert eng._ar_session["graph"] is sess["graph"]
+    assert eng._ar_session.graph is sess.graph
     monkeypatch.setenv("UNIGEN_AR_GRAPH_CACHE", "0")
     fresh = run(cond2, ar["uncond"], am2, ar["scale"])
     monkeypatch.delenv("UNIGEN_AR_GRAPH_CACHE")
@@ -89,11 +89,11 @@ def test_ar_decode_session_is_reused_across_calls_and_never_stale(dev, monkeypat
     s2 = eng._ar_session
     b = run(ar["cond"], ar["uncond"], ar["attention_mask"], ar["scale"], seed=6, greedy=False)
     c = run(ar["cond"], ar["uncond"], ar["attention_mask"], ar["scale"], seed=5, greedy=False)
-    assert eng._ar_session["graph"] is s2["graph"] and not torch.equal(a, b)
+    assert eng._ar_session.graph is s2.graph and not torch.equal(a, b)
     print(f"sampled tokens equal for equal seeds through a reused session: {(a == c).float().mean().item():.3f} of positions")
     # a sampling constant that is baked into a kernel argument: new session
     run(ar["cond"], ar["uncond"], ar["attention_mask"], ar["scale"] + 1.0)
-    assert eng._ar_session["graph"] is not s2["graph"]
+    assert eng._ar_session.graph is not s2.graph
     # round 6: the kept session -- KV cache, scratch, graph pool -- is released explicitly or on the way back to training
     model.drop_decode_session()
     assert eng._ar_session is None
@@ -102,6 +102,74 @@ def test_ar_decode_session_is_reused_across_calls_and_never_stale(dev, monkeypat
     model.train()
     assert eng._ar_session is None
     model.eval()
+
+
+def _ar_run(model, g, dev, **kw):
+    ar = g["ar"]
+    return model.t2i_generate_ar(input_ids=ar["cond"].to(dev), uncond_input_ids=ar["uncond"].to(dev), attention_mask=ar["attention_mask"].to(dev),
+                                 guidance_scale=ar["scale"], temperature=1.0, text_vocab_size=g["ids"]["text_vocab"],
+                                 image_token_num_per_image=ar["n"], greedy=True, **kw)
+
+
+def test_ar_and_text_sessions_do_not_disturb_each_other(dev):
+    """The AR session and the on-device text session live side by side on the engine: a text call between two AR calls leaves the AR
+    session's graph in place and its tokens as they were, and the other way round."""
+    g = golden("g9_generate.pt")
+    model = _model(g, dev, g["weight_std"])
+    eng = model.llm.engine
+    prompt = g["mmu"]["idx"].reshape(1, -1).to(dev)
+    first = _ar_run(model, g, dev)
+    graph = eng._ar_session.graph
+    assert graph is not None
+    text = model.generate(input_ids=prompt, max_new_tokens=6, on_device=True)
+    captures = eng.text_graph_captures
+    again = _ar_run(model, g, dev)
+    assert eng._ar_session.graph is graph and torch.equal(first, again) and eng._text_session is not None
+    text_sess = eng._text_session
+    text_again = model.generate(input_ids=prompt, max_new_tokens=6, on_device=True)
+    assert eng.last_decode_graph and eng._text_session is text_sess and eng.text_graph_captures == captures
+    assert text_again.shape == text.shape
+    model.drop_decode_session()
+
+
+def test_ar_call_that_raises_leaves_no_session_and_the_next_call_is_fresh(dev, monkeypatch):
+    """A call that fails part-way (here: a Python exception at step 1, ahead of that step's first launch and outside any capture) must
+    not leave its half-used session on the engine; the next call builds a fresh one and returns the completed call's tokens."""
+    g = golden("g9_generate.pt")
+    model = _model(g, dev, g["weight_std"])
+    eng = model.llm.engine
+    want = _ar_run(model, g, dev)
+    assert eng._ar_session is not None
+    model.drop_decode_session()
+
+    def broken(sess, trace=None):
+        raise RuntimeError("step refused by the test")
+    with monkeypatch.context() as mp:
+        mp.setattr(eng, "ar_step", broken)
+        with pytest.raises(RuntimeError, match="refused by the test"):
+            _ar_run(model, g, dev)
+        assert eng._ar_session is None
+    got = _ar_run(model, g, dev)
+    assert torch.equal(got, want) and eng._ar_session is not None and eng._ar_session.graph is not None
+    model.drop_decode_session()
+
+
+def test_ar_host_sampler_branch_runs_through_the_loop(dev):
+    """torch_sampler=True: the host sampler's step, captured (no generator) and eager, gives the same tokens and log-probabilities within
+    the tolerance of tests/test_ar_logprobs_gpu.py (two evaluations of one fp32 formula on the same bf16 head rows), and keeps no session."""
+    from test_ar_logprobs_gpu import TOL
+    g = golden("g9_generate.pt")
+    model = _model(g, dev, g["weight_std"])
+    eng = model.llm.engine
+    captured = _ar_run(model, g, dev, torch_sampler=True, return_logprobs=True, use_graph=True)
+    assert eng.last_decode_graph and eng._ar_session is None
+    eager = _ar_run(model, g, dev, torch_sampler=True, return_logprobs=True, use_graph=False)
+    assert not eng.last_decode_graph and eng._ar_session is None
+    assert torch.equal(captured[0], eager[0])
+    for a, b in zip(captured[1:], eager[1:]):
+        worst = float((a - b).abs().max())
+        print(f"host sampler, captured vs eager: worst log-probability difference {worst:.2e} (bar {TOL:.0e})")
+        assert a.shape == eager[0].shape and worst <= TOL
 
 
 def test_mmu_generate_matches_reference_trajectory(dev):
