@@ -60,7 +60,7 @@ int ug_gemm_bf16(const ug_handle* h, const void* A, int64_t lda, int a_kmajor, c
 /* h: the calling stream's handle (ug_create) or null.  The handle owns the fp32 scratch of the k-sliced launch forms
  * (partial last round of 256x256 tiles, small weight gradients, lm-head dgrad); without one those forms are not chosen.
  * One handle must not be used by two streams at once; any number of handles may run concurrently.
- * policy: -1 = automatic kernel selection (the product path); >= 0 pins a kernel for A/B benchmarks and tests:
+ * policy: (the rules themselves: ml-unigen_amd/csrc/gemm_plan.h, plan_gemm / decode_policy) -1 = automatic kernel selection (the product path); >= 0 pins a kernel for A/B benchmarks and tests:
  * 0 = 128x128 two LDS stages, 2 = 128x128 one LDS stage, 3 = staggered 256x256, 6 = 256x256 with the k-sliced tail forced,
  * 8 = k-sliced small outputs, 10 = 320x256 tiles (A row-major, N % 256 == 0, K % 32 == 0, bf16 / residual epilogue; other
  * launches ignore it), 44 ... 52 except 48 = the same kernel at a tile height of 16 * (policy - 32) = 192 ... 320 rows; UG_GEMM_POLICY_AUTO_BITS = automatic selection when only modifier bits are wanted;

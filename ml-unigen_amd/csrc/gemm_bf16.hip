@@ -10,7 +10,7 @@
 //   dgrad    dx = dy W        : A = dy  RowK, B = W  KRow   (W is [N_out][K_in] = [k][row])
 //   wgrad    dW = dy^T x      : A = dy  KRow, B = x  KRow   (contraction over tokens)
 //
-// Kernels in this file (the launcher picks per shape, see launch<>() and DESIGN.md section 4.1):
+// Kernels in this file (gemm_plan.h picks per shape: plan_gemm / plan_fused):
 //   gemm_kernel             128x128 tiles, 4 waves, 1-2 LDS stages: small / ragged problems
 //   gemm_kernel_p8          256x256 tiles, 8 waves in two groups that alternate fragment reads (L) and MFMAs (M), 4-stage
 //                           LDS-DMA ring; two barriers per k-tile (forward, dgrad) or one (weight gradients); k-sliced forms
@@ -45,17 +45,16 @@
 #include <atomic>
 #include "unigen_hip.h"
 #include "vmem_asm.h"
+#include "gemm_plan.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
+using namespace ug_plan;          // tile shapes (BM ... QBM), enum Epi, and the kernel selection itself: gemm_plan.h
 constexpr int TILE_BYTES = BM * BK * 2;   // 16 KiB per operand tile (either layout)
 constexpr int GROUP_M = 8;
 constexpr int P8_GROUP_M = 4;    // row panels per column sweep of the 256-wide kernels: the four 786 KB A panels of a
                                              // K = 1536 launch stay in an XCD's 4 MB L2 while its 32 workgroups walk the columns
                                              // (8: 8192^3 1325 -> 1385, gate_up forward / weight gradients +1..2 %)
-
-enum Epi { EPI_BF16 = 0, EPI_F32 = 1, EPI_RESID = 2, EPI_ROPE = 3, EPI_SWIGLU = 4, EPI_SWIGLU_BWD = 5 };    // EPI_ROPE: EPI_BF16 + rotate-half RoPE on the first rope_cols columns (128...320-row kernel only)
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -562,7 +561,6 @@ __global__ __launch_bounds__(256, DBUF ? 2 : 4) void gemm_kernel(GemmArgs p) {
 // is never more than a counted `s_waitcnt vmcnt(8)` away (two newer DMA batches stay in flight).
 // Ring safety: tile t is read in intervals 2t (group 0) and 2t+1 (group 1); its stage is refilled
 // with tile t+4, issued no earlier than interval 2t+2 (inside L(t+1)).
-constexpr int PBM = 256, PBN = 256, PBK = 32;
 constexpr int P_TILE = PBM * PBK * 2;          // 16 KiB per operand per stage
 constexpr int P_STAGE = 2 * P_TILE;            // 32 KiB
 constexpr int P_NST = 4;
@@ -882,7 +880,6 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_p8_wgrad_group(GroupArgs g
 // N % 256 == 0, bf16 / residual epilogues through the LDS strips, no k-slices.  The 20 A instructions of a k-tile go two
 // per wave plus a third for the waves of group 0, so the counted waits are per group (5 / 4 DMA instructions per tile).
 constexpr int P10_GROUP_M = 4;
-constexpr int QBM = 320;
 constexpr int Q_TILE_A = QBM * PBK * 2;        // 20 KiB
 constexpr int Q_STAGE = Q_TILE_A + P_TILE;     // 36 KiB; four stages = 144 KiB
 
@@ -1043,159 +1040,81 @@ __global__ __launch_bounds__(256) void tail_finish_kernel(GemmArgs p, int ntail)
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------ host side
+// Which kernel runs is decided in gemm_plan.h (plan_gemm / plan_fused: pure functions, tested on the CPU against recorded
+// decisions); the code below checks arguments, fills GemmArgs and launches what the plan says.
+//
 // Scratch of the k-sliced tiles: WS_PRIVATE_SLOTS slots of 256 KiB for private partials (192 MiB: room for 3 rounds of
 // k-slices).  It belongs to a ug_handle (ug_create / ug_destroy, runtime.hip): nothing on the op path allocates, clears or
 // synchronises, and two streams that each use their own handle never share partials.  A launch without a handle simply
 // does not use the k-sliced forms.
-constexpr int WS_PRIVATE_SLOTS = UG_HANDLE_WS_SLOTS;
+static_assert(WS_PRIVATE_SLOTS == UG_HANDLE_WS_SLOTS && POLICY_NARROW_EPILOGUE == UG_GEMM_NARROW_EPILOGUE && POLICY_ONE_BARRIER == UG_GEMM_ONE_BARRIER &&
+              POLICY_TWO_BARRIERS == UG_GEMM_TWO_BARRIERS && POLICY_AUTO_BITS == UG_GEMM_POLICY_AUTO_BITS, "gemm_plan.h restates these");
+
+bool env_switch_on(const char* name) { const char* v = getenv(name); return !(v && atoi(v) == 0); }      // A/B switches: on unless set to 0
+
+// gemm_kernel_p10 at `height` rows: the height list of an epilogue (gemm_plan.h: P10Heights) expands into exactly the kernels that
+// epilogue instantiates.  False: the list does not hold the height (nothing was launched).
+template <int EPI, bool BKM, int H>
+bool launch_p10_height(int height, dim3 grid, const GemmArgs& a, hipStream_t st) {
+  if (height != H) return false;
+  hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, p10_f0(H), p10_f1(H)>), grid, dim3(512), 0, st, a);
+  return true;
+}
+template <int EPI, bool BKM, int... H>
+bool launch_p10(HeightList<H...>, int height, dim3 grid, const GemmArgs& a, hipStream_t st) {
+  return (launch_p10_height<EPI, BKM, H>(height, grid, a, st) || ...);
+}
 
 template <int EPI, bool AK, bool BKM>
-int launch(GemmArgs a, const ug_handle* h, int policy, hipStream_t st) {
-  float* const ws = (h && h->tail_ws) ? h->tail_ws : nullptr;          // k-sliced forms need a handle's scratch
-  const int g_tile_policy = policy;                                    // per call: -1 auto, see ug_gemm_bf16 in the header
-  const int tiles = a.tiles_m * a.tiles_n;
-  int splits = 1;
-  if (EPI == EPI_F32 && a.beta == 1 && tiles < 384) {            // wgrad of a small weight: fill the chip along K
-    const int nk = (a.K + BK - 1) / BK;
-    splits = min(32, max(1, 768 / tiles));                         // skinny decode GEMMs (M = 16) get up to 32 slices
-    splits = max(1, min(splits, nk / 2));
-  }
-  // Staggered 256x256 kernel when its one-workgroup-per-CU grid quantises well (measured, tools/gemm_bench.py:
-  // +8..17 % on the wide shapes; the 294-tile N=1536 shapes lose a half-empty second round and stay on 128x128).
-  const int tiles_p8 = ((a.M + PBM - 1) / PBM) * ((a.N + PBN - 1) / PBN);
-  const int rounds = (tiles_p8 + 255) / 256;
-  const bool p8_fits = (tiles_p8 <= 256) ? (tiles_p8 >= 200) : (4 * tiles_p8 >= 3 * rounds * 256);
-  // token-count x 1536 outputs (o / down forward, qkv / o / gate_up dgrad): one round of 320 x 256 tiles instead of 1.15 rounds
-  // of 256 x 256 -- also ahead of the k-sliced tail where the contraction is long (down forward 954 -> 1065, gate_up dgrad
-  // 1188 -> 1354 TF/s)
-  if constexpr (!AK && EPI != EPI_F32) {
-    const int tiles_q = ((a.M + QBM - 1) / QBM) * (a.N / PBN);
-    const bool aligned = a.N % PBN == 0 && a.K % PBK == 0 &&
-                         (EPI == EPI_BF16 ? (a.ldc % 8 == 0 && (!a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 7) == 0))
-                                          : (a.ldc % 4 == 0 && a.ldr % 4 == 0));
-    // many rounds: a 320-row tile costs 1.25 x a 256-row one and runs ~7 % more efficiently (fewer LDS and DMA bytes per MFMA);
-    // taken when whole rounds come out at least 3 % cheaper (gate_up forward: 14 rounds -> 11 x 1.16 = 12.8: 1240 -> 1322 TF/s)
-    const bool fewer_rounds = tiles_p8 >= 1024 && 1.1625f * (float)((tiles_q + 255) / 256) < 0.97f * (float)((tiles_p8 + 255) / 256);
-    // Round 4: the same comparison over every tile height -- rounds(h) x t(h), t(h) = 0.35 + 0.00254 h in units of a 256-row tile
-    // (from the two measured points t(256) = 1, t(320) = 1.1625).  down dgrad (12 336 x 8 960): 288 rows = 6 rounds x 1.08 against 7
-    // rounds of 256 (286 -> 255 us); 9 288 rows: 272; gate_up forward keeps 320 at 12 336 rows and takes 304 at 9 288
-    // (tools/gemm_shape_sweep.py agrees with the model's ranking on every shape it changes).
-    int hb_multi = 0;
-    // One-round launches (round 4): a round takes as long as one tile, so the SMALLEST tile height whose row tiles x column tiles
-    // still fit the 256 CUs wins -- 12 336 x 1 536 outputs: 304 rows (246 workgroups) instead of 320 (234); 9 288 rows: 224.
-    int hb = 0;
-    static const bool heights_on = !(getenv("UNIGEN_GEMM_HEIGHTS") && atoi(getenv("UNIGEN_GEMM_HEIGHTS")) == 0);   // A/B switch
-    if (aligned && g_tile_policy < 0 && a.N / PBN >= 1 && a.N / PBN <= 64) {
-      static const int heights[] = {128, 144, 160, 176, 192, 208, 224, 240, 256, 272, 288, 304, 320};
-      for (int h_ : heights) {
-        if (!heights_on && h_ != QBM) continue;                  // (round 3's choice: 320 rows or nothing)
-        const int64_t wgs = (int64_t)((a.M + h_ - 1) / h_) * (a.N / PBN);
-        // (measured down to 78 workgroups: tools/gemm_shape_sweep.py at M = 1 542.)  Few workgroups AND a very long contraction
-        // (an lm-head dgrad whose vocabulary is a multiple of 32: >= 2048 k-tiles on < 200 CUs) stay with the k-sliced form
-        // below, which cuts every tile along K over the whole chip (measured 632 -> 1 094 TF/s at 174 tiles, K = 159 867)
-        if (wgs <= 256) { if (wgs >= 64 && !(a.K / PBK >= 2048 && wgs < 200)) hb = h_; break; }
-      }
-      if (hb == 256 && p8_fits) hb = 0;                          // (the 256 x 256 kernel's own one-round case)
-    }
-    if (aligned && g_tile_policy < 0 && heights_on && hb == 0 && tiles_p8 >= 768) {
-      static const int mheights[] = {176, 192, 208, 224, 240, 272, 288, 304, 320};
-      float best = 0.97f * (float)((tiles_p8 + 255) / 256);
-      for (int h_ : mheights) {
-        const int64_t wgs = (int64_t)((a.M + h_ - 1) / h_) * (a.N / PBN);
-        const float cost = (float)((wgs + 255) / 256) * (0.35f + 0.00254f * (float)h_);
-        if (cost < best) { best = cost; hb_multi = h_; }
+int run_plan(const GemmPlan& pl, GemmArgs a, hipStream_t st) {       // a.tail_ws: the handle's scratch or null
+  a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n;
+  a.full_tiles = pl.full_tiles; a.tail_split = pl.tail_split; a.tail_private = pl.tail_private;
+  if (!pl.uses_workspace) a.tail_ws = nullptr;
+  const dim3 grid(pl.grid_x, pl.grid_y);
+  if (pl.kind == KIND_P10) {
+    if constexpr (!AK && EPI != EPI_F32) {
+      if (launch_p10<EPI, BKM>(typename P10Heights<EPI>::type{}, pl.height, grid, a, st)) {
+        UG_CHECK_LAUNCH("ug_gemm_bf16(p10)");
+        return UG_OK;
       }
     }
-    if (aligned && g_tile_policy >= 40 && g_tile_policy <= 52 && g_tile_policy != 48) hb = 16 * (g_tile_policy - 32);   // forced height (tests, A/B)
-    if (hb == 0 && hb_multi != 0) hb = hb_multi;
-    if (hb == 0 && aligned && (g_tile_policy == 10 || (g_tile_policy < 0 && !heights_on && fewer_rounds))) hb = QBM;
-    if (hb != 0) {
-      a.tiles_m = (a.M + hb - 1) / hb; a.tiles_n = a.N / PBN;
-      const dim3 grid(a.tiles_m * a.tiles_n), block(512);
-      switch (hb) {
-        case 320: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 10, 10>), grid, block, 0, st, a); break;
-        case 304: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 10, 9>), grid, block, 0, st, a); break;
-        case 288: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 9, 9>), grid, block, 0, st, a); break;
-        case 272: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 9, 8>), grid, block, 0, st, a); break;
-        case 256: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 8, 8>), grid, block, 0, st, a); break;
-        case 240: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 8, 7>), grid, block, 0, st, a); break;
-        case 224: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 7, 7>), grid, block, 0, st, a); break;
-        case 208: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 7, 6>), grid, block, 0, st, a); break;
-        case 192: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 6, 6>), grid, block, 0, st, a); break;
-        case 176: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 6, 5>), grid, block, 0, st, a); break;
-        case 160: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 5, 5>), grid, block, 0, st, a); break;
-        case 144: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 5, 4>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((gemm_kernel_p10<EPI, BKM, 4, 4>), grid, block, 0, st, a); break;
-      }
-      UG_CHECK_LAUNCH("ug_gemm_bf16(p10)");
-      return UG_OK;
-    }
+    ug_set_error("ug_gemm_bf16: no %d-row tile kernel for this layout and epilogue", pl.height);
+    return UG_ERR_ARG;
   }
-  // A partial last round of 256x256 tiles is cut along K instead: r = tiles mod 256 leftover tiles x s slices fill
-  // the chip once more for 1/s of a tile time (fp32 atomics into a scratch, then tail_finish applies the epilogue).
-  int tail_r = 0, tail_s = 1;
-  if (!p8_fits && tiles_p8 > 256 && (tiles_p8 % 256) <= 128 && g_tile_policy != 5) {
-    const int r = tiles_p8 % 256, nk32 = (a.K + PBK - 1) / PBK;
-    int sp = 256 / r;
-    // measured with private partials (tools/gemm_bench.py): slices of >= 40 k-tiles and >= 3 slices win (down fwd
-    // 856 -> 1073, gate_up dgrad 748 -> ~1000 TF/s); the K = 1536 shapes (<= 24 k-tiles per slice) lose to 128x128
-    while (sp > 1 && nk32 / sp < 40) --sp;
-    if ((sp >= 3 || g_tile_policy == 6) && sp >= 2 && r * sp <= WS_PRIVATE_SLOTS && ws) { tail_r = r; tail_s = sp; }
-  }
-  // Small accumulating fp32 outputs (weight gradients of the attention projections: 48 / 36 tiles): cut EVERY tile
-  // along K so one round fills the chip, each slice storing a private partial that a finishing pass sums into C.
-  // (The same cut with fp32 atomics was 118-316 TF/s, the 128x128 kernel's 4 atomic slices 353: atomics cost more
-  // than the GEMM itself at these sizes.)
-  {
-    const int nk32 = (a.K + PBK - 1) / PBK;
-    int sp = 0;
-    if (EPI == EPI_F32 && tiles_p8 >= 24 && tiles_p8 <= 128 && a.M >= 512 && a.N >= 512) {
-      sp = 256 / tiles_p8;                               // one round
-      while (sp > 1 && nk32 / sp < 32) --sp;
-    } else if (tiles_p8 >= 24 && tiles_p8 < 200 && nk32 >= 2048) {
-      // few output tiles, very long contraction (lm-head dgrad: 96 tiles, K = 159 867): up to three rounds of slices,
-      // the count that fills whole rounds best (632 -> 1094 TF/s); up to 199 tiles since round 4 (the pt1 mixed batch's
-      // 7 184 head rows = 174 tiles ran 2.7 rounds of 128 x 128 tiles at 817 TF/s)
-      float best = (tiles_p8 > 128) ? (float)tiles_p8 / 256.f : 0.f;      // (must beat the unsliced single round)
-      for (int c = 2; c <= 8 && tiles_p8 * c <= WS_PRIVATE_SLOTS; ++c) {
-        const int items = tiles_p8 * c, r = (items + 255) / 256;
-        const float eff = (float)items / (float)(r * 256);
-        if (eff > best + 0.01f) { best = eff; sp = c; }
-      }
-    }
-    if (sp >= 2 && tiles_p8 * sp <= WS_PRIVATE_SLOTS && (g_tile_policy < 0 || g_tile_policy == 8) && ws) {
-      a.tiles_m = (a.M + PBM - 1) / PBM; a.tiles_n = (a.N + PBN - 1) / PBN;
-      a.full_tiles = 0; a.tail_split = sp; a.tail_private = 1;
-      a.tail_ws = ws;
-      if (a.one_barrier) hipLaunchKernelGGL((gemm_kernel_p8<EPI, AK, BKM, true>), dim3(tiles_p8 * sp), dim3(512), 0, st, a);
-      else hipLaunchKernelGGL((gemm_kernel_p8<EPI, AK, BKM>), dim3(tiles_p8 * sp), dim3(512), 0, st, a);
-      UG_CHECK_LAUNCH("ug_gemm_bf16(p8 k-sliced)");
-      hipLaunchKernelGGL((tail_finish_kernel<EPI>), dim3(tiles_p8 * 16), dim3(256), 0, st, a, tiles_p8);
-      UG_CHECK_LAUNCH("ug_gemm_bf16(partial sum)");
-      return UG_OK;
-    }
-  }
-  if (g_tile_policy == 3 || g_tile_policy == 6 || (g_tile_policy < 0 && (p8_fits || tail_s > 1))) {
-    a.tiles_m = (a.M + PBM - 1) / PBM; a.tiles_n = (a.N + PBN - 1) / PBN;
-    a.full_tiles = tiles_p8 - tail_r; a.tail_split = tail_s;
-    a.tail_private = 1;                          // private partials beat atomics here too (gate_up dgrad 886 -> see DESIGN)
-    a.tail_ws = ws;
-    if (a.one_barrier) hipLaunchKernelGGL((gemm_kernel_p8<EPI, AK, BKM, true>), dim3(a.full_tiles + tail_r * tail_s), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((gemm_kernel_p8<EPI, AK, BKM>), dim3(a.full_tiles + tail_r * tail_s), dim3(512), 0, st, a);
-    UG_CHECK_LAUNCH("ug_gemm_bf16(p8)");
-    if (tail_s > 1) {
-      hipLaunchKernelGGL((tail_finish_kernel<EPI>), dim3(tail_r * 16), dim3(256), 0, st, a, tail_r);
-      UG_CHECK_LAUNCH("ug_gemm_bf16(tail finish)");
-    }
+  if (pl.kind == KIND_128) {
+    if (pl.dbuf) hipLaunchKernelGGL((gemm_kernel<EPI, AK, BKM, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((gemm_kernel<EPI, AK, BKM, false>), grid, dim3(256), 0, st, a);
+    UG_CHECK_LAUNCH("ug_gemm_bf16");
     return UG_OK;
   }
-  bool dbuf = (!AK && !BKM && a.K >= 4096);
-  if (g_tile_policy == 0) dbuf = true;
-  if (g_tile_policy == 2) dbuf = false;
-  dim3 grid(tiles, splits);
-  if (dbuf) hipLaunchKernelGGL((gemm_kernel<EPI, AK, BKM, true>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((gemm_kernel<EPI, AK, BKM, false>), grid, dim3(256), 0, st, a);
-  UG_CHECK_LAUNCH("ug_gemm_bf16");
+  const bool sliced = pl.kind == KIND_256_SLICED;
+  if (a.one_barrier) hipLaunchKernelGGL((gemm_kernel_p8<EPI, AK, BKM, true>), grid, dim3(512), 0, st, a);
+  else hipLaunchKernelGGL((gemm_kernel_p8<EPI, AK, BKM>), grid, dim3(512), 0, st, a);
+  UG_CHECK_LAUNCH(sliced ? "ug_gemm_bf16(p8 k-sliced)" : "ug_gemm_bf16(p8)");
+  if (pl.finish_tiles) {
+    hipLaunchKernelGGL((tail_finish_kernel<EPI>), dim3(pl.finish_tiles * 16), dim3(256), 0, st, a, pl.finish_tiles);
+    UG_CHECK_LAUNCH(sliced ? "ug_gemm_bf16(partial sum)" : "ug_gemm_bf16(tail finish)");
+  }
+  return UG_OK;
+}
+
+// The fused-epilogue entries' launch: tile height by plan_fused -- or the height ug_gemm_set_fused_tile_height() forces (tests and
+// A/B runs reach every instantiation that way; 0 = automatic).  A forced height the epilogue does not instantiate is refused.
+std::atomic<int> g_fused_height{0};
+
+template <int EPI, bool BKM>
+int launch_fused(GemmArgs a, int64_t col_tiles, const char* who, hipStream_t st) {
+  const int forced = g_fused_height.load();
+  const int hb = plan_fused(EPI, a.M, col_tiles, forced);
+  if (hb < 0) {
+    ug_set_error("%s: tile height %d forced by ug_gemm_set_fused_tile_height is not instantiated for this epilogue", who, forced);
+    return UG_ERR_ARG;
+  }
+  a.tiles_m = (a.M + hb - 1) / hb; a.tiles_n = (int)col_tiles;
+  a.tail_split = 1; a.tail_private = 1; a.wide_epilogue = 1;
+  launch_p10<EPI, BKM>(typename P10Heights<EPI>::type{}, hb, dim3(a.tiles_m * a.tiles_n), a, st);
+  UG_CHECK_LAUNCH(who);
   return UG_OK;
 }
 
@@ -1219,31 +1138,30 @@ extern "C" int ug_gemm_bf16(const ug_handle* h, const void* A, int64_t lda, int 
   UG_REQUIRE(b_kmajor || ldb >= ((K + 7) & ~7LL), "ug_gemm_bf16: row-major B needs ldb >= round_up(K,8)");
   UG_REQUIRE(!a_kmajor || lda >= M, "ug_gemm_bf16: k-major A needs lda >= M");
   UG_REQUIRE(!b_kmajor || ldb >= N, "ug_gemm_bf16: k-major B needs ldb >= N");
-  GemmArgs a;
+  if (epilogue == EPI_RESID) UG_REQUIRE(resid != nullptr && ldr % 4 == 0, "ug_gemm_bf16: EPI_RESID needs a 16B-aligned residual");
+  const GemmPolicy pol = decode_policy(policy, a_kmajor != 0, b_kmajor != 0);
+  GemmArgs a{};
   a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C;
   a.bias = (const bf16_t*)bias; a.resid = resid; a.alpha_dev = alpha_dev;
   a.M = (int)M; a.N = (int)N; a.K = (int)K;
   a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.ldr = ldr; a.beta = beta;
-  a.swiglu_I = 0; a.act = nullptr; a.ld_act = 0;
-  a.wide_epilogue = (policy >= 0 && (policy & UG_GEMM_NARROW_EPILOGUE)) ? 0 : 1;
-  // main loop of the 256x256 kernel: one barrier per k-tile for the weight gradients (both operands through the transposing
-  // fragment reads make L half again as long as M: +10..13 %), two for forward and dgrad (short L: one barrier is -2..-3 %)
-  a.one_barrier = (a_kmajor && b_kmajor) ? 1 : 0;
-  if (policy >= 0 && (policy & UG_GEMM_ONE_BARRIER)) a.one_barrier = 1;
-  if (policy >= 0 && (policy & UG_GEMM_TWO_BARRIERS)) a.one_barrier = 0;
-  if (policy >= 0) policy &= ~(UG_GEMM_NARROW_EPILOGUE | UG_GEMM_ONE_BARRIER | UG_GEMM_TWO_BARRIERS);
-  if (policy == UG_GEMM_POLICY_AUTO_BITS) policy = -1;
-  a.tiles_m = (int)((M + BM - 1) / BM); a.tiles_n = (int)((N + BN - 1) / BN);
+  a.wide_epilogue = pol.wide_epilogue; a.one_barrier = pol.one_barrier;
+  a.tail_ws = h ? h->tail_ws : nullptr;                                 // k-sliced forms need a handle's scratch
+  static const bool heights_on = env_switch_on("UNIGEN_GEMM_HEIGHTS");
+  GemmProblem pr;
+  pr.M = a.M; pr.N = a.N; pr.K = a.K; pr.epilogue = epilogue; pr.a_kmajor = a_kmajor != 0; pr.b_kmajor = b_kmajor != 0; pr.beta = beta;
+  pr.ldc = ldc; pr.ldr = ldr; pr.bias_aligned8 = !bias || (reinterpret_cast<uintptr_t>(bias) & 7) == 0;
+  pr.has_workspace = a.tail_ws != nullptr; pr.policy = pol.policy; pr.heights_on = heights_on;
+  const GemmPlan pl = plan_gemm(pr);
   const int mode = (a_kmajor ? 2 : 0) | (b_kmajor ? 1 : 0);
-  if (epilogue == EPI_RESID) UG_REQUIRE(resid != nullptr && ldr % 4 == 0, "ug_gemm_bf16: EPI_RESID needs a 16B-aligned residual");
   switch (mode * 4 + epilogue) {
-    case 0 * 4 + EPI_BF16: return launch<EPI_BF16, false, false>(a, h, policy, stream);
-    case 0 * 4 + EPI_F32: return launch<EPI_F32, false, false>(a, h, policy, stream);
-    case 0 * 4 + EPI_RESID: return launch<EPI_RESID, false, false>(a, h, policy, stream);
-    case 1 * 4 + EPI_BF16: return launch<EPI_BF16, false, true>(a, h, policy, stream);
-    case 1 * 4 + EPI_F32: return launch<EPI_F32, false, true>(a, h, policy, stream);
-    case 3 * 4 + EPI_F32: return launch<EPI_F32, true, true>(a, h, policy, stream);
-    case 3 * 4 + EPI_BF16: return launch<EPI_BF16, true, true>(a, h, policy, stream);
+    case 0 * 4 + EPI_BF16: return run_plan<EPI_BF16, false, false>(pl, a, stream);
+    case 0 * 4 + EPI_F32: return run_plan<EPI_F32, false, false>(pl, a, stream);
+    case 0 * 4 + EPI_RESID: return run_plan<EPI_RESID, false, false>(pl, a, stream);
+    case 1 * 4 + EPI_BF16: return run_plan<EPI_BF16, false, true>(pl, a, stream);
+    case 1 * 4 + EPI_F32: return run_plan<EPI_F32, false, true>(pl, a, stream);
+    case 3 * 4 + EPI_F32: return run_plan<EPI_F32, true, true>(pl, a, stream);
+    case 3 * 4 + EPI_BF16: return run_plan<EPI_BF16, true, true>(pl, a, stream);
     default:
       ug_set_error("ug_gemm_bf16: layout/epilogue combination (a_kmajor=%d b_kmajor=%d epilogue=%d) is not instantiated",
                    a_kmajor, b_kmajor, epilogue);
@@ -1279,32 +1197,9 @@ extern "C" int ug_gemm_bf16_wgrad_group(int n, const void* const* dy, const int6
   return UG_OK;
 }
 
-
-// Tile height of the fused-epilogue launches (ug_gemm_bf16_swiglu / _qkv_rope / _swiglu_bwd): rounds(h) x t(h) over the heights the
-// entry point instantiates -- or the height ug_gemm_set_fused_tile_height() forces (tests and A/B runs reach every instantiation
-// that way; 0 = automatic).  A forced height the entry point does not instantiate is refused.
-static std::atomic<int> g_fused_height{0};
 extern "C" int ug_gemm_set_fused_tile_height(int rows) {
   UG_REQUIRE(rows == 0 || (rows >= 128 && rows <= 320 && rows % 16 == 0), "ug_gemm_set_fused_tile_height: 0 (automatic) or 128 ... 320 in steps of 16 (%d)", rows);
   g_fused_height.store(rows);
-  return UG_OK;
-}
-template <size_t NH>
-static int pick_fused_height(const int (&heights)[NH], int64_t M, int64_t col_tiles, const char* who, int* out) {
-  const int forced = g_fused_height.load();
-  if (forced) {
-    for (int h_ : heights)
-      if (h_ == forced) { *out = forced; return UG_OK; }
-    ug_set_error("%s: tile height %d forced by ug_gemm_set_fused_tile_height is not instantiated for this epilogue", who, forced);
-    return UG_ERR_ARG;
-  }
-  int hb = heights[NH - 1]; float best = 1e30f;
-  for (int h_ : heights) {
-    const int64_t wgs = ((M + h_ - 1) / h_) * col_tiles;
-    const float cost = (float)((wgs + 255) / 256) * (0.35f + 0.00254f * (float)h_);
-    if (cost < best) { best = cost; hb = h_; }
-  }
-  *out = hb;
   return UG_OK;
 }
 
@@ -1329,26 +1224,9 @@ extern "C" int ug_gemm_bf16_swiglu(const ug_handle* h, const void* x, int64_t ld
   a.A = (const bf16_t*)x; a.B = (const bf16_t*)w_gate_up; a.C = gu;
   a.M = (int)M; a.N = (int)(2 * I); a.K = (int)K;
   a.lda = ldx; a.ldb = ldw; a.ldc = ld_gu;
-  a.tail_split = 1; a.tail_private = 1; a.wide_epilogue = 1;
   a.swiglu_I = (int)I; a.act = (bf16_t*)act; a.ld_act = ld_act;
   // round 4: the 128 ... 320-row kernel with gate and up of a hidden unit in one lane (EPI_SWIGLU); tile height by rounds(h) x t(h)
-  static const int heights[] = {128, 160, 192, 208, 224, 256, 288, 320};
-  int hb = 320;
-  if (int rc = pick_fused_height(heights, M, 2 * I / PBN, "ug_gemm_bf16_swiglu", &hb)) return rc;
-  a.tiles_m = (int)((M + hb - 1) / hb); a.tiles_n = (int)(2 * I / PBN);
-  const dim3 grid(a.tiles_m * a.tiles_n), block(512);
-  switch (hb) {
-    case 320: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU, false, 10, 10>), grid, block, 0, stream, a); break;
-    case 288: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU, false, 9, 9>), grid, block, 0, stream, a); break;
-    case 256: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU, false, 8, 8>), grid, block, 0, stream, a); break;
-    case 224: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU, false, 7, 7>), grid, block, 0, stream, a); break;
-    case 208: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU, false, 7, 6>), grid, block, 0, stream, a); break;
-    case 192: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU, false, 6, 6>), grid, block, 0, stream, a); break;
-    case 160: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU, false, 5, 5>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU, false, 4, 4>), grid, block, 0, stream, a); break;
-  }
-  UG_CHECK_LAUNCH("ug_gemm_bf16_swiglu(p10)");
-  return UG_OK;
+  return launch_fused<EPI_SWIGLU, false>(a, 2 * I / PBN, "ug_gemm_bf16_swiglu", stream);
 }
 
 // The fused q/k/v projection: qkv = bf16(x W^T + b) with rotate-half RoPE applied to the first rope_cols columns (the q and k heads)
@@ -1368,7 +1246,7 @@ extern "C" int ug_gemm_bf16_qkv_rope(const ug_handle* h, const void* x, int64_t 
   const bool fused = head_dim == 128 && N % PBN == 0 && rope_cols % PBN == 0 && K % PBK == 0 && ldq % 8 == 0 && ldx % 8 == 0 && ldw % 8 == 0 &&
                      ldx >= K && ldw >= K && ldq >= N && ug_aligned16(x) && ug_aligned16(w) && ug_aligned16(qkv) &&
                      (!bias || (reinterpret_cast<uintptr_t>(bias) & 7) == 0) && N / PBN <= 64;
-  static const bool fused_on = !(getenv("UNIGEN_FUSED_ROPE") && atoi(getenv("UNIGEN_FUSED_ROPE")) == 0);      // A/B switch
+  static const bool fused_on = env_switch_on("UNIGEN_FUSED_ROPE");
   if (!fused || !fused_on) {                    // any other shape: the projection and the rotation as two launches (identical values)
     if (int rc = ug_gemm_bf16(h, x, ldx, 0, w, ldw, 0, qkv, ldq, M, N, K, EPI_BF16, bias, nullptr, 0, 0, nullptr, -1, stream)) return rc;
     if (rope_cols == 0) return UG_OK;
@@ -1378,25 +1256,7 @@ extern "C" int ug_gemm_bf16_qkv_rope(const ug_handle* h, const void* x, int64_t 
   a.A = (const bf16_t*)x; a.B = (const bf16_t*)w; a.C = qkv; a.bias = (const bf16_t*)bias;
   a.M = (int)M; a.N = (int)N; a.K = (int)K; a.lda = ldx; a.ldb = ldw; a.ldc = ldq;
   a.rope_cos = cos_tab; a.rope_sin = sin_tab; a.rope_L = (int)L; a.rope_cols = (int)rope_cols;
-  a.tail_split = 1; a.tail_private = 1; a.wide_epilogue = 1;
-  // tile height: rounds(h) x t(h), the rule of launch() (one round: the smallest height that fits)
-  static const int heights[] = {128, 160, 192, 208, 224, 256, 288, 320};
-  int hb = 320;
-  if (int rc = pick_fused_height(heights, M, N / PBN, "ug_gemm_bf16_qkv_rope", &hb)) return rc;
-  a.tiles_m = (int)((M + hb - 1) / hb); a.tiles_n = (int)(N / PBN);
-  const dim3 grid(a.tiles_m * a.tiles_n), block(512);
-  switch (hb) {
-    case 320: hipLaunchKernelGGL((gemm_kernel_p10<EPI_ROPE, false, 10, 10>), grid, block, 0, stream, a); break;
-    case 288: hipLaunchKernelGGL((gemm_kernel_p10<EPI_ROPE, false, 9, 9>), grid, block, 0, stream, a); break;
-    case 256: hipLaunchKernelGGL((gemm_kernel_p10<EPI_ROPE, false, 8, 8>), grid, block, 0, stream, a); break;
-    case 224: hipLaunchKernelGGL((gemm_kernel_p10<EPI_ROPE, false, 7, 7>), grid, block, 0, stream, a); break;
-    case 208: hipLaunchKernelGGL((gemm_kernel_p10<EPI_ROPE, false, 7, 6>), grid, block, 0, stream, a); break;
-    case 192: hipLaunchKernelGGL((gemm_kernel_p10<EPI_ROPE, false, 6, 6>), grid, block, 0, stream, a); break;
-    case 160: hipLaunchKernelGGL((gemm_kernel_p10<EPI_ROPE, false, 5, 5>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((gemm_kernel_p10<EPI_ROPE, false, 4, 4>), grid, block, 0, stream, a); break;
-  }
-  UG_CHECK_LAUNCH("ug_gemm_bf16_qkv_rope");
-  return UG_OK;
+  return launch_fused<EPI_ROPE, false>(a, N / PBN, "ug_gemm_bf16_qkv_rope", stream);
 }
 
 
@@ -1415,23 +1275,6 @@ extern "C" int ug_gemm_bf16_swiglu_bwd(const ug_handle* h, const void* dy, int64
   a.A = (const bf16_t*)dy; a.B = (const bf16_t*)w_down; a.C = dgu;
   a.M = (int)M; a.N = (int)I; a.K = (int)K; a.lda = ld_dy; a.ldb = ldw; a.ldc = ld_dgu;
   a.sw_gu = (const bf16_t*)gu; a.ld_gu = ld_gu; a.swiglu_I = (int)I;
-  a.tail_split = 1; a.tail_private = 1; a.wide_epilogue = 1;
-  static const int heights[] = {128, 160, 192, 208, 224, 256, 272, 288, 320};
-  int hb = 320;
-  if (int rc = pick_fused_height(heights, M, I / PBN, "ug_gemm_bf16_swiglu_bwd", &hb)) return rc;
-  a.tiles_m = (int)((M + hb - 1) / hb); a.tiles_n = (int)(I / PBN);
-  const dim3 grid(a.tiles_m * a.tiles_n), block(512);
-  switch (hb) {
-    case 320: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU_BWD, true, 10, 10>), grid, block, 0, stream, a); break;
-    case 288: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU_BWD, true, 9, 9>), grid, block, 0, stream, a); break;
-    case 272: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU_BWD, true, 9, 8>), grid, block, 0, stream, a); break;
-    case 256: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU_BWD, true, 8, 8>), grid, block, 0, stream, a); break;
-    case 224: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU_BWD, true, 7, 7>), grid, block, 0, stream, a); break;
-    case 208: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU_BWD, true, 7, 6>), grid, block, 0, stream, a); break;
-    case 192: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU_BWD, true, 6, 6>), grid, block, 0, stream, a); break;
-    case 160: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU_BWD, true, 5, 5>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((gemm_kernel_p10<EPI_SWIGLU_BWD, true, 4, 4>), grid, block, 0, stream, a); break;
-  }
-  UG_CHECK_LAUNCH("ug_gemm_bf16_swiglu_bwd");
-  return UG_OK;
+  return launch_fused<EPI_SWIGLU_BWD, true>(a, I / PBN, "ug_gemm_bf16_swiglu_bwd", stream);
 }
+

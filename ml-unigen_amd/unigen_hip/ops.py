@@ -1,5 +1,6 @@
 """Tensor-level wrappers over the C ABI: torch supplies device memory and the stream, the kernels do
 the work.  Every wrapper launches on torch's current HIP stream and never synchronises."""
+import contextlib
 import ctypes
 import math
 import torch
@@ -13,6 +14,34 @@ _MASK_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.int64: 2, torch.bool:
 # bench.py sets this to a list to time every GEMM launch with HIP events on the launch stream
 GEMM_PROFILE = None
 GEMM_PROFILE_FUSED = None     # with GEMM_PROFILE: indices of the launches whose epilogue carries element-wise work (RoPE, SwiGLU forward / backward)
+
+
+class _GemmTimed:
+    """HIP events on the launch stream around one GEMM launch: appends (e0, e1, flops) to `prof`, and the entry's index to
+    GEMM_PROFILE_FUSED for a fused-epilogue launch.  A launch that raises leaves no entry."""
+
+    def __init__(self, prof, flops, fused):
+        self.prof, self.flops, self.fused = prof, flops, fused
+
+    def __enter__(self):
+        self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        self.e0.record()
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.e1.record()
+            self.prof.append((self.e0, self.e1, self.flops))
+            if self.fused and GEMM_PROFILE_FUSED is not None:
+                GEMM_PROFILE_FUSED.append(len(self.prof) - 1)
+        return False
+
+
+_UNTIMED = contextlib.nullcontext()
+
+
+def _gemm_timed(flops, fused=False):
+    prof = GEMM_PROFILE             # profiling off: this one global read
+    return _UNTIMED if prof is None else _GemmTimed(prof, flops, fused)
 
 
 def _stream():
@@ -79,17 +108,11 @@ def gemm(a, b, out=None, *, M=None, N=None, K=None, a_kmajor=False, b_kmajor=Fal
         dt = out_dtype or (torch.bfloat16 if epilogue == UG_EPI_BF16 else torch.float32)
         out = torch.empty((M, N), dtype=dt, device=a.device)
     lib = _l.load()
-    prof = GEMM_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = lib.ug_gemm_bf16(_handle(), _p(a), a.stride(0), int(a_kmajor), _p(b), b.stride(0), int(b_kmajor), _p(out), out.stride(0),
-                          M, N, K, epilogue, _p(bias), _p(resid), resid.stride(0) if resid is not None else 0, beta,
-                          _p(alpha_dev), GEMM_POLICY, _stream())
-    _l.check(rc, "ug_gemm_bf16")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * N * K))
+    with _gemm_timed(2.0 * M * N * K):
+        rc = lib.ug_gemm_bf16(_handle(), _p(a), a.stride(0), int(a_kmajor), _p(b), b.stride(0), int(b_kmajor), _p(out), out.stride(0),
+                              M, N, K, epilogue, _p(bias), _p(resid), resid.stride(0) if resid is not None else 0, beta,
+                              _p(alpha_dev), GEMM_POLICY, _stream())
+        _l.check(rc, "ug_gemm_bf16")
     return out
 
 
@@ -111,17 +134,9 @@ def gemm_swiglu(x, w_gate_up):
     I = w_gate_up.shape[0] // 2
     gu = torch.empty((M, 2 * I), dtype=torch.bfloat16, device=x.device)
     act = torch.empty((M, I), dtype=torch.bfloat16, device=x.device)
-    prof = GEMM_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _l.check(_l.load().ug_gemm_bf16_swiglu(_handle(), _p(x), x.stride(0), _p(w_gate_up), w_gate_up.stride(0), _p(gu), gu.stride(0),
-                                           _p(act), act.stride(0), M, I, K, _stream()), "ug_gemm_bf16_swiglu")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * 2 * I * K))
-        if GEMM_PROFILE_FUSED is not None:
-            GEMM_PROFILE_FUSED.append(len(prof) - 1)
+    with _gemm_timed(2.0 * M * 2 * I * K, fused=True):
+        _l.check(_l.load().ug_gemm_bf16_swiglu(_handle(), _p(x), x.stride(0), _p(w_gate_up), w_gate_up.stride(0), _p(gu), gu.stride(0),
+                                               _p(act), act.stride(0), M, I, K, _stream()), "ug_gemm_bf16_swiglu")
     return gu, act
 
 
@@ -142,20 +157,14 @@ def gemm_wgrad_group(problems):
     for dy, x, dw, _ in problems:
         _need_cuda(dy, x, dw)
         assert dy.shape[0] == x.shape[0] and dw.shape == (dy.shape[1], x.shape[1])
-    prof = GEMM_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = _l.load().ug_gemm_bf16_wgrad_group(
-        n, PA(*[_p(dy) for dy, _, _, _ in problems]), LA(*[dy.stride(0) for dy, _, _, _ in problems]),
-        PA(*[_p(x) for _, x, _, _ in problems]), LA(*[x.stride(0) for _, x, _, _ in problems]),
-        PA(*[_p(dw) for _, _, dw, _ in problems]), LA(*[dw.stride(0) for _, _, dw, _ in problems]),
-        LA(*[dy.shape[1] for dy, _, _, _ in problems]), LA(*[x.shape[1] for _, x, _, _ in problems]),
-        IA(*[int(b) for _, _, _, b in problems]), LA(*[dy.shape[0] for dy, _, _, _ in problems]), _stream())
-    _l.check(rc, "ug_gemm_bf16_wgrad_group")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, sum(2.0 * dy.shape[1] * x.shape[1] * dy.shape[0] for dy, x, _, _ in problems)))
+    with _gemm_timed(sum(2.0 * dy.shape[1] * x.shape[1] * dy.shape[0] for dy, x, _, _ in problems)):
+        rc = _l.load().ug_gemm_bf16_wgrad_group(
+            n, PA(*[_p(dy) for dy, _, _, _ in problems]), LA(*[dy.stride(0) for dy, _, _, _ in problems]),
+            PA(*[_p(x) for _, x, _, _ in problems]), LA(*[x.stride(0) for _, x, _, _ in problems]),
+            PA(*[_p(dw) for _, _, dw, _ in problems]), LA(*[dw.stride(0) for _, _, dw, _ in problems]),
+            LA(*[dy.shape[1] for dy, _, _, _ in problems]), LA(*[x.shape[1] for _, x, _, _ in problems]),
+            IA(*[int(b) for _, _, _, b in problems]), LA(*[dy.shape[0] for dy, _, _, _ in problems]), _stream())
+        _l.check(rc, "ug_gemm_bf16_wgrad_group")
 
 
 def set_gemm_tile_policy(policy):
@@ -289,17 +298,9 @@ def gemm_qkv_rope(x, w, bias, cos, sin, L, nheads, head_dim):
         qkv = gemm(x, w, bias=bias)
         return rope_(qkv, cos, sin, L, nheads, head_dim)
     qkv = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    prof = GEMM_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _l.check(_l.load().ug_gemm_bf16_qkv_rope(_handle(), _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(qkv), qkv.stride(0), M, N, K,
-                                              _p(cos), _p(sin), L, nheads * head_dim, head_dim, _stream()), "ug_gemm_bf16_qkv_rope")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * N * K))
-        if GEMM_PROFILE_FUSED is not None:
-            GEMM_PROFILE_FUSED.append(len(prof) - 1)
+    with _gemm_timed(2.0 * M * N * K, fused=True):
+        _l.check(_l.load().ug_gemm_bf16_qkv_rope(_handle(), _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(qkv), qkv.stride(0), M, N, K,
+                                                  _p(cos), _p(sin), L, nheads * head_dim, head_dim, _stream()), "ug_gemm_bf16_qkv_rope")
     return qkv
 
 
@@ -326,17 +327,9 @@ def gemm_swiglu_bwd(dy, w_down, gu):
     if not ok:
         return swiglu_bwd(gu, gemm(dy, w_down, b_kmajor=True))
     dgu = torch.empty_like(gu)
-    prof = GEMM_PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _l.check(_l.load().ug_gemm_bf16_swiglu_bwd(_handle(), _p(dy), dy.stride(0), _p(w_down), w_down.stride(0), _p(gu), gu.stride(0),
-                                                _p(dgu), dgu.stride(0), M, I, K, _stream()), "ug_gemm_bf16_swiglu_bwd")
-    if prof is not None:
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * I * K))
-        if GEMM_PROFILE_FUSED is not None:
-            GEMM_PROFILE_FUSED.append(len(prof) - 1)
+    with _gemm_timed(2.0 * M * I * K, fused=True):
+        _l.check(_l.load().ug_gemm_bf16_swiglu_bwd(_handle(), _p(dy), dy.stride(0), _p(w_down), w_down.stride(0), _p(gu), gu.stride(0),
+                                                    _p(dgu), dgu.stride(0), M, I, K, _stream()), "ug_gemm_bf16_swiglu_bwd")
     return dgu
 
 

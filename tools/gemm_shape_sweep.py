@@ -1,5 +1,5 @@
 """The layer's eight forward / dgrad GEMM launches at a given token count M under every tile policy: which kernel wins where
-(the selection rule of gemm_bf16.hip::launch is checked against this table).  usage: gemm_shape_sweep.py M [policies...]"""
+(the selection rule of gemm_plan.h::plan_gemm is checked against this table).  usage: gemm_shape_sweep.py M [policies...]"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ml-unigen_amd"))
 import torch
