@@ -659,8 +659,8 @@ class Qwen2Engine:
         if deterministic:
             ord_dims = H == 256 * ops.ORD_QKV_SLABS and I == 1792 * ops.ORD_DOWN_KBLOCKS and d.num_hidden_layers >= 1
             return "ord_sw" if sw_ok and ord_dims else "ord_wide"
-        if not fused or rows > 32 or hd != 128 or min(H, I, q_dim) < 256 or H % 32 or I % 32:
-            return "wide"
+        if not fused or rows > 32 or hd != 128 or min(H, I, q_dim) < 256 or H % 32 or I % 32 or H > 4096:
+            return "wide"                                   # (H > 4096: ug_decode_finish_resid_norm holds a row of at most 4096 columns)
         return "sw" if sw_ok else "splitk"
 
     def decode_sw(self, st):

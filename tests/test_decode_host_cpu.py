@@ -38,6 +38,7 @@ FORM_TABLE = [
     (dict(head_dim=64, num_attention_heads=24), True, None, 1, False, "wide"),
     (dict(intermediate_size=8976), True, None, 1, False, "wide"),                 # 1536-wide, intermediate no multiple of 32
     (dict(hidden_size=256, intermediate_size=512, num_attention_heads=2), True, None, 1, False, "splitk"),
+    (dict(hidden_size=5120, num_attention_heads=40), True, None, 1, False, "wide"),     # wider than the split-K step's finisher takes
 ]
 
 

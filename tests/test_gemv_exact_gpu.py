@@ -9,7 +9,8 @@ give `torch.equal` with the CPU reference at every element).
   ug_gemv_bf16_ord + ug_skinny_finish_ord, ug_decode_sw_kblock_ord + ug_decode_finish_resid_norm_ord (without the norm output)
 
 Activations and weights are stored with padded leading dimensions; accumulators carry a sentinel past column N.  The launches that
-fuse a norm, RoPE or attention are not here: their arithmetic is not integer.
+fuse RMSNorm, the residual add or SwiGLU are in tests/test_decode_exact_gpu.py (inputs that make their arithmetic integer); the ones
+that fuse RoPE and attention are not integer and stay with tests/test_decode_parity_gpu.py.
 """
 import pytest
 import torch
@@ -38,9 +39,11 @@ def _assert_cleared(*ts):
         assert float(t.abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("R,N,K", ep.GEMV_SHAPES)
+@pytest.mark.parametrize("R,N,K", ep.GEMV_SHAPES + ep.GEMV_TALL_SHAPES)
 def test_gemv_acc_into_prefilled_accumulator(dev, R, N, K):
-    """ug_gemv_bf16: the ring kernel (K >= 256) and the direct-load kernel (K = 32); twice into the same accumulator"""
+    """ug_gemv_bf16: the ring kernel (K >= 256) and the direct-load kernel (K = 32); twice into the same accumulator.  The shapes of
+    more than 16 rows run the two-row-block instantiations: gemv_kernel<2, .> at K = 32, gemv_ring_kernel<2, 1> and -- from 3000 tiles
+    on, (24, 8016, 1536) has 501 groups x 6 slabs -- gemv_ring_kernel<2, 2>."""
     ops = _ops()
     x, w, _, ref = _operands(dev, R, N, K, "dense")
     pre = ep.int_prefill(R, N, seed=N + K)
@@ -50,7 +53,7 @@ def test_gemv_acc_into_prefilled_accumulator(dev, R, N, K):
         ep.assert_exact(acc, N, pre + rep * ref, f"gemv_acc_ {(R, N, K)} call {rep}")
 
 
-@pytest.mark.parametrize("R,N,K", ep.GEMV_SHAPES)
+@pytest.mark.parametrize("R,N,K", ep.GEMV_SHAPES + ep.GEMV_TALL_SHAPES)
 def test_skinny_linear_bias_and_residual(dev, R, N, K):
     ops = _ops()
     x, w, bias, ref = _operands(dev, R, N, K, "small")
@@ -64,7 +67,7 @@ def test_skinny_linear_bias_and_residual(dev, R, N, K):
     ep.assert_exact(res, N, pre + ref, f"skinny_linear residual {(R, N, K)}")
 
 
-@pytest.mark.parametrize("R,N,K", [s for s in ep.GEMV_SHAPES if s[2] >= 256])
+@pytest.mark.parametrize("R,N,K", [s for s in ep.GEMV_SHAPES + ep.GEMV_TALL_SHAPES if s[2] >= 256])
 def test_decode_gemv_with_clears(dev, R, N, K):
     ops = _ops()
     x, w, _, ref = _operands(dev, R, N, K, "dense")
