@@ -13,6 +13,7 @@
 // contraction needs the streamed operand k-major: its fragments are read from the SAME row-major LDS
 // tile with the hardware transposing read (ds_read_b64_tr_b16), so every operand is staged once, row-major,
 // with 16-byte loads, and no transposed copy exists in HBM or LDS.
+#include "attn_plan.h"
 #include "common.h"
 #include "unigen_hip.h"
 #include "vmem_asm.h"
@@ -299,10 +300,7 @@ __device__ __forceinline__ WgCoord wg_coord(int wid, int nT, int H, int HKV, int
   c.tile = heavy_last ? nT - 1 - rank : rank;
   return c;
 }
-static inline unsigned wg_grid(int64_t nT, int H, int HKV, int64_t B) {
-  const int64_t P = B * HKV;
-  return (unsigned)(8 * ((P + 7) / 8) * nT * (H / HKV));
-}
+// (the grid that goes with it: ug_plan::wg_grid, attn_plan.h)
 
 // ================================================================== forward
 // grid (ceil(L / (16 NW)), H, B).  NW = 4: one 64-row query tile per workgroup; NW = 8: two (128 rows) sharing every staged
@@ -1444,16 +1442,14 @@ extern "C" int ug_attn_fwd(const void* q, const void* k, const void* v, int64_t 
   a.o = (bf16_t*)o; a.lse = lse; a.bits = bits; a.tileany = tileany;
   a.ldq = ldq; a.ldo = ldo; a.B = (int)B; a.L = (int)L; a.Lp = (int)Lp; a.nW = (int)((L + 63) / 64);
   a.H = H; a.HKV = HKV; a.scale = scale;
-  { static const int abl = [] { const char* e = getenv("UNIGEN_ATTN_ABLATE"); return e ? atoi(e) : 0; }(); a.ablate = abl; }
-  // 128-row query tiles (eight waves share each staged K / V tile) once there are enough of them to fill the chip
-  static const int use32 = [] { const char* e = getenv("UNIGEN_ATTN_FWD32"); return e ? atoi(e) : 1; }();
-  { static const int ord = [] { const char* e = getenv("UNIGEN_ATTN_ORDER"); return e ? atoi(e) : 1; }(); a.order = ord & 1; }
-  if (use32 && L >= 256 && L <= 4096 && (int64_t)((L + 127) / 128) * H * B >= 512)
-    hipLaunchKernelGGL(attn_fwd32_kernel<4>, dim3(wg_grid((L + 127) / 128, H, HKV, B)), dim3(256), 0, st, a);
-  else if (L >= 256 && (int64_t)((L + 127) / 128) * H * B >= 512)
-    hipLaunchKernelGGL(attn_fwd_kernel<8>, dim3(wg_grid((L + 127) / 128, H, HKV, B)), dim3(512), 0, st, a);
-  else
-    hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(wg_grid(a.nW, H, HKV, B)), dim3(256), 0, st, a);
+  const ug_plan::AttnFwdPlan pl = ug_plan::plan_attn_fwd(B, L, H, HKV);
+  a.order = pl.order;
+  const dim3 grid(pl.grid), block(pl.block);
+  switch (pl.kernel) {
+    case ug_plan::ATTN_FWD32_4: hipLaunchKernelGGL(attn_fwd32_kernel<4>, grid, block, 0, st, a); break;
+    case ug_plan::ATTN_FWD_8: hipLaunchKernelGGL(attn_fwd_kernel<8>, grid, block, 0, st, a); break;
+    case ug_plan::ATTN_FWD_4: hipLaunchKernelGGL(attn_fwd_kernel<4>, grid, block, 0, st, a); break;
+  }
   UG_CHECK_LAUNCH("ug_attn_fwd");
   return UG_OK;
 }
@@ -1477,58 +1473,36 @@ extern "C" int ug_attn_bwd(const void* q, const void* k, const void* v, int64_t 
   a.bits = bits; a.tileany = tileany;
   a.ldq = ldq; a.ldo = ldo; a.ldg = ldg; a.B = (int)B; a.L = (int)L; a.Lp = (int)Lp; a.nW = (int)((L + 63) / 64);
   a.H = H; a.HKV = HKV; a.scale = scale;
-  { static const int abl = [] { const char* e = getenv("UNIGEN_ATTN_ABLATE"); return e ? atoi(e) : 0; }(); a.ablate = abl; }
-  static const int use32 = [] { const char* e = getenv("UNIGEN_ATTN_DQ32"); return e ? atoi(e) : 1; }();
-  static const int fuse = [] { const char* e = getenv("UNIGEN_ATTN_BWD_FUSE_ROPE"); return e ? atoi(e) : 1; }();
+  const ug_plan::AttnBwdPlan pl = ug_plan::plan_attn_bwd(B, L, H, HKV, dkv_ws != nullptr, rope_cos != nullptr, dbias != nullptr);
   const int64_t tokens = B * L;
-  // what the fused stores do not cover is done by the stand-alone passes (same arithmetic): ug_rope / ug_colsum_bf16
-  auto rope_pass = [&](void* x, int nheads) -> int { return rope_cos ? ug_rope(x, rope_cos, rope_sin, tokens, L, ldg, nheads, HD, 1, st) : UG_OK; };
-  auto colsum_pass = [&](const void* x, float* out, int cols) -> int { return dbias ? ug_colsum_bf16(x, ldg, out, tokens, cols, st) : UG_OK; };
-  static const int ord = [] { const char* e = getenv("UNIGEN_ATTN_ORDER"); return e ? atoi(e) : 1; }();
-  a.order = (ord >> 1) & 1;
-  if (use32 && L >= 256 && L <= 4096 && (int64_t)((L + 127) / 128) * H * B >= 512) {
-    if (fuse) { a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.dbias = dbias; }
-    hipLaunchKernelGGL(attn_bwd_dq32_kernel<4>, dim3(wg_grid((L + 127) / 128, H, HKV, B)), dim3(256), 0, st, a);
-    UG_CHECK_LAUNCH("ug_attn_bwd(dq)");
-    if (!fuse) { if (int rc = rope_pass(dq, H)) return rc; if (int rc = colsum_pass(dq, dbias, H * HD)) return rc; }
-  } else {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(wg_grid(a.nW, H, HKV, B)), dim3(256), 0, st, a);
-    UG_CHECK_LAUNCH("ug_attn_bwd(dq)");
-    if (int rc = rope_pass(dq, H)) return rc;
-    if (int rc = colsum_pass(dq, dbias, H * HD)) return rc;
-  }
+  const dim3 block(256);
+  a.order = pl.dq_order;
+  if (pl.dq_fused) { a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.dbias = dbias; }
+  if (pl.dq == ug_plan::ATTN_DQ32_4) hipLaunchKernelGGL(attn_bwd_dq32_kernel<4>, dim3(pl.dq_grid), block, 0, st, a);
+  else hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(pl.dq_grid), block, 0, st, a);
+  UG_CHECK_LAUNCH("ug_attn_bwd(dq)");
+  if (pl.rope_dq) { if (int rc = ug_rope(dq, rope_cos, rope_sin, tokens, L, ldg, H, HD, 1, st)) return rc; }
+  if (pl.colsum_dq) { if (int rc = ug_colsum_bf16(dq, ldg, dbias, tokens, H * HD, st)) return rc; }
   a.rope_cos = a.rope_sin = nullptr; a.dbias = nullptr;
   float* dbias_k = dbias ? dbias + H * HD : nullptr;
   float* dbias_v = dbias ? dbias + (H + HKV) * HD : nullptr;
-  if (dkv_ws) {
-    static const int dma = [] { const char* e = getenv("UNIGEN_ATTN_DKV_DMA"); return e ? atoi(e) : 1; }();
-    a.order = (ord >> 2) & 1;
-    static const int hpw_env = [] { const char* e = getenv("UNIGEN_ATTN_DKV_HEADS"); return e ? atoi(e) : 2; }();
-    static const int hpw_min_wgs = [] { const char* e = getenv("UNIGEN_ATTN_DKV_MIN_WGS"); return e ? atoi(e) : 1024; }();
-    a.dkv_heads = (hpw_env >= 1 && (H / HKV) % hpw_env == 0 && (int64_t)a.nW * (H / hpw_env) * B >= hpw_min_wgs) ? hpw_env : 1;
-    if (dma && L <= 4096) hipLaunchKernelGGL(attn_bwd_dkv_dma_kernel, dim3(wg_grid(a.nW, H / a.dkv_heads, HKV, B)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, dim3(wg_grid(a.nW, H, HKV, B)), dim3(256), 0, st, a);
-    UG_CHECK_LAUNCH("ug_attn_bwd(dkv split)");
-    if (fuse && (rope_cos || dbias) && HKV <= 16 && (HKV & (HKV - 1)) == 0) {
-      // ~128 workgroups: every workgroup ends with one atomic per bias column (512 addresses), and 1 000 same-address atomics
-      // in a burst cost more (53 us measured) than the whole streaming pass (9 us)
-      static const int fin_wgs = [] { const char* e = getenv("UNIGEN_ATTN_FINISH_WGS"); return e ? atoi(e) : 128; }();
-      const int rpb = (int)((tokens + fin_wgs - 1) / fin_wgs < 8 ? 8 : (tokens + fin_wgs - 1) / fin_wgs);
-      hipLaunchKernelGGL(dkv_finish_rope_kernel, dim3((unsigned)((tokens + rpb - 1) / rpb)), dim3(256), 0, st, dkv_ws, a.dk, a.dv, ldg,
-                         tokens, (int)L, HKV, rope_cos, rope_sin, dbias_k, dbias_v, rpb);
-      UG_CHECK_LAUNCH("ug_attn_bwd(dkv finish + rope)");
-      return UG_OK;
-    }
-    const int64_t total = B * L * (2 * HKV * HD / 4);
-    int64_t gsz = (total + 255) / 256; if (gsz > 4096) gsz = 4096;
-    hipLaunchKernelGGL(dkv_finish_kernel, dim3((unsigned)gsz), dim3(256), 0, st, dkv_ws, a.dk, a.dv, ldg, B * L, HKV * HD);
-    UG_CHECK_LAUNCH("ug_attn_bwd(dkv finish)");
-  } else {
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, dim3(wg_grid(a.nW, HKV, HKV, B)), dim3(256), 0, st, a);
-    UG_CHECK_LAUNCH("ug_attn_bwd(dkv)");
+  a.order = pl.dkv_order; a.dkv_heads = pl.dkv_heads;
+  switch (pl.dkv) {
+    case ug_plan::ATTN_DKV_DMA_SPLIT: hipLaunchKernelGGL(attn_bwd_dkv_dma_kernel, dim3(pl.dkv_grid), block, 0, st, a); break;
+    case ug_plan::ATTN_DKV_SPLIT: hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, dim3(pl.dkv_grid), block, 0, st, a); break;
+    case ug_plan::ATTN_DKV_WHOLE: hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, dim3(pl.dkv_grid), block, 0, st, a); break;
   }
-  if (int rc = rope_pass(dk, HKV)) return rc;
-  if (int rc = colsum_pass(dk, dbias_k, HKV * HD)) return rc;
-  if (int rc = colsum_pass(dv, dbias_v, HKV * HD)) return rc;
+  UG_CHECK_LAUNCH(dkv_ws ? "ug_attn_bwd(dkv split)" : "ug_attn_bwd(dkv)");
+  if (pl.finish == ug_plan::ATTN_FINISH_ROPE) {
+    hipLaunchKernelGGL(dkv_finish_rope_kernel, dim3(pl.finish_grid), block, 0, st, dkv_ws, a.dk, a.dv, ldg, tokens, (int)L, HKV,
+                       rope_cos, rope_sin, dbias_k, dbias_v, pl.rpb);
+    UG_CHECK_LAUNCH("ug_attn_bwd(dkv finish + rope)");
+  } else if (pl.finish == ug_plan::ATTN_FINISH_PLAIN) {
+    hipLaunchKernelGGL(dkv_finish_kernel, dim3(pl.finish_grid), block, 0, st, dkv_ws, a.dk, a.dv, ldg, tokens, HKV * HD);
+    UG_CHECK_LAUNCH("ug_attn_bwd(dkv finish)");
+  }
+  if (pl.rope_dk) { if (int rc = ug_rope(dk, rope_cos, rope_sin, tokens, L, ldg, HKV, HD, 1, st)) return rc; }
+  if (pl.colsum_dk) { if (int rc = ug_colsum_bf16(dk, ldg, dbias_k, tokens, HKV * HD, st)) return rc; }
+  if (pl.colsum_dv) { if (int rc = ug_colsum_bf16(dv, ldg, dbias_v, tokens, HKV * HD, st)) return rc; }
   return UG_OK;
 }

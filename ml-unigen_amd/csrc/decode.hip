@@ -1105,8 +1105,7 @@ void launch_ring_auto(hipStream_t st, const bf16_t* x, int ldx, int R, const bf1
     int NWc = cands[best].nw, KWc = cands[best].kw, xcd_chunks = 0;
     // many k-slabs (down projection: 35): the workgroups of a slab on one XCD -- 8 waves x 2 tiles, chunks x ceil(slabs / 8)
     // workgroups per XCD must fit its 32 CUs
-    static const int xcd_major = [] { const char* e = getenv("UNIGEN_DECODE_XCD_SLABS"); return e ? atoi(e) : 1; }();
-    if (xcd_major && R <= 16 && nslabs >= 16) {
+    if (R <= 16 && nslabs >= 16) {
       const int64_t chunks8 = (groups + 15) / 16;
       if (chunks8 * ((nslabs + 7) / 8) <= 32) { NWc = 8; KWc = 2; xcd_chunks = (int)chunks8; }
     }

@@ -11,8 +11,8 @@
 
 namespace {
 
-// Streaming accesses.  NT bit 0 = non-temporal stores, bit 1 = non-temporal loads; UNIGEN_EW_NT = four hex digits, AdamW |
-// rmsnorm_bwd | swiglu_bwd | swiglu_fwd.  Default 0x3032, measured inside the step (tools/probes/ab.sh env UNIGEN_EW_NT ...): the SwiGLU backward
+// Streaming accesses.  NT bit 0 = non-temporal stores, bit 1 = non-temporal loads; one constant per kernel family below (AdamW |
+// rmsnorm_bwd | swiglu_bwd | swiglu_fwd = 3 | 0 | 3 | 2), measured inside the step (tools/probes/ab.sh, probe builds with -DUG_EW_NT=0x....): the SwiGLU backward
 // reads gate | up and d(act) for the last time and nothing reads d(gate | up) before the two GEMMs that follow evict it anyway
 // (203 -> ~185 us per launch); the forward's gate | up is next read in the backward, its output at once by the down projection
 // (so only its loads); the optimizer touches every byte once per step.  Together 132.8 -> 131.7 ms per step; the RMSNorm
@@ -33,7 +33,7 @@ __device__ __forceinline__ void st_stream(T* p, T v) {
   else if constexpr ((NT & 1) && sizeof(T) == 8) __builtin_nontemporal_store(__builtin_bit_cast(ntu2_t, v), reinterpret_cast<ntu2_t*>(p));
   else *p = v;
 }
-static int ew_nt() { static const int v = [] { const char* e = getenv("UNIGEN_EW_NT"); return e ? (int)strtol(e, nullptr, 16) : 0x3032; }(); return v; }
+constexpr int NT_ADAMW = 3, NT_RMSNORM_BWD = 0, NT_SWIGLU_BWD = 3, NT_SWIGLU_FWD = 2;
 
 // =========================================================================== RMSNorm
 // y = bf16( w * (x * rsqrt(mean(x^2) + eps)) )      (transformers Qwen2RMSNorm.forward,
@@ -612,8 +612,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const bf16_t* __restri
 }
 
 inline int grid_for(int64_t work_items, int block = 256, int cap = 256 * 8) {
-  static const int cap_env = [] { const char* e = getenv("UNIGEN_EW_GRID_CAP"); return e ? atoi(e) : 0; }();
-  if (cap_env > 0) cap = cap_env;
   int64_t g = (work_items + block - 1) / block;
   if (g < 1) g = 1;
   if (g > cap) g = cap;
@@ -630,7 +628,7 @@ extern "C" int ug_rmsnorm_fwd(const float* x, const float* w, void* y, float* rs
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   // rows per wave of the register form (0: the two-pass kernel).  In the step (tools/probes/ab.sh env): 27.7 us two-pass, 21.0 at one
   // row per wave, 22.2 at two, 25.4 at four
-  static const int reg = [] { const char* e = getenv("UNIGEN_RN_FWD_REG"); return e ? atoi(e) : 1; }();
+  constexpr int reg = 1;
   if (reg > 0 && cols <= 2048 && !out_f32) {
     dim3 g2((unsigned)((rows + 4 * reg - 1) / (4 * reg)));
     hipLaunchKernelGGL((rmsnorm_fwd_reg_kernel<false, 8>), g2, block, 0, st, x, w, y, rstd, (int)rows, (int)cols, eps, reg);
@@ -646,25 +644,17 @@ extern "C" int ug_rmsnorm_bwd(const void* dy, const float* x, const float* rstd,
              "ug_rmsnorm_bwd: cols=%ld unsupported (multiple of 4, <= %d)", (long)cols, 64 * 4 * RN_MAXV);
   UG_REQUIRE(ug_aligned16(x) && ug_aligned16(w) && ug_aligned16(dres) && ((uintptr_t)dy & 7) == 0,
              "ug_rmsnorm_bwd: pointers must be aligned");
-  static const int rpb_env = [] { const char* e = getenv("UNIGEN_RN_RPB"); return e ? atoi(e) : 0; }();
   // ONE round of workgroups: the kernel's 182 registers leave two 4-wave workgroups per CU (512 slots), and 16 rows per workgroup --
   // round 3's choice, 771 workgroups for 12 336 rows -- is a full round plus a half-empty one.  Rows per workgroup = rows / 480 rounded
   // up to a multiple of 4 (28 at the benchmark shape: 441 workgroups, 7 rows per wave): element-wise family 15.5 -> 14.7 ms per step
   // (in-step sweep of 16 / 24 / 25 / 26 / 28 / 32 / 40 / 48: 15.5 / 16.1 / 14.8 / 14.8 / 14.7 / 14.6-14.8 / 15.0 / 15.6).
-  const int rpb = rpb_env > 0 ? rpb_env : (int)std::max<int64_t>(16, ((rows + 479) / 480 + 3) / 4 * 4);
+  const int rpb = (int)std::max<int64_t>(16, ((rows + 479) / 480 + 3) / 4 * 4);
   dim3 grid((unsigned)((rows + rpb - 1) / rpb)), block(256);
   UG_REQUIRE(((uintptr_t)dres_bf16 & 7) == 0, "ug_rmsnorm_bwd: dres_bf16 must be 8-byte aligned");
   // (a 6-slot instantiation for 1536 columns -- 148 instead of 182 registers, three waves per SIMD instead of two -- measured
   // SLOWER inside the step: 86 vs 78 us per launch, profiles/r03b vs r03a; the generic form stays)
-#define UG_RNB(NTV) hipLaunchKernelGGL((rmsnorm_bwd_kernel<RN_MAXV, NTV>), grid, block, 0, st, (const bf16_t*)dy, x, rstd, w, dres, dw, \
-                                      (bf16_t*)dres_bf16, (int)rows, (int)cols, rpb)
-  switch ((ew_nt() >> 8) & 0xf) {          // third hex digit
-    case 1: UG_RNB(1); break;
-    case 2: UG_RNB(2); break;
-    case 3: UG_RNB(3); break;
-    default: UG_RNB(0);
-  }
-#undef UG_RNB
+  hipLaunchKernelGGL((rmsnorm_bwd_kernel<RN_MAXV, NT_RMSNORM_BWD>), grid, block, 0, st, (const bf16_t*)dy, x, rstd, w, dres, dw,
+                     (bf16_t*)dres_bf16, (int)rows, (int)cols, rpb);
   UG_CHECK_LAUNCH("ug_rmsnorm_bwd");
   return UG_OK;
 }
@@ -686,12 +676,7 @@ extern "C" int ug_swiglu_fwd(const void* gate_up, void* act, int64_t tokens, int
   UG_REQUIRE(tokens > 0 && I % 8 == 0, "ug_swiglu_fwd: I=%ld must be a multiple of 8", (long)I);
   UG_REQUIRE(ug_aligned16(gate_up) && ug_aligned16(act), "ug_swiglu_fwd: alignment");
   dim3 grid(grid_for(tokens * (I / 8))), block(256);
-  switch (ew_nt() & 0xf) {
-    case 1: hipLaunchKernelGGL(swiglu_fwd_kernel<1>, grid, block, 0, st, (const bf16_t*)gate_up, (bf16_t*)act, tokens, (int)I); break;
-    case 2: hipLaunchKernelGGL(swiglu_fwd_kernel<2>, grid, block, 0, st, (const bf16_t*)gate_up, (bf16_t*)act, tokens, (int)I); break;
-    case 3: hipLaunchKernelGGL(swiglu_fwd_kernel<3>, grid, block, 0, st, (const bf16_t*)gate_up, (bf16_t*)act, tokens, (int)I); break;
-    default: hipLaunchKernelGGL(swiglu_fwd_kernel<0>, grid, block, 0, st, (const bf16_t*)gate_up, (bf16_t*)act, tokens, (int)I);
-  }
+  hipLaunchKernelGGL(swiglu_fwd_kernel<NT_SWIGLU_FWD>, grid, block, 0, st, (const bf16_t*)gate_up, (bf16_t*)act, tokens, (int)I);
   UG_CHECK_LAUNCH("ug_swiglu_fwd");
   return UG_OK;
 }
@@ -701,14 +686,7 @@ extern "C" int ug_swiglu_bwd(const void* gate_up, const void* dact, void* dgate_
   UG_REQUIRE(tokens > 0 && I % 8 == 0, "ug_swiglu_bwd: I=%ld must be a multiple of 8", (long)I);
   UG_REQUIRE(ug_aligned16(gate_up) && ug_aligned16(dact) && ug_aligned16(dgate_up), "ug_swiglu_bwd: alignment");
   dim3 grid(grid_for(tokens * (I / 8))), block(256);
-#define UG_SWB(NTV) hipLaunchKernelGGL(swiglu_bwd_kernel<NTV>, grid, block, 0, st, (const bf16_t*)gate_up, (const bf16_t*)dact, (bf16_t*)dgate_up, tokens, (int)I)
-  switch ((ew_nt() >> 4) & 0xf) {          // second hex digit: the backward
-    case 1: UG_SWB(1); break;
-    case 2: UG_SWB(2); break;
-    case 3: UG_SWB(3); break;
-    default: UG_SWB(0);
-  }
-#undef UG_SWB
+  hipLaunchKernelGGL(swiglu_bwd_kernel<NT_SWIGLU_BWD>, grid, block, 0, st, (const bf16_t*)gate_up, (const bf16_t*)dact, (bf16_t*)dgate_up, tokens, (int)I);
   UG_CHECK_LAUNCH("ug_swiglu_bwd");
   return UG_OK;
 }
@@ -767,37 +745,23 @@ extern "C" int ug_adamw_flat(float* p, const float* g, float* m, float* v, void*
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   // max_blocks > 0: a deliberately small grid (one 4-wave workgroup per CU; the lean kernel above) for an update that runs on a
   // side stream beside MFMA-bound kernels -- it leaves the register file and LDS to them and lives off spare HBM bandwidth
-  dim3 grid(max_blocks > 0 ? grid_for(n / 4 + 1, 256, max_blocks) : grid_for(n / 4 + 1)), block(256);
-  static const int lean = [] { const char* e = getenv("UNIGEN_ADAMW_LEAN"); return e ? atoi(e) : 1; }();
+  const dim3 block(256);
   // round 4: the pipelined small-grid kernel is also the fastest form ALONE (tools/probes/adamw_alone.py, 400 M elements: 6.14 TB/s on 256
   // workgroups against 5.35 for the whole-chip four-element kernel), so the default grid (max_blocks = 0) takes it too
-  static const int piped_default = [] { const char* e = getenv("UNIGEN_ADAMW_PIPED"); return e ? atoi(e) : 1; }();
-  if (max_blocks == 0 && lean && piped_default && n < (1LL << 29)) max_blocks = 256;
-  if (max_blocks > 0 && lean) {
-    const int wgs = lean > 1 ? lean : max_blocks;
-    dim3 lgrid(grid_for(n / 2 + 1, 256, wgs));
-    static const int piped = [] { const char* e = getenv("UNIGEN_ADAMW_PIPED"); return e ? atoi(e) : 1; }();
-    if (piped && n < (1LL << 29))
-      hipLaunchKernelGGL(adamw_lean2_kernel<3>, lgrid, block, 0, st, p, g, m, v, (bf16_t*)p_bf16, (uint32_t)n, lr, beta1, beta2, eps, weight_decay,
-                         (float)bc1, (float)sqrt(bc2), grad_scale);
-    else if ((ew_nt() >> 12) & 0xf)
-      hipLaunchKernelGGL(adamw_lean_kernel<3>, lgrid, block, 0, st, p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, weight_decay,
+  if (max_blocks == 0 && n < (1LL << 29)) max_blocks = 256;
+  if (max_blocks > 0) {
+    dim3 lgrid(grid_for(n / 2 + 1, 256, max_blocks));
+    if (n < (1LL << 29))
+      hipLaunchKernelGGL(adamw_lean2_kernel<NT_ADAMW>, lgrid, block, 0, st, p, g, m, v, (bf16_t*)p_bf16, (uint32_t)n, lr, beta1, beta2, eps, weight_decay,
                          (float)bc1, (float)sqrt(bc2), grad_scale);
     else
-      hipLaunchKernelGGL(adamw_lean_kernel<0>, lgrid, block, 0, st, p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, weight_decay,
+      hipLaunchKernelGGL(adamw_lean_kernel<NT_ADAMW>, lgrid, block, 0, st, p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, weight_decay,
                          (float)bc1, (float)sqrt(bc2), grad_scale);
     UG_CHECK_LAUNCH("ug_adamw_flat(lean)");
     return UG_OK;
   }
-#define UG_ADW(NTV) hipLaunchKernelGGL(adamw_kernel<NTV>, grid, block, 0, st, p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, \
-                     weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale)
-  switch ((ew_nt() >> 12) & 0xf) {         // fourth hex digit
-    case 1: UG_ADW(1); break;
-    case 2: UG_ADW(2); break;
-    case 3: UG_ADW(3); break;
-    default: UG_ADW(0);
-  }
-#undef UG_ADW
+  hipLaunchKernelGGL(adamw_kernel<NT_ADAMW>, dim3(grid_for(n / 4 + 1)), block, 0, st, p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps,
+                     weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale);
   UG_CHECK_LAUNCH("ug_adamw_flat");
   return UG_OK;
 }

@@ -34,7 +34,7 @@ FWD_WHOLE, GRAD_WHOLE = 8e-3, 2e-2       # the whole-tensor bars of test_attenti
 GRAD_ROW_BAR = {"dq": 4 * 3.50e-2, "dk": 4 * 9.08e-3, "dv": 4 * 4.31e-3}
 LSE_FACTOR = 8             # lse: absolute error <= 8 x the error of an fp32 evaluation of the same formula on the same inputs
 
-# (B, L, H, HKV) -> the kernels ug_attn_fwd / ug_attn_bwd select (conditions as they stand at the end of attention.hip;
+# (B, L, H, HKV) -> the kernels ug_attn_fwd / ug_attn_bwd select (conditions as they stand in csrc/attn_plan.h;
 # nW = ceil(L / 64) key tiles, nT = ceil(L / 128) 128-row query tiles, G = H / HKV):
 #   32-row forward and dQ kernels:  256 <= L <= 4096 and nT * H * B >= 512; 8-wave forward: L > 4096 and nT * H * B >= 512
 #   two heads per dK/dV workgroup:  G even and nW * (H / 2) * B >= 1024;  DMA dK/dV: L <= 4096
@@ -56,6 +56,27 @@ BIG_SHAPES = [
     (1, 4096, 16, 2),    # nT = 32: 32 * 16 = 512 >= 512 -> 32-row kernels at nW = 64: bit 63 of the vis / minem words; 64 * 8 = 512: one head
     (1, 4160, 16, 2),    # L > 4096, nT = 33: 528 >= 512 -> attn_fwd_kernel<8>, 16-row dQ, non-DMA split attn_bwd_dkv_kernel<true>
 ]
+# The comments above as data, held against csrc/attn_plan.h by tests/test_attn_plan_cpu.py (which also requires that the two lists
+# together reach every kernel and finish the plan can return): forward, dQ and dK/dV kernel, query heads per dK/dV workgroup
+# (0: the kernel without a split workspace does not read it), and the dK/dV finish when RoPE tables or dbias are given.  The
+# workspace is there when H > HKV (ops.attn_bwd).
+FWD64, FWD128, FWD32 = "attn_fwd_kernel<4>", "attn_fwd_kernel<8>", "attn_fwd32_kernel<4>"
+DQ16, DQ32 = "attn_bwd_dq_kernel", "attn_bwd_dq32_kernel<4>"
+DKV_DMA, DKV_SPLIT, DKV_WHOLE = "attn_bwd_dkv_dma_kernel", "attn_bwd_dkv_kernel<true>", "attn_bwd_dkv_kernel<false>"
+FIN_ROPE, FIN_PLAIN = "dkv_finish_rope_kernel", "dkv_finish_kernel"
+KERNELS = {
+    (2, 70, 2, 1): dict(fwd=FWD64, dq=DQ16, dkv=DKV_DMA, heads=1, finish=FIN_ROPE),
+    (3, 129, 6, 2): dict(fwd=FWD64, dq=DQ16, dkv=DKV_DMA, heads=1, finish=FIN_ROPE),
+    (29, 129, 24, 4): dict(fwd=FWD64, dq=DQ16, dkv=DKV_DMA, heads=2, finish=FIN_ROPE),
+    (35, 260, 12, 2): dict(fwd=FWD32, dq=DQ32, dkv=DKV_DMA, heads=2, finish=FIN_ROPE),
+    (22, 256, 12, 2): dict(fwd=FWD32, dq=DQ32, dkv=DKV_DMA, heads=1, finish=FIN_ROPE),
+    (22, 257, 12, 2): dict(fwd=FWD32, dq=DQ32, dkv=DKV_DMA, heads=1, finish=FIN_ROPE),
+    (3, 200, 4, 4): dict(fwd=FWD64, dq=DQ16, dkv=DKV_WHOLE, heads=0, finish=None),
+    (13, 260, 28, 4): dict(fwd=FWD32, dq=DQ32, dkv=DKV_DMA, heads=1, finish=FIN_ROPE),
+    (4, 130, 6, 3): dict(fwd=FWD64, dq=DQ16, dkv=DKV_DMA, heads=1, finish=FIN_PLAIN),
+    (1, 4096, 16, 2): dict(fwd=FWD32, dq=DQ32, dkv=DKV_DMA, heads=1, finish=FIN_ROPE),
+    (1, 4160, 16, 2): dict(fwd=FWD128, dq=DQ16, dkv=DKV_SPLIT, heads=1, finish=FIN_ROPE),
+}
 KINDS = ["leftpad", "band_sink", "band", "holes"]
 PADS = [130, 0, 1, 63, 64, 65, 2, 5, 17, 31, 3, 7]            # left-pad counts per batch row (clamped to L - 1), cycled
 

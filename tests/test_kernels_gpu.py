@@ -613,26 +613,32 @@ def test_adamw_small_grid_form_is_the_same_update(dev, n):
 def test_adamw_whole_chip_kernel_beyond_32_bit_indices(dev):
     """Flat runs of 2^29 elements and more keep the whole-chip four-element kernel (`adamw_kernel`, 64-bit indices; everything smaller
     runs the pipelined small-grid kernel since round 4): one update over 2^29 + 5 elements against the pipelined kernel on the two
-    halves of a copy -- the same element function, the same bits."""
+    halves of a copy -- the same element function, the same bits.  A third evaluation with max_blocks=256, the optimizer's own call
+    on a flat run that long, takes the small-grid two-element kernel with 64-bit indices (`adamw_lean_kernel`): the same bits again."""
     ops = _ops()
     n = (1 << 29) + 5
     gen = torch.Generator(device=dev).manual_seed(11)
     p0 = torch.randn(n, device=dev, generator=gen)
     g = torch.randn(n, device=dev, generator=gen)
-    outs = []
-    for split in (False, True):
+    want = None
+    for form in ("whole", "halves", "small_grid"):
         p = p0.clone(); m = torch.full((n,), 0.01, device=dev); v = torch.full((n,), 0.02, device=dev)
         pb = torch.zeros(n, dtype=torch.bfloat16, device=dev)
-        if not split:
+        if form == "whole":
             ops.adamw_flat_(p, g, m, v, pb, 1e-3, 0.9, 0.999, 1e-8, 0.01, 2)
-        else:
+        elif form == "halves":
             h = (n // 2) & ~7
             for lo, hi in ((0, h), (h, n)):
                 ops.adamw_flat_(p[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi], pb[lo:hi], 1e-3, 0.9, 0.999, 1e-8, 0.01, 2)
-        outs.append((p, m, v, pb))
-    for a, b in zip(*outs):
-        assert torch.equal(a, b)
-    del outs
+        else:
+            ops.adamw_flat_(p, g, m, v, pb, 1e-3, 0.9, 0.999, 1e-8, 0.01, 2, max_blocks=256)
+        if want is None:
+            want = (p, m, v, pb)
+            continue
+        for a, b in zip(want, (p, m, v, pb)):
+            assert torch.equal(a, b), form
+        del p, m, v, pb                  # (7 GB per evaluation: freed before the next one)
+    del want
 
 
 # ------------------------------------------------------------------ cross entropy

@@ -11,7 +11,7 @@
 # Every line of the command's stdout is prefixed with the value / variant; -o NAME tees everything to gpurun_out/NAME.txt.  Run on the
 # GPU box from the repo root (gpurun -- 'bash tools/probes/ab.sh ...').  Examples (the experiments of rounds 3-5 were these):
 #   ab.sh env UNIGEN_FUSED_ROPE "0 1" -r 3 -- python3 bench.py --no-cpu-baseline --no-ar --no-extra --steps 8
-#   ab.sh env UNIGEN_ATTN_DKV_HEADS "2 3 6" -- python3 tools/attn_bench.py
+#   ab.sh lib "ship dkv3 dkv6" -- python3 tools/attn_bench.py                          (after build_variant.py dkv3 attention.hip -DUG_ATTN_DKV_HEADS=3 ...)
 #   ab.sh lib "ship mo1 mo4" -r 3 -- env REPS=30 python3 tools/gemm_bench.py          (after build_variant.py mo1 gemm_bf16.hip -DUG_MFMA_ORDER=1 ...)
 #   ab.sh lib "ship adf1 adf2 adf8" -- python3 tools/ar_bench.py graph                 (attention-decode ablations, -DUG_ADF_ABLATE=n)
 #   ab.sh prof r05_ar -- python3 tools/ar_bench.py graph && python3 tools/ar_timeline.py gpurun_out/prof_r05_ar
