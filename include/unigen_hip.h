@@ -334,6 +334,35 @@ int ug_maskgit_step(const void* logits, int64_t ld, int64_t V, int64_t N, int64_
                     int64_t mask_len_sched, float temperature, int64_t* sampled, float* sel_ws, int64_t* next_cur,
                     int64_t* next_ids, uint8_t* masking_out, hipStream_t stream);
 
+/* ug_maskgit_step with a sampling temperature, top-k / top-p / min-p truncation and the drawn tokens' log-probabilities.  Every
+ * argument of ug_maskgit_step keeps its meaning (`temperature` stays the Gumbel temperature of the re-masking, which is unchanged);
+ * sample_temperature > 0, top_k >= 0 (0 or >= V: off), 0 < top_p <= 1 (1: off), 0 <= min_p <= 1 (0: off).
+ * Per masked position bi (cur_ids[bi] == mask_id), with c, u the bf16 logits of rows bi and N*n + bi taken to fp32:
+ *   v[e] = (guidance_scale * (c[e] - u[e]) + u[e]) * fp32(1 / sample_temperature)      (cfg == 0: v = c * fp32(1 / sample_temperature))
+ *   kept set = ug_ar_sample_filtered's, word for word: {v >= tau}, tau = max(tau_k, tau_p, tau_m); every value tied at the top-k value
+ *     is kept, top-p keeps or drops a run of equal values as a whole, the maximum is always kept;
+ *   sampled[bi] = inverse CDF in index order on u_sample[bi] over exp(v - max v), dropped entries counted as 0: always a kept token;
+ *   sel_ws[bi] = exp(v[tok] - max v) / (sum over the kept): the confidence that decides re-masking is the token's probability under
+ *     the distribution it was drawn from.
+ * logp (optional, fp32 [N*n][2], natural logs -- the pair ug_ar_sample_*_logp writes):
+ *   logp[2*bi]   = v[tok] - max v - log(sum over the kept e of exp(v[e] - max v));
+ *   logp[2*bi+1] = c[tok] - max c - log(sum over e < V of exp(c[e] - max c)): the conditional model's own log-softmax (no CFG, no
+ *     temperature, no truncation).
+ * stats (optional, fp32 [N*n][2]): stats[2*bi] = the smallest kept value, stats[2*bi+1] = the number of kept entries.
+ * Known positions behave as in ug_maskgit_step; their logp / stats slots are NOT written (a caller that zeroes logp once and passes it
+ * to every round ends with each position's entry from the last round that drew it).
+ * Every float sum runs in a fixed order and there are no float atomics: the call is a bit-reproducible function of its inputs.
+ * With every filter off and sample_temperature == 1 the draw is ug_maskgit_step's own kernel (instantiated with the two outputs riding
+ * along): sampled, sel_ws, next_cur, next_ids and masking_out are bit for bit ug_maskgit_step's, with or without logp / stats.
+ * Otherwise one workgroup per masked position reads its two rows once, stages the mixed row in LDS and runs the threshold search it
+ * shares with ug_ar_sample_filtered; that path needs V <= 8192 (an argument error beyond).  Any ld >= V and any base alignment
+ * work: 16-byte loads are used when ld % 8 == 0 and logits is 16-byte aligned, 2-byte loads otherwise. */
+int ug_maskgit_step_ex(const void* logits, int64_t ld, int64_t V, int64_t N, int64_t n, int cfg, float guidance_scale,
+                       const float* u_sample, const float* u_conf, const int64_t* cur_ids, int64_t mask_id, int64_t id_offset,
+                       int64_t mask_len_sched, float temperature, float sample_temperature, int64_t top_k, float top_p, float min_p,
+                       int64_t* sampled, float* sel_ws, int64_t* next_cur, int64_t* next_ids, uint8_t* masking_out, float* logp,
+                       float* stats, hipStream_t stream);
+
 /* one autoregressive sampling step (models/unigen.py:503-519) on the raw fp32 lm-head accumulator acc [2*bsz][ldacc]
  * (conditional rows, then unconditional; rounded to bf16 like the head's output; cleared on exit): CFG mix, /temperature,
  * softmax + inverse-CDF draw on uniforms[step*bsz + b] (or argmax if greedy), step = *pos_dev - pos0.  Writes tok[b],

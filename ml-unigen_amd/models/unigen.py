@@ -557,11 +557,37 @@ class UniGen(ModelMixin, ConfigMixin):
             generator: Optional[torch.Generator] = None,
             image_token_num_per_image: int = 256,
             text_vocab_size: int = 151936,
+            top_k: Optional[int] = 0,
+            top_p: Optional[float] = 1.0,
+            min_p: Optional[float] = 0.0,
+            sampling_temperature: Optional[float] = 1.0,
+            return_logprobs: bool = False,
             **kwargs,
     ):
         """Iterative parallel decoding; step-for-step the procedure of reference models/unigen.py:344-455
         (incl. its quirks: untempered multinomial, compounded Gumbel temperature, >=1 token re-masked
-        even on the last step, `sampled_ids` returned)."""
+        even on the last step, `sampled_ids` returned).
+        top_k / top_p / min_p / sampling_temperature: every round draws its tokens from the truncated, tempered distribution, in the
+        order temperature -> top-k -> top-p -> min-p -> draw (0 / 1.0 / 0.0 / 1.0 or None: off, the reference's draw).  The filters are
+        the value thresholds of `t2i_generate_ar` (ties at the top-k value all kept, a run of equal logits kept or dropped whole by
+        top-p), found on the device by the round's one fused launch (include/unigen_hip.h: ug_maskgit_step_ex); the confidence that
+        decides re-masking is the token's probability under the distribution it was drawn from.  `temperature` stays the
+        Gumbel / confidence temperature.
+        return_logprobs: returns (sampled_ids [bsz, n], logprobs [bsz, n], cond_logprobs [bsz, n]), the last two fp32 on the device.
+        Entry [b, i] belongs to the round that drew the returned token -- the last round at whose start position i was still masked:
+        logprobs is its natural-log probability under the drawn-from distribution (after CFG, sampling temperature and truncation),
+        cond_logprobs the conditional model's own log-softmax at it.  Positions already known in `input_ids` get 0.0.  One buffer,
+        zeroed once, that every round's launch overwrites at masked positions only: no extra pass over the logits, no host work per
+        round.
+        kwargs: incremental=False recomputes the prefix every round; trace=list receives (sampled_ids, next_ids) of every round,
+        logit_trace=list a clone of every round's bf16 code-book logits."""
+        top_k = 0 if top_k is None else top_k
+        top_p = 1.0 if top_p is None else float(top_p)
+        min_p = 0.0 if min_p is None else float(min_p)
+        sampling_temperature = 1.0 if sampling_temperature is None else float(sampling_temperature)
+        if not (isinstance(top_k, int) and top_k >= 0 and 0.0 < top_p <= 1.0 and 0.0 <= min_p <= 1.0 and sampling_temperature > 0.0):
+            raise UniGenHipError(f"t2i_generate: need an int top_k >= 0, 0 < top_p <= 1, 0 <= min_p <= 1 and sampling_temperature > 0 "
+                                 f"(got top_k={top_k!r}, top_p={top_p!r}, min_p={min_p!r}, sampling_temperature={sampling_temperature!r})")
         n = image_token_num_per_image
         mask_token_id = self.config.mask_token_id
         embed = self.llm.model.embed_tokens
@@ -599,6 +625,8 @@ class UniGen(ModelMixin, ConfigMixin):
                 and not bool((attention_mask[:, 0, :seg_start, seg_start:] == 0).any())
         sess = None
         trace = kwargs.get("trace", None)
+        logit_trace = kwargs.get("logit_trace", None)
+        logp = torch.zeros((bsz * n, 2), dtype=torch.float32, device=image_embeddings.device) if return_logprobs else None
         for step in range(timesteps):
             img = torch.cat([image_embeddings, image_embeddings]) if cfg else image_embeddings
             if incremental:
@@ -629,11 +657,19 @@ class UniGen(ModelMixin, ConfigMixin):
             # confidence + Gumbel noise, re-masking of the max(1, min(#unknown - 1, mask_len)) least confident positions
             u_dev = lg.device if generator is None else generator.device
             u = torch.rand((2, bsz, n), device=u_dev, generator=generator).to(lg.device)
-            sampled_ids, cur_ids, next_ids = ops.maskgit_step(lg.contiguous(), bsz, n, cfg, guidance_scale, u[0], u[1], cur_ids,
-                                                              mask_token_id, 0 if gen else text_vocab_size, mask_len, temperature)
+            lg = lg.contiguous()
+            if logit_trace is not None:
+                logit_trace.append(lg.clone())
+            sampled_ids, cur_ids, next_ids = ops.maskgit_step(lg, bsz, n, cfg, guidance_scale, u[0], u[1], cur_ids,
+                                                              mask_token_id, 0 if gen else text_vocab_size, mask_len, temperature,
+                                                              top_k=top_k, top_p=top_p, min_p=min_p,
+                                                              sample_temperature=sampling_temperature, logp=logp)
             if trace is not None:                        # parity tests follow the trajectory round by round
                 trace.append((sampled_ids.clone(), next_ids.clone()))
             image_embeddings = self.get_gen_embed(next_ids).to(input_embeddings.dtype) if gen else embed(next_ids)
+        if return_logprobs:
+            logp = logp.view(bsz, n, 2)
+            return sampled_ids, logp[..., 0].contiguous(), logp[..., 1].contiguous()
         return sampled_ids
 
     # ------------------------------------------------------------------ autoregressive generation

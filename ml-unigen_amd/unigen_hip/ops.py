@@ -717,23 +717,43 @@ def decode_finish_resid_norm_ord_(parts, x, w, xn, eps, advance=None):
 
 # ------------------------------------------------------------------------------------ MaskGIT sampler
 def maskgit_step(logits, N, n, cfg, guidance_scale, u_sample, u_conf, cur_ids, mask_id, id_offset, mask_len_sched, temperature,
-                 want_masking=False):
+                 want_masking=False, top_k=0, top_p=1.0, min_p=0.0, sample_temperature=1.0, logp=None, stats=None):
     """One parallel-decoding round on bf16 code-book logits [(2 if cfg else 1)*N*n, V(+pad)] -> (sampled, next_cur,
-    next_ids[, masking]) int64 [N, n]; see include/unigen_hip.h."""
+    next_ids[, masking]) int64 [N, n]; see include/unigen_hip.h.
+    top_k / top_p / min_p / sample_temperature: truncated, tempered draw (ug_maskgit_step_ex; `temperature` stays the Gumbel
+    temperature of the re-masking).  logp / stats: optional fp32 [N*n, 2] device buffers that the launch writes at masked positions
+    only -- (log-probability under the drawn-from distribution, conditional log-softmax) and (smallest kept value, kept count).
+    With every one of them at its default this is the ug_maskgit_step call."""
     V = logits.shape[-1]
     logits = logits.reshape(-1, V)
     if logits.dtype != torch.bfloat16 or logits.stride(1) != 1:
         raise _l.UniGenHipError("maskgit_step: logits must be bf16 with contiguous rows")
+    plain = top_k == 0 and top_p == 1.0 and min_p == 0.0 and sample_temperature == 1.0 and logp is None and stats is None
+    if not plain:
+        if not (isinstance(top_k, int) and top_k >= 0 and 0.0 < top_p <= 1.0 and 0.0 <= min_p <= 1.0 and sample_temperature > 0.0):
+            raise _l.UniGenHipError(f"maskgit_step: need an int top_k >= 0, 0 < top_p <= 1, 0 <= min_p <= 1 and sample_temperature > 0 "
+                                    f"(got top_k={top_k!r}, top_p={top_p!r}, min_p={min_p!r}, sample_temperature={sample_temperature!r})")
+        if logp is not None:
+            _logp_buffer(logp, (N * n, 2))
+        if stats is not None:
+            _logp_buffer(stats, (N * n, 2), "stats")
     dev = logits.device
     sampled = torch.empty((N, n), dtype=torch.int64, device=dev)
     next_cur, next_ids = torch.empty_like(sampled), torch.empty_like(sampled)
     sel = torch.empty((N, n), dtype=torch.float32, device=dev)
     masking = torch.empty((N, n), dtype=torch.uint8, device=dev) if want_masking else None
     cur_ids = cur_ids.to(torch.int64).contiguous()
-    _l.check(_l.load().ug_maskgit_step(_p(logits), logits.stride(0), V, N, n, int(bool(cfg)), float(guidance_scale),
-                                       _p(u_sample.contiguous()), _p(u_conf.contiguous()), _p(cur_ids), int(mask_id),
-                                       int(id_offset), int(mask_len_sched), float(temperature), _p(sampled), _p(sel), _p(next_cur),
-                                       _p(next_ids), _p(masking), _stream()), "ug_maskgit_step")
+    if plain:
+        _l.check(_l.load().ug_maskgit_step(_p(logits), logits.stride(0), V, N, n, int(bool(cfg)), float(guidance_scale),
+                                           _p(u_sample.contiguous()), _p(u_conf.contiguous()), _p(cur_ids), int(mask_id),
+                                           int(id_offset), int(mask_len_sched), float(temperature), _p(sampled), _p(sel), _p(next_cur),
+                                           _p(next_ids), _p(masking), _stream()), "ug_maskgit_step")
+    else:
+        _l.check(_l.load().ug_maskgit_step_ex(_p(logits), logits.stride(0), V, N, n, int(bool(cfg)), float(guidance_scale),
+                                              _p(u_sample.contiguous()), _p(u_conf.contiguous()), _p(cur_ids), int(mask_id),
+                                              int(id_offset), int(mask_len_sched), float(temperature), float(sample_temperature),
+                                              int(top_k), float(top_p), float(min_p), _p(sampled), _p(sel), _p(next_cur), _p(next_ids),
+                                              _p(masking), _p(logp), _p(stats), _stream()), "ug_maskgit_step_ex")
     return (sampled, next_cur, next_ids, masking.bool()) if want_masking else (sampled, next_cur, next_ids)
 
 
@@ -778,11 +798,11 @@ def ar_sample_filtered_(acc, bsz, V, guidance_scale, temperature, greedy, unifor
                  "ug_ar_sample_filtered_logp")
 
 
-def _logp_buffer(logp, shape):
+def _logp_buffer(logp, shape, what="logp"):
     """the log-probability output of a sampler launch: fp32, contiguous, on the device, of exactly `shape` (the kernels index it by
     row and step, so anything else would be written out of bounds)"""
     if not (torch.is_tensor(logp) and logp.is_cuda and logp.dtype == torch.float32 and logp.is_contiguous() and tuple(logp.shape) == tuple(shape)):
-        raise _l.UniGenHipError(f"logp must be a contiguous fp32 device tensor of shape {tuple(shape)}")
+        raise _l.UniGenHipError(f"{what} must be a contiguous fp32 device tensor of shape {tuple(shape)}")
     return logp
 
 
