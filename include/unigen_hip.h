@@ -200,6 +200,19 @@ int ug_rope_at(void* qkv, const float* cos_tab, const float* sin_tab, int64_t ro
 int ug_attn_decode(const void* q, int64_t ldq, const void* cache_k, const void* cache_v, const uint8_t* key_valid,
                    void* o, int64_t ldo, int64_t rows, int H, int HKV, int head_dim, int64_t Tmax,
                    const int* len_dev, float scale, hipStream_t stream);
+/* Prefill onto a filled cache (a shared prompt prefix, chunked prefill, the next turn of a conversation): causal attention of S
+ * new query rows per cache row against the keys and values IN the cache.  Query (r, s) is row r*S + s of q (head h at column
+ * h*128, row stride ldq) and sits at position P + s; it attends to key t of cache row r iff t <= P + s and (key_valid is null or
+ * key_valid[r*Tmax + t] != 0).  The caller has already stored the new keys and values at positions P .. P+S-1 (ug_kv_store with
+ * pos_host = P).  P >= 0 is a host int (prefill is not captured), P + S <= Tmax.  o: bf16 [rows*S, ldo], every element written;
+ * a query that sees no key gets o = 0.  Forward only, no lse, no atomics: the same bits on every run.
+ * Masked keys inside a staged 64-key tile are still multiplied by exact-zero probabilities (as at ug_attn_fwd), so the cache
+ * positions [0, round_up(P+S, 64)) clipped to Tmax must hold FINITE values in both caches, whatever the mask hides (a zero-
+ * initialised cache does). */
+int ug_attn_prefill_cached(const void* q, int64_t ldq, const void* cache_k, const void* cache_v,
+                           const uint8_t* key_valid /* [rows][Tmax] or null */, void* o, int64_t ldo,
+                           int64_t rows, int64_t S, int64_t P, int H, int HKV, int head_dim, int64_t Tmax,
+                           float scale, hipStream_t stream);
 /* weight-streaming GEMV for <= 32 activation rows: acc[r*acc_stride_r + n*acc_stride_n] += sum_k x[r][k] W[n][k]
  * (fp32 atomics into a zeroed accumulator; the decode-time form of every nn.Linear of the backbone,
  * models/unigen.py:496-502).  The decode path keeps row-major accumulators (acc_stride_n = 1). */

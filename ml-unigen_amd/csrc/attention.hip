@@ -397,6 +397,108 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void attn_fwd_kernel(Attn
   }
 }
 
+// ================================================================== forward onto the decode cache (ug_attn_prefill_cached)
+// attn_fwd_kernel<4> with the keys and values read from the decode cache [rows][HKV][Tmax][128] instead of the q | k | v rows:
+// S new query rows per cache row at positions P .. P + S - 1, query s sees key t iff t <= P + s and key_valid[row][t] (or null).
+// The mask word of attn_fwd_kernel is not read but built per lane from that compare and the row's validity bytes; the key-tile
+// loop ends at the last tile the workgroup's last query row can see (uniform over the workgroup), and a wave skips the arithmetic
+// of the tiles that lie wholly past its own last row.  No lse, no atomics: the same bits on every run.
+struct AttnCachedArgs {
+  const bf16_t* q; const bf16_t* ck; const bf16_t* cv;   // q row (r*S+s), head h at +h*128, row stride ldq; caches [rows][HKV][Tmax][128]
+  const uint8_t* key_valid;                              // [rows][Tmax] or null
+  bf16_t* o;                                             // [rows*S, ldo]
+  int64_t ldq, ldo;
+  int rows, S, P, H, HKV, Tmax;
+  float scale;
+};
+
+__global__ __launch_bounds__(256, 2) void attn_prefill_cached_kernel(AttnCachedArgs p) {
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[64 * RM_LD];
+  __shared__ __attribute__((aligned(16))) bf16_t Vs[64 * RM_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
+  const WgCoord wc = wg_coord((int)blockIdx.x, (p.S + 63) / 64, p.H, p.HKV, p.rows);
+  if (!wc.ok) return;
+  const int qt = wc.tile, h = wc.h, b = wc.b;
+  const int hk = h / (p.H / p.HKV);
+  const int qs = qt * 64 + wave * 16 + (lane & 15);             // this lane's query (column of S^T), index into the S new rows
+  const int qs_c = min(qs, p.S - 1);
+  const int lim = p.P + qs_c;                                    // last key position this lane's query sees
+  const bf16_t* qseq = p.q + (int64_t)b * p.S * p.ldq + h * HD;
+  const bf16_t* kseq = p.ck + ((int64_t)b * p.HKV + hk) * p.Tmax * HD;
+  const bf16_t* vseq = p.cv + ((int64_t)b * p.HKV + hk) * p.Tmax * HD;
+  const uint8_t* kv = p.key_valid ? p.key_valid + (int64_t)b * p.Tmax : nullptr;
+
+  bf16x8_t qf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+    qf[ks] = *reinterpret_cast<const bf16x8_t*>(qseq + (int64_t)qs_c * p.ldq + ks * 32 + g * 8);
+
+  f32x4_t ot[8];
+#pragma unroll
+  for (int d = 0; d < 8; ++d) ot[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float m_i = -INFINITY, l_i = 0.f;
+  const int nt = (p.P + min(qt * 64 + 63, p.S - 1)) / 64 + 1;           // key tiles the workgroup's last query row reaches
+  const int wave_lim = p.P + min(qt * 64 + wave * 16 + 15, p.S - 1);    // last key position any row of this wave sees
+
+  for (int t = 0; t < nt; ++t) {
+    __syncthreads();
+    stage_rm<256>(Ks, kseq, HD, t * 64, p.Tmax, tid);
+    stage_rm<256>(Vs, vseq, HD, t * 64, p.Tmax, tid);         // rows past Tmax repeat the last one: their probabilities are exact zeros
+    __syncthreads();
+    if (t * 64 > wave_lim) continue;                            // wave-uniform: these keys all lie past this wave's rows
+
+    f32x4_t st[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      st[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+        st[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rm(Ks, j, ks, lane), qf[ks], st[j], 0, 0, 0);
+    }
+    float mloc = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = t * 64 + j * 16 + g * 4 + r;
+        bool on = key <= lim;
+        if (kv) on = on && kv[min(key, p.Tmax - 1)] != 0;
+        const float s = on ? st[j][r] * p.scale : -INFINITY;
+        st[j][r] = s;
+        mloc = fmaxf(mloc, s);
+      }
+    mloc = group_max(mloc);
+    const float m_new = fmaxf(m_i, mloc);
+    const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+    const float alpha = __expf(m_i - m_use);
+    float rs = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { const float e = __expf(st[j][r] - m_use); st[j][r] = e; rs += e; }
+    rs = group_sum(rs);
+    l_i = l_i * alpha + rs;
+    m_i = m_new;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) { ot[d][0] *= alpha; ot[d][1] *= alpha; ot[d][2] *= alpha; ot[d][3] *= alpha; }
+    const bf16x8_t pf0 = pack_p(st[0], st[1]), pf1 = pack_p(st[2], st[3]);
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      ot[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_trr(Vs, d, 0, lane), pf0, ot[d], 0, 0, 0);
+      ot[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_trr(Vs, d, 1, lane), pf1, ot[d], 0, 0, 0);
+    }
+  }
+  if (qs < p.S) {
+    const float inv = (l_i > 0.f) ? 1.f / l_i : 0.f;
+    bf16_t* orow = p.o + ((int64_t)b * p.S + qs) * p.ldo + h * HD;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      uint2 w; w.x = pack_bf2(ot[d][0] * inv, ot[d][1] * inv); w.y = pack_bf2(ot[d][2] * inv, ot[d][3] * inv);
+      *reinterpret_cast<uint2*>(orow + d * 16 + g * 4) = w;
+    }
+  }
+}
+
 // ================================================================== forward, 32 query rows per wave (round 3)
 // The same S^T formulation on v_mfma_f32_32x32x16_bf16: a wave owns 32 query rows (lane = query column n = lane & 31, key half
 // hh = lane >> 5), a workgroup of NW waves 32 * NW rows.  Against the 16-row kernel above, per query row: half the LDS fragment
@@ -1451,6 +1553,26 @@ extern "C" int ug_attn_fwd(const void* q, const void* k, const void* v, int64_t 
     case ug_plan::ATTN_FWD_4: hipLaunchKernelGGL(attn_fwd_kernel<4>, grid, block, 0, st, a); break;
   }
   UG_CHECK_LAUNCH("ug_attn_fwd");
+  return UG_OK;
+}
+
+extern "C" int ug_attn_prefill_cached(const void* q, int64_t ldq, const void* cache_k, const void* cache_v,
+                                      const uint8_t* key_valid, void* o, int64_t ldo, int64_t rows, int64_t S, int64_t P, int H,
+                                      int HKV, int head_dim, int64_t Tmax, float scale, hipStream_t st) {
+  UG_REQUIRE(head_dim == HD, "ug_attn_prefill_cached: head_dim %d unsupported (this build is specialised for 128)", head_dim);
+  UG_REQUIRE(H > 0 && HKV > 0 && H % HKV == 0, "ug_attn_prefill_cached: H=%d not a multiple of HKV=%d", H, HKV);
+  UG_REQUIRE(rows > 0 && S > 0 && P >= 0 && q && cache_k && cache_v && o, "ug_attn_prefill_cached: bad args");
+  UG_REQUIRE(P + S <= Tmax && Tmax < (1ll << 31) && rows * S < (1ll << 31),
+             "ug_attn_prefill_cached: P=%ld + S=%ld must not exceed Tmax=%ld", (long)P, (long)S, (long)Tmax);
+  UG_REQUIRE(ldq % 8 == 0 && ldq >= (int64_t)H * HD && ldo % 4 == 0 && ldo >= (int64_t)H * HD && ug_aligned16(q) &&
+                 ug_aligned16(cache_k) && ug_aligned16(cache_v) && ((uintptr_t)o & 7) == 0,
+             "ug_attn_prefill_cached: alignment / row strides");
+  AttnCachedArgs a{};
+  a.q = (const bf16_t*)q; a.ck = (const bf16_t*)cache_k; a.cv = (const bf16_t*)cache_v; a.key_valid = key_valid;
+  a.o = (bf16_t*)o; a.ldq = ldq; a.ldo = ldo;
+  a.rows = (int)rows; a.S = (int)S; a.P = (int)P; a.H = H; a.HKV = HKV; a.Tmax = (int)Tmax; a.scale = scale;
+  hipLaunchKernelGGL(attn_prefill_cached_kernel, dim3(ug_plan::wg_grid((S + 63) / 64, H, HKV, rows)), dim3(256), 0, st, a);
+  UG_CHECK_LAUNCH("ug_attn_prefill_cached");
   return UG_OK;
 }
 

@@ -147,6 +147,80 @@ def with_repetition_penalty(pick, emit, penalty, seen):
     return (lambda last: pick(apply_repetition_penalty(last, seen, penalty))), emit_and_mark
 
 
+MMU_MAX_ROWS = 32
+
+
+class MmuPrefix:
+    """A prompt prefix prefilled once and shared by many continuations (`UniGen.mmu_prefix`): a one-row DecodeState whose first P
+    cache positions hold the prefix's keys / values of every layer, P itself, the key validity of the prefix mask's last row (bool
+    [1, P]: what every later position sees of the prefix), and the prefix's ids (long [1, P]; None once any part of it came as
+    embeddings) for the repetition penalty.  `mmu_generate_batch(prefix=...)` / `mmu_generate(prefix=...)` read it and leave it
+    unchanged; `extend` grows it in place.  The object belongs to the model, device and WEIGHTS it was built with, and to the
+    caller: nothing in the model keeps or drops it (`drop_decode_session()` does not touch it)."""
+
+    def __init__(self, model, st, P, key_valid, ids):
+        self.model, self.engine, self.device = model, model.llm.engine, model.llm.engine.device
+        self.st, self.P, self.key_valid, self.ids = st, int(P), key_valid, ids
+        self.all_valid = True if key_valid is None else bool(key_valid.all())
+
+    @property
+    def capacity(self):
+        return self.st.Tmax
+
+    @torch.no_grad()
+    def extend(self, idx=None, input_embeddings=None):
+        """Append a causal continuation of S positions (ids [1, S] or embeddings [1, S, H]) to the prefix through
+        Qwen2Engine.prefill_onto: chunked prefill, or the next turn of a conversation on one row.  The new positions see what the
+        prefix mask's last row saw plus everything appended since.  Beyond `capacity` it raises.  -> self."""
+        if (idx is None) == (input_embeddings is None):
+            raise UniGenHipError("MmuPrefix.extend: give idx or input_embeddings")
+        new = idx if input_embeddings is None else input_embeddings
+        if new.shape[0] != 1 or new.shape[1] < 1:
+            raise UniGenHipError(f"MmuPrefix.extend: one row of at least one position, got {tuple(new.shape)}")
+        S = int(new.shape[1])
+        if self.P + S > self.capacity:
+            raise UniGenHipError(f"MmuPrefix.extend: {self.P} + {S} positions exceed the prefix's capacity of {self.capacity}")
+        x = (self.model.llm.model.embed_tokens(idx) if input_embeddings is None else input_embeddings).float()
+        ones = torch.ones((1, S), dtype=torch.bool, device=self.key_valid.device)
+        key_valid = torch.cat([self.key_valid, ones], dim=1)
+        self.engine.prefill_onto(self.st, x, self.P, None if self.all_valid else key_valid)
+        self.engine.check_errors()
+        self.ids = None if self.ids is None or idx is None else torch.cat([self.ids, idx.to(self.ids.device).long()], dim=1)
+        self.P, self.key_valid = self.P + S, key_valid
+        return self
+
+
+def check_mmu_prefix_call(who, engine, prefix, idx, input_embeddings, attention_mask, tail_valid):
+    """The argument checks of a generation call that takes `prefix`, all on the host and before anything is launched
+    -> (rows, tail length, tail_valid as a bool tensor or None)."""
+    if not isinstance(prefix, MmuPrefix):
+        raise UniGenHipError(f"{who}: prefix must be the object UniGen.mmu_prefix returns, got {type(prefix).__name__}")
+    if prefix.engine is not engine:
+        raise UniGenHipError(f"{who}: the prefix was built by another model")
+    if (idx is None) == (input_embeddings is None):
+        raise UniGenHipError(f"{who}: with a prefix, give the rows' tails as idx [R, S] or input_embeddings [R, S, H]")
+    tail = idx if input_embeddings is None else input_embeddings
+    pd, td = torch.device(prefix.device), tail.device
+    if td.type != pd.type or (td.index is not None and pd.index is not None and td.index != pd.index):
+        raise UniGenHipError(f"{who}: the prefix lives on another device ({pd}) than the tails ({td})")
+    if tail.dim() != (2 if input_embeddings is None else 3) or tail.shape[1] < 1:
+        raise UniGenHipError(f"{who}: the tails must be [R, S] ids or [R, S, H] embeddings with S >= 1, got {tuple(tail.shape)}")
+    R, S = int(tail.shape[0]), int(tail.shape[1])
+    if R < 1 or R > MMU_MAX_ROWS:
+        raise UniGenHipError(f"{who}: {R} rows (at most {MMU_MAX_ROWS} per call)")
+    if attention_mask is not None:
+        raise UniGenHipError(f"{who}: a dense attention_mask cannot be combined with a prefix (the tails are causal; mark their "
+                             f"left pads with tail_valid)")
+    if tail_valid is not None:
+        tail_valid = torch.as_tensor(tail_valid)
+        if tuple(tail_valid.shape) != (R, S):
+            raise UniGenHipError(f"{who}: tail_valid must be [{R}, {S}], got {tuple(tail_valid.shape)}")
+        tail_valid = tail_valid != 0
+        if not bool(tail_valid.any(0).all()):
+            raise UniGenHipError(f"{who}: a tail position is a pad in every row (left-pad the tails to the longest one only)")
+    return R, S, tail_valid
+
+
 class UniGen(ModelMixin, ConfigMixin):
     _supports_gradient_checkpointing = True
 
@@ -677,7 +751,8 @@ class UniGen(ModelMixin, ConfigMixin):
         """Release the decode step kept from the last `t2i_generate_ar` call: the static KV cache of every layer (rows x (prefix + n)
         tokens), the decode scratch, and the captured graph with its private memory pool -- hundreds of MB that otherwise stay
         allocated until a call with different shapes replaces them.  `train(True)` calls this (periodic evaluation inside a training
-        run must not keep generation buffers for the rest of it); `UNIGEN_AR_GRAPH_CACHE=0` disables keeping a session at all."""
+        run must not keep generation buffers for the rest of it); `UNIGEN_AR_GRAPH_CACHE=0` disables keeping a session at all.
+        Prefix objects (`mmu_prefix`) are not touched: the caller owns them and drops them by dropping the reference."""
         eng = getattr(getattr(self, "llm", None), "engine", None)
         if eng is not None:
             eng._ar_session = None
@@ -965,9 +1040,50 @@ class UniGen(ModelMixin, ConfigMixin):
 
     # ------------------------------------------------------------------ text decoding for understanding
     @torch.no_grad()
+    def mmu_prefix(self, idx=None, input_embeddings=None, attention_mask=None, capacity=None):
+        """Prefill one prompt prefix (ids [1, P] or embeddings [1, P, H]) ONCE, for many continuations: the rating loop of CoT-V asks
+        several questions about one image, and every row of such a call starts with the same [system | image] positions.
+        attention_mask: the prefix's dense additive [1, 1, P, P] mask, any the reference builds (the mmu mask with its bidirectional
+        image block, ...); None: causal.  The prefix is prefilled under it by the ordinary prefill; every later position sees the
+        keys the mask's LAST row sees.  capacity: cache positions of the object (default: P rounded up to 128) -- what `extend` may
+        grow it to; calls that take the prefix copy its rows into their own state and need no spare capacity.
+        -> MmuPrefix, for `mmu_generate_batch(prefix=...)`, `mmu_generate(prefix=...)` and its own `extend`.  The caller owns it:
+        `drop_decode_session()` and `train()` do not touch it, and it is only valid for the weights it was built with."""
+        from unigen_hip.qwen2 import DecodeState
+        if (idx is None) == (input_embeddings is None):
+            raise UniGenHipError("mmu_prefix: give idx [1, P] or input_embeddings [1, P, H]")
+        src = idx if input_embeddings is None else input_embeddings
+        if src.shape[0] != 1 or src.shape[1] < 1:
+            raise UniGenHipError(f"mmu_prefix: one row of at least one position, got {tuple(src.shape)}")
+        P = int(src.shape[1])
+        if attention_mask is not None and tuple(attention_mask.shape) != (1, 1, P, P):
+            raise UniGenHipError(f"mmu_prefix: attention_mask must be the prefix's dense [1, 1, {P}, {P}] additive mask")
+        cap = ops.round_up(P, 128) if capacity is None else int(capacity)
+        if cap < P:
+            raise UniGenHipError(f"mmu_prefix: capacity {cap} is below the prefix length {P}")
+        eng = self.llm.engine
+        prompt = (self.llm.model.embed_tokens(idx) if input_embeddings is None else input_embeddings).float()
+        dev = prompt.device
+        mb = eng.mask_bits(attention_mask, 1, P)
+        key_valid = torch.ones((1, P), dtype=torch.bool, device=dev) if attention_mask is None else (attention_mask[:, 0, -1, :] == 0).to(dev)
+        st = DecodeState(eng.dims, 1, cap, dev)
+        eng.prefill(st, prompt, mask_bits=mb)
+        eng.check_errors()
+        return MmuPrefix(self, st, P, key_valid, None if idx is None else idx.to(dev).long())
+
+    def _prefill_after_prefix(self, st, prefix, tails, key_valid):
+        """the prefill of a call that takes a prefix: the prefix's keys / values of every layer into positions [0, P) of every row of
+        `st`, then the rows' tails [R, S, H] onto them (Qwen2Engine.prefill_onto) -> final-norm hidden of the last tail position"""
+        P = prefix.P
+        for i in range(len(st.k)):
+            st.k[i][:, :, :P].copy_(prefix.st.k[i][:, :, :P])          # (one row, broadcast to the call's rows)
+            st.v[i][:, :, :P].copy_(prefix.st.v[i][:, :, :P])
+        return self.llm.engine.prefill_onto(st, tails, P, key_valid)
+
+    @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
                      top_k=None, eot_token=None, use_cache=True, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0,
-                     return_logprobs=False, trace=None):
+                     return_logprobs=False, trace=None, prefix=None):
         """Greedy / top-k text continuation (reference models/unigen.py:523-581).  The reference re-runs the whole
         growing sequence every step and extends the additive mask by one row that copies the previous last row;
         here the prompt is prefilled once under its mask into the static KV cache and every new token is one decode
@@ -981,11 +1097,26 @@ class UniGen(ModelMixin, ConfigMixin):
         sees, nothing with an `input_embeddings` prompt.  The recompute form raises for a penalty other than 1.
         return_logprobs: returns (token list, fp32 1-D device tensor of the same length): every token's log-probability as in `generate`
         (temperature 0: the greedy form; temperature > 0: behind temperature and top-k).  Cached form only.
-        trace: a list that receives every eager on-device step's raw fp32 head logits (use_graph=False)."""
+        trace: a list that receives every eager on-device step's raw fp32 head logits (use_graph=False).
+        prefix: an `mmu_prefix` object; `idx` / `input_embeddings` are then only the continuation [1, S], which is causal (no
+        attention_mask) and sees of the prefix what its mask's last row saw.  Cached form only; everything else as without."""
         from unigen_hip.qwen2 import resolve_deterministic
+        if prefix is not None:
+            check_mmu_prefix_call("mmu_generate", self.llm.engine, prefix, idx, input_embeddings, attention_mask, None)
+            if (idx if input_embeddings is None else input_embeddings).shape[0] != 1:
+                raise UniGenHipError("mmu_generate: one row per call (mmu_generate_batch takes several)")
+            if not use_cache:
+                raise UniGenHipError("mmu_generate: a prefix needs the cached form (use_cache=True)")
         penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate")
         det = resolve_deterministic(deterministic)
         self.llm.engine.last_decode_deterministic = det
+        if prefix is not None:
+            dev_loop = self._text_on_device(on_device, "mmu_generate", 1, True, eot_token, max_new_tokens)
+            self.llm.engine.last_text_decode_on_device = dev_loop
+            tokens, _, steps, logp = self._mmu_decode(idx, input_embeddings, None, max_new_tokens, temperature, top_k, eot_token, det,
+                                                      on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace,
+                                                      return_logprobs=bool(return_logprobs), prefix=prefix)
+            return (list(tokens[0, :steps]), logp[0, :steps].clone()) if return_logprobs else list(tokens[0, :steps])
         cached = bool(use_cache and attention_mask is not None and attention_mask.shape[0] == 1)
         dev_loop = self._text_on_device(on_device, "mmu_generate", 1, cached, eot_token, max_new_tokens)
         self.llm.engine.last_text_decode_on_device = dev_loop
@@ -1057,7 +1188,8 @@ class UniGen(ModelMixin, ConfigMixin):
         raise UniGenHipError(f"{who}: on_device=True cannot serve this call: {why}")
 
     def _decode_text_on_device(self, prompt, max_new_tokens, det, key_valid=None, mask_bits=None, sampling=None, stop=(), pad_token_id=None,
-                               generator=None, use_graph=True, trace=None, repetition_penalty=1.0, prompt_ids=None, return_logprobs=False):
+                               generator=None, use_graph=True, trace=None, repetition_penalty=1.0, prompt_ids=None, return_logprobs=False,
+                               prefix=None, prompt_valid=None):
         """The token loop of `text_token_loop` + `emit_until_stop` with nothing but launches per token: prefill, token 0 eagerly from
         the prefill's hidden state (GEMV head + pick), then unigen_hip/qwen2.py: decode_loop (step 1 eagerly, step 2 captured, replays
         from there).  The pick launch applies the stop rule on the device; with stop ids the host reads `remaining` every 8 tokens and
@@ -1074,11 +1206,19 @@ class UniGen(ModelMixin, ConfigMixin):
         outside the captured step.  p == 1 allocates and launches nothing.
         return_logprobs: the session owns a log-probability buffer and its pick launches are the entry points that fill it (part of the
         session key: such a call never replays the graph of a call without it, nor the reverse).
+        prefix (an MmuPrefix): `prompt` holds only the rows' tails [R, S, H]; the prompt is prefix + tail (L = P + S positions, which
+        is what key_valid [R, L] and prompt_ids [R, L] cover) and the prefill is the prefix's rows copied into the session's cache
+        plus Qwen2Engine.prefill_onto on the tails.  The session key needs nothing more: rows, capacity and the presence of
+        key_valid cover it, and the copy rewrites every prefix position of a reused session.
+        prompt_valid [R, L]: the positions of prompt_ids that count for the penalty (default: key_valid).
         -> (tokens int64 [R, steps], lengths int64 [R], steps, log-probabilities fp32 [R, steps] or None)."""
         from unigen_hip.qwen2 import TextDecodeSession, decode_loop, put_session, take_session
         eng = self.llm.engine
         dev = eng.device
         R, L, _ = prompt.shape
+        if prefix is not None:
+            L += prefix.P
+        prompt_valid = key_valid if prompt_valid is None else prompt_valid
         n, V = int(max_new_tokens), self.config.vocab_size
         stop = [int(s) for s in stop]
         if sampling is not None and sampling[1] >= V:
@@ -1097,13 +1237,16 @@ class UniGen(ModelMixin, ConfigMixin):
             sess = TextDecodeSession(eng, R, cap, width, V, deterministic=det, sampling=sampling, stop_ids=stop, pad_id=pad, key_valid=key_valid,
                                      repetition_penalty=penalty, logprobs=bool(return_logprobs))
             sess.key = key
-            sess.begin(n, prompt_ids=prompt_ids, prompt_valid=key_valid)
+            sess.begin(n, prompt_ids=prompt_ids, prompt_valid=prompt_valid)
         else:
-            sess.begin(n, key_valid, L, prompt_ids=prompt_ids, prompt_valid=key_valid)
+            sess.begin(n, key_valid, L, prompt_ids=prompt_ids, prompt_valid=prompt_valid)
         if sampling is not None:
             u_dev = dev if generator is None else generator.device
             sess.uniforms[:n].copy_(torch.rand((n, R), device=u_dev, generator=generator))
-        hn = eng.prefill(sess.st, prompt, key_valid, mask_bits=mask_bits)
+        if prefix is not None:
+            hn = self._prefill_after_prefix(sess.st, prefix, prompt, key_valid)
+        else:
+            hn = eng.prefill(sess.st, prompt, key_valid, mask_bits=mask_bits)
         eng.check_errors()
         eng.text_first_token(sess, hn, trace)
         done = (lambda emitted: emitted % 8 == 0 and int(sess.state[1]) == 0) if stop else None    # (the one host read per 8 tokens)
@@ -1126,33 +1269,58 @@ class UniGen(ModelMixin, ConfigMixin):
                                step=lambda x: eng.decode_step(st, x))            # (also advances the cache position)
 
     def _mmu_decode(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det, on_device=False,
-                    use_graph=True, repetition_penalty=1.0, trace=None, return_logprobs=False):
+                    use_graph=True, repetition_penalty=1.0, trace=None, return_logprobs=False, prefix=None, tail_valid=None):
         """Prefill R left-padded rows under their dense [R, 1, L, L] masks, then decode -> (tokens [R, max_new_tokens] on the device,
         the rows' lengths cut after `eot_token` [R], the number of steps taken, and with return_logprobs the tokens' log-probabilities fp32
         [R, max_new_tokens] (0.0 behind a row's `eot_token` and behind the last step taken), else None).  repetition_penalty: the prompt
-        ids are `idx` (when the prompt is not given as embeddings) at the keys the prompt's last row sees."""
+        ids are `idx` (when the prompt is not given as embeddings) at the keys the prompt's last row sees.
+        prefix (an MmuPrefix, already checked: check_mmu_prefix_call): idx / input_embeddings are the rows' tails [R, S], causal behind
+        the prefix and left-padded where tail_valid [R, S] is False; there is no dense mask.  The prompt is then prefix + tail: L = P + S
+        positions, key validity = the prefix's, then tail_valid; penalty ids = the prefix's ids (if it has any) and the tail ids (if given
+        as ids) at the valid positions."""
         from unigen_hip.qwen2 import DecodeState
         from .sampling import seen_mask_of
         eng = self.llm.engine
         prompt = (self.llm.model.embed_tokens(idx) if input_embeddings is None else input_embeddings).float()
         dev = prompt.device
         R, L = prompt.shape[0], prompt.shape[1]
-        mb = eng.mask_bits(attention_mask, R, L)
-        eng.check_errors()
-        key_valid = attention_mask[:, 0, -1, :] == 0
+        if prefix is None:
+            mb = eng.mask_bits(attention_mask, R, L)
+            eng.check_errors()
+            key_valid = attention_mask[:, 0, -1, :] == 0
+            prompt_ids, prompt_valid = (idx if input_embeddings is None else None), key_valid
+        else:
+            mb, P, S = None, prefix.P, L
+            L = P + S
+            tv = torch.ones((R, S), dtype=torch.bool, device=dev) if tail_valid is None else tail_valid.to(dev)
+            key_valid = torch.cat([prefix.key_valid.to(dev).expand(R, P), tv], dim=1)
+            prompt_ids = prompt_valid = None
+            if prefix.ids is not None or input_embeddings is None:
+                nothing = torch.zeros((R, 1), dtype=torch.long, device=dev)
+                prompt_ids = torch.cat([(nothing if prefix.ids is None else prefix.ids.to(dev)).expand(R, P),
+                                        idx.to(dev).long() if input_embeddings is None else nothing.expand(R, S)], dim=1)
+                prompt_valid = key_valid.clone()
+                if prefix.ids is None:
+                    prompt_valid[:, :P] = False
+                if input_embeddings is not None:
+                    prompt_valid[:, P:] = False
         if on_device:
             sampling = (float(temperature), int(top_k or 0), 1.0) if temperature > 0 else None
             tokens, lengths, steps, logp = self._decode_text_on_device(
                 prompt, max_new_tokens, det, key_valid=key_valid, mask_bits=mb, sampling=sampling, stop=self._stop_list(eot_token),
                 use_graph=use_graph, trace=trace, repetition_penalty=repetition_penalty,
-                prompt_ids=idx if input_embeddings is None else None, return_logprobs=return_logprobs)
+                prompt_ids=prompt_ids, return_logprobs=return_logprobs, prefix=prefix, prompt_valid=prompt_valid)
             if steps < max_new_tokens:              # (the host loop's shapes: the buffer is max_new_tokens wide)
                 tokens = torch.cat([tokens, tokens.new_zeros((R, max_new_tokens - steps))], dim=1)
                 if return_logprobs:
                     logp = torch.cat([logp, logp.new_zeros((R, max_new_tokens - steps))], dim=1)
             return tokens, lengths, steps, logp
         st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
-        hn = eng.prefill(st, prompt, mask_bits=mb)
+        if prefix is not None:
+            hn = self._prefill_after_prefix(st, prefix, prompt, key_valid)
+            eng.check_errors()
+        else:
+            hn = eng.prefill(st, prompt, mask_bits=mb)
         tokens = torch.zeros((R, max_new_tokens), dtype=torch.long, device=dev)
         lengths = torch.full((R,), max_new_tokens, dtype=torch.long, device=dev)
         pick, emit = (lambda last: self._pick_next(last, temperature, top_k)), emit_until_stop(tokens, eot_token, lengths=lengths)
@@ -1162,7 +1330,7 @@ class UniGen(ModelMixin, ConfigMixin):
             pick, emit = with_logprobs(lambda last: self._process_next(last, temperature, top_k),
                                        lambda scores: self._choose_next(scores, temperature), emit, logp)
         if repetition_penalty != 1.0:
-            seen = seen_mask_of(idx if input_embeddings is None else None, key_valid, R, self.config.vocab_size, dev)
+            seen = seen_mask_of(prompt_ids, prompt_valid, R, self.config.vocab_size, dev)
             pick, emit = with_repetition_penalty(pick, emit, repetition_penalty, seen)
         steps = self._decode_text(st, hn, max_new_tokens, pick, emit)
         return tokens, lengths, steps, logp
@@ -1181,7 +1349,7 @@ class UniGen(ModelMixin, ConfigMixin):
     @torch.no_grad()
     def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=0.0,
                            top_k=None, eot_token=None, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0, trace=None,
-                           return_logprobs=False):
+                           return_logprobs=False, prefix=None, tail_valid=None):
         """`mmu_generate` for up to 32 prompts at once -- the rating loop of CoT-V (reference
         evaluation/inference_unigen_cot.py:308-415 calls mmu_generate once per (image, question) pair; every decode
         step streams the whole backbone whatever the row count, so R pairs cost about one).  Rows are LEFT-padded to a
@@ -1193,21 +1361,35 @@ class UniGen(ModelMixin, ConfigMixin):
         on_device / use_graph: the token loop on the device, as in `mmu_generate`.  repetition_penalty: as in `mmu_generate`, both
         loops.  trace: a list that receives every eager on-device step's raw fp32 head logits (use_graph=False).
         return_logprobs: returns (the token lists, a list of fp32 1-D device tensors, row r's cut at its length): every token's
-        log-probability as in `mmu_generate`."""
+        log-probability as in `mmu_generate`.
+        prefix: an `mmu_prefix` object shared by every row -- one image, R questions: the image is prefilled once, not R times.
+        `idx` / `input_embeddings` are then only the rows' tails [R, S], causal behind the prefix (no attention_mask: a dense one
+        raises) and seeing of the prefix what its mask's last row saw.  tail_valid [R, S] (bool, None: all) marks the real tokens of
+        tails LEFT-padded to the longest one, so every row's next position is P + S; pads count as positions, as the left pads of the
+        rows do without a prefix.  The repetition penalty's prompt ids are the tail ids and, if the prefix was given as ids, those.
+        The call copies the prefix's keys / values into its own state and leaves the object unchanged.  Wrong arguments (a prefix of
+        another model or device, more than 32 rows, a tail position that is a pad in every row) raise UniGenHipError before any
+        launch."""
         from unigen_hip.qwen2 import resolve_deterministic
+        if prefix is not None:
+            R, _, tail_valid = check_mmu_prefix_call("mmu_generate_batch", self.llm.engine, prefix, idx, input_embeddings, attention_mask,
+                                                     tail_valid)
+        elif tail_valid is not None:
+            raise UniGenHipError("mmu_generate_batch: tail_valid belongs to a call with a prefix")
         penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate_batch")
         det = resolve_deterministic(deterministic)
         self.llm.engine.last_decode_deterministic = det
-        R, L = (idx if input_embeddings is None else input_embeddings).shape[:2]
-        if R > 32:
-            raise ValueError("mmu_generate_batch: at most 32 rows per call")
-        if attention_mask is None or tuple(attention_mask.shape) != (R, 1, L, L):
-            raise ValueError("mmu_generate_batch: attention_mask must be the rows' dense [R, 1, L, L] additive masks")
+        if prefix is None:
+            R, L = (idx if input_embeddings is None else input_embeddings).shape[:2]
+            if R > 32:
+                raise ValueError("mmu_generate_batch: at most 32 rows per call")
+            if attention_mask is None or tuple(attention_mask.shape) != (R, 1, L, L):
+                raise ValueError("mmu_generate_batch: attention_mask must be the rows' dense [R, 1, L, L] additive masks")
         dev_loop = self._text_on_device(on_device, "mmu_generate_batch", R, True, eot_token, max_new_tokens)
         self.llm.engine.last_text_decode_on_device = dev_loop
         tokens, lengths, _, logp = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
                                                     on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace,
-                                                    return_logprobs=bool(return_logprobs))
+                                                    return_logprobs=bool(return_logprobs), prefix=prefix, tail_valid=tail_valid)
         tokens, lengths = tokens.cpu(), lengths.cpu()
         lists = [list(tokens[r, :int(lengths[r])]) for r in range(R)]
         if return_logprobs:

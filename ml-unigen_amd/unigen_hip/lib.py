@@ -46,6 +46,7 @@ SIGNATURES = {
     "ug_kv_store": [P, I64, I64, I64, P, P, I64, I64, I32, I32, I64, P, I32, P],
     "ug_rope_at": [P, P, P, I64, I64, I32, I32, P, I64, P],
     "ug_attn_decode": [P, I64, P, P, P, P, I64, I64, I32, I32, I32, I64, P, F32, P],
+    "ug_attn_prefill_cached": [P, I64, P, P, P, P, I64, I64, I64, I64, I32, I32, I32, I64, F32, P],
     "ug_gemv_bf16": [P, I64, I64, P, I64, P, I64, I64, I64, I64, P],
     "ug_decode_gemv": [P, I64, I64, P, I64, P, I64, I64, I64, P, I64, P, I64, P, P],
     "ug_decode_gemv_resid_norm": [P, P, I64, P, P, P, I64, P, I64, P, I64, I64, I64, P, I64, P, I64, P, P],
@@ -135,7 +136,7 @@ PROFILE = None
 def family_of(name):
     if name.startswith("ug_gemm_bf16"):
         return "gemm"
-    if name in ("ug_attn_fwd", "ug_attn_bwd"):
+    if name in ("ug_attn_fwd", "ug_attn_bwd", "ug_attn_prefill_cached"):
         return "attention"
     if name.startswith(("ug_conv", "ug_groupnorm", "ug_amax", "ug_lfq", "ug_nchw", "ug_nhwc", "ug_gemm_f32", "ug_softmax_rows", "ug_linear_",
                         "ug_layernorm", "ug_siglip")):

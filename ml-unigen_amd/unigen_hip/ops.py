@@ -539,6 +539,25 @@ def attn_decode(qkv, cache_k, cache_v, key_valid, H, HKV, hd, Tmax, len_dev, sca
     return o
 
 
+def attn_prefill_cached(qkv, cache_k, cache_v, key_valid, S, P, H, HKV, hd, Tmax, scale=None, out=None):
+    """Causal attention of S new rows per cache row onto the decode cache [rows, HKV, Tmax, hd]: qkv bf16 [rows*S, >= H*hd] (the
+    query heads in its first H*hd columns, RoPE applied at positions P .. P+S-1), whose keys / values kv_store(pos_host=P) has
+    already put into the cache.  key_valid: uint8 [rows, Tmax] or None.  -> o bf16 [rows*S, H*hd] (every element written)."""
+    if qkv.shape[0] % S:
+        raise _l.UniGenHipError(f"attn_prefill_cached: {qkv.shape[0]} query rows are no multiple of S={S}")
+    rows = qkv.shape[0] // S
+    if key_valid is not None and (key_valid.dtype != torch.uint8 or tuple(key_valid.shape) != (rows, Tmax) or not key_valid.is_contiguous()):
+        raise _l.UniGenHipError(f"attn_prefill_cached: key_valid must be contiguous uint8 [{rows}, {Tmax}]")
+    if tuple(cache_k.shape) != (rows, HKV, Tmax, hd) or tuple(cache_v.shape) != (rows, HKV, Tmax, hd) or \
+            not (cache_k.is_contiguous() and cache_v.is_contiguous()):
+        raise _l.UniGenHipError(f"attn_prefill_cached: caches must be contiguous [{rows}, {HKV}, {Tmax}, {hd}]")
+    scale = 1.0 / math.sqrt(hd) if scale is None else scale
+    o = out if out is not None else torch.empty((rows * S, H * hd), dtype=torch.bfloat16, device=qkv.device)
+    _l.check(_l.load().ug_attn_prefill_cached(_p(qkv), qkv.stride(0), _p(cache_k), _p(cache_v), _p(key_valid), _p(o), o.stride(0),
+                                              rows, S, P, H, HKV, hd, Tmax, scale, _stream()), "ug_attn_prefill_cached")
+    return o
+
+
 def skinny_linear(x, w, bias=None, resid=None):
     """Decode-time Linear for a handful of rows: split-K fp32 accumulation (fills the chip while the weights
     stream once) + a finishing pass.  resid given -> in-place residual update, else bf16 output."""

@@ -640,6 +640,43 @@ class Qwen2Engine:
         hn, _ = ops.rmsnorm_fwd(h, self.fp.p("norm"), d.rms_norm_eps, want_rstd=False)
         return hn.view(R, P, H)[:, -1].contiguous()
 
+    def prefill_onto(self, st, embeds, P, key_valid=None):
+        """Causal prefill of S more positions onto a cache whose first P positions are filled (a shared prompt prefix, the next
+        chunk of a chunked prefill, the next turn of a conversation): embeds fp32 [rows, S, H], P + S <= st.Tmax, key_valid
+        [rows, P+S] (0 = a key no row may see) or None -> final-norm hidden of the last new position, bf16 [rows, H].  New row s
+        sits at position P + s and sees the cache keys [0, P + s] that key_valid allows (ug_attn_prefill_cached, the only
+        multi-row attention that reads the cache).  Leaves st.pos = P + S, st.len = P + S + 1 -- what prefill leaves for a prompt
+        of P + S positions, so every decode form continues unchanged; prefill_onto(st, x, 0) is a plain causal prefill."""
+        d, fp = self.dims, self.fp
+        R, S, H = embeds.shape
+        P = int(P)
+        Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
+        if R != st.rows or S < 1 or P < 0 or P + S > st.Tmax:
+            raise UniGenHipError(f"prefill_onto: {R} rows of {S} positions at {P} do not fit a state of {st.rows} rows, {st.Tmax} positions")
+        kv = None
+        if key_valid is not None:
+            if tuple(key_valid.shape) != (R, P + S):
+                raise UniGenHipError(f"prefill_onto: key_valid must be [{R}, {P + S}], got {tuple(key_valid.shape)}")
+            kv = torch.ones((R, st.Tmax), dtype=torch.uint8, device=self.device)
+            kv[:, :P + S] = key_valid.to(device=self.device, dtype=torch.uint8)
+        fp.refresh_compute_copies()
+        cos, sin = self.rope(P + S)
+        cos, sin = cos[P:].contiguous(), sin[P:].contiguous()
+        h = embeds.reshape(R * S, H).float().contiguous()
+        for i in range(d.num_hidden_layers):
+            xn1, _ = ops.rmsnorm_fwd(h, fp.p(f"l{i}.ln1"), d.rms_norm_eps, want_rstd=False)
+            qkv = ops.gemm_qkv_rope(xn1, fp.w(f"l{i}.wqkv"), fp.w(f"l{i}.bqkv"), cos, sin, S, Hq + Hk, hd)   # row r sits at position P + r % S
+            ops.kv_store(qkv, st.k[i], st.v[i], R, S, Hq, Hk, hd, st.Tmax, None, P)
+            o = ops.attn_prefill_cached(qkv, st.k[i], st.v[i], kv, S, P, Hq, Hk, hd, st.Tmax)
+            h_mid = ops.gemm_nt(o, fp.w(f"l{i}.wo"), epilogue=ops.UG_EPI_RESID, resid=h)
+            xn2, _ = ops.rmsnorm_fwd(h_mid, fp.p(f"l{i}.ln2"), d.rms_norm_eps, want_rstd=False)
+            _, act = ops.gemm_swiglu(xn2, fp.w(f"l{i}.wgu"))
+            h = ops.gemm_nt(act, fp.w(f"l{i}.wdown"), epilogue=ops.UG_EPI_RESID, resid=h_mid)
+        st.pos.fill_(P + S)
+        st.len.fill_(P + S + 1)
+        hn, _ = ops.rmsnorm_fwd(h.view(R, S, H)[:, -1].contiguous(), fp.p("norm"), d.rms_norm_eps, want_rstd=False)
+        return hn
+
     def decode_form(self, rows, deterministic):
         """The layer form of a decode step on `rows` rows -- the ONE place that chooses it; recomputed on every call, since
         `decode_fused` and UNIGEN_DECODE_SW may change between states on one engine:
