@@ -530,6 +530,37 @@ int ug_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, in
                   float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
                   int max_blocks /* 0 = fill the chip; > 0 = grid cap for an update overlapped with other kernels */,
                   hipStream_t stream);
+/* ug_adamw_flat with a device-side gradient factor: grads are multiplied by grad_scale * *grad_factor (one fp32 product, formed
+ * once per workgroup).  grad_factor: device address of one fp32, 4-byte aligned -- word [1] or [2] of ug_clip_finish's result
+ * block -- read when the kernel runs, so no host synchronisation sits between the norm and the update.  Null = ug_adamw_flat
+ * exactly (same kernels, same bits). */
+int ug_adamw_flat_dev(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                      const float* grad_factor, int max_blocks, hipStream_t stream);
+
+/* ---- gradient-norm clipping ------------------------------------------------------------------ */
+/* replaces: torch.nn.utils.clip_grad_norm_ behind accelerator.clip_grad_norm_ (training/train.py:777), norm_type 2.
+ * Span table (device, int64, 8-byte aligned): n_spans pairs {byte address of the span's first fp32, element count}.  An address
+ * is a multiple of 4 and need NOT be a multiple of 16, a count is any value >= 0 (64-bit: spans beyond 2^31 elements are fine);
+ * spans must not overlap.  1 <= n_spans <= 65535.
+ *
+ * ug_sumsq_spans_f32: partials[b] (device, fp64, `blocks` values, 1 <= blocks <= 4096 = the grid) = the sum of squares of the
+ * elements workgroup b read, over all spans.  Plain stores, every slot written on every call, no atomics, fixed summation
+ * order: the same bits on every run for the same table, data and `blocks`.  accum 0 = fp64 accumulation (what ships);
+ * 1 = fp32 chains of 32 elements flushed into fp64 (kept for measurement, tools/clip_bench.py). */
+int ug_sumsq_spans_f32(const int64_t* spans, int64_t n_spans, double* partials, int blocks, int accum, hipStream_t stream);
+/* One workgroup: sum = partials[0] + ... + partials[n_partials - 1] in that order in fp64 (1 <= n_partials <= 8192; a caller
+ * may append slots of its own, e.g. the squared norm of gradients that took another path), then in fp32, in torch's order:
+ *   result[0] total_norm = float(sqrt(sum) * |grad_scale|)          (the norm of grad_scale * g)
+ *   result[1] clip_coef  = min(1, max_norm / (total_norm + 1e-6))   (NaN stays NaN, as torch.clamp keeps it)
+ *   result[2] grad_scale * clip_coef                                (the factor an optimizer applies to the raw gradients)
+ *   result[3] 1.0 if total_norm is inf or NaN, else 0.0
+ *   result[4..5] the fp64 sum itself, result[6..7] zero.
+ * result: device, 8 fp32 words, 16-byte aligned.  max_norm and grad_scale must not be NaN. */
+int ug_clip_finish(const double* partials, int64_t n_partials, float max_norm, float grad_scale, float* result, hipStream_t stream);
+/* g *= *coef over the span table (same layout as above), in place.  *coef == 1.0f: the kernel returns without touching the
+ * gradients (bit-identical to multiplying by 1.0).  blocks: the grid, 0 = whole chip. */
+int ug_scale_spans_f32(const int64_t* spans, int64_t n_spans, const float* coef, int blocks, hipStream_t stream);
 
 /* ---- data-parallel gradient exchange staging ------------------------------------------------ */
 /* replaces: the bucket copies + fp32 all-reduce of torch DistributedDataParallel's reducer behind

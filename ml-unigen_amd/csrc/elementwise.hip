@@ -1,5 +1,5 @@
 // HBM-bound row/elementwise kernels of the Qwen2.5 backbone for gfx950: RMSNorm fwd/bwd, RoPE,
-// SwiGLU, cast, embedding gather / scatter-add, column sums, fused AdamW.
+// SwiGLU, cast, embedding gather / scatter-add, column sums, fused AdamW, gradient-norm clipping.
 // All are one pass over their operands with 16-byte per-lane accesses and wave64 shuffles for the
 // row reductions (no LDS round trip unless a cross-wave sum is needed).
 //
@@ -385,9 +385,14 @@ __device__ __forceinline__ void adamw_element(float& p, float g, float& m, float
   p = pk - c.step_size * (mk / denom);
   m = mk; v = vk;
 }
-__device__ __forceinline__ AdamConsts adam_consts(float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt, float grad_scale) {
+// gfac (ug_adamw_flat_dev): a device scalar that multiplies grad_scale -- the clip factor of ug_clip_finish, read once per workgroup
+// through a uniform address before the loop, so clipping costs the update no host synchronisation.  Null = ug_adamw_flat: no
+// multiplication happens at all, so that path keeps its bits.
+__device__ __forceinline__ AdamConsts adam_consts(float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt, float grad_scale,
+                                                  const float* gfac) {
 #pragma clang fp contract(off)
-  return AdamConsts{grad_scale, 1.f - lr * wd, 1.f - beta1, beta2, 1.f - beta2, bc2_sqrt, eps, lr / bc1};
+  const float gs = gfac ? grad_scale * *gfac : grad_scale;
+  return AdamConsts{gs, 1.f - lr * wd, 1.f - beta1, beta2, 1.f - beta2, bc2_sqrt, eps, lr / bc1};
 }
 // Same update order as torch.optim.AdamW's single-tensor path (reference optimizer,
 // training/train.py:324-330): decay, lerp first moment, second moment, bias-corrected step.
@@ -399,9 +404,9 @@ template <int NT>
 __global__ __launch_bounds__(256) void adamw_lean_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, bf16_t* __restrict__ p_bf16, int64_t n, float lr,
                                                          float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                         float grad_scale) {
+                                                         float grad_scale, const float* __restrict__ gfac) {
   const int64_t n2 = n >> 1;
-  const AdamConsts c = adam_consts(lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale);
+  const AdamConsts c = adam_consts(lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale, gfac);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
     float2 pp = ld_stream<NT>(reinterpret_cast<const float2*>(p) + i);
     const float2 gg = ld_stream<NT>(reinterpret_cast<const float2*>(g) + i);
@@ -443,9 +448,9 @@ template <int NT>
 __global__ __launch_bounds__(256) void adamw_lean2_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                           float* __restrict__ v, bf16_t* __restrict__ p_bf16, uint32_t n, float lr,
                                                           float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                          float grad_scale) {
+                                                          float grad_scale, const float* __restrict__ gfac) {
   const uint32_t n2 = n >> 1;
-  const AdamConsts c = adam_consts(lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale);
+  const AdamConsts c = adam_consts(lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale, gfac);
   const uint32_t stride = gridDim.x * blockDim.x;
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t trips = (n2 + stride - 1) / stride;             // uniform over the grid: waits and loads are never behind a divergent branch
@@ -500,9 +505,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     bf16_t* __restrict__ p_bf16, int64_t n, float lr, float beta1,
                                                     float beta2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                    float grad_scale) {
+                                                    float grad_scale, const float* __restrict__ gfac) {
   const int64_t n4 = n >> 2;
-  const AdamConsts c = adam_consts(lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale);
+  const AdamConsts c = adam_consts(lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale, gfac);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     float4 pp = ld_stream<NT>(reinterpret_cast<const float4*>(p) + i);
     float4 gg = ld_stream<NT>(reinterpret_cast<const float4*>(g) + i);
@@ -526,6 +531,150 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     adamw_element(pk, g[ti], mk, vk, c);
     p[ti] = pk; m[ti] = mk; v[ti] = vk;
     if (p_bf16) p_bf16[ti] = f2bf(pk);
+  }
+}
+
+// =========================================================================== gradient-norm clipping (flat fp32 spans)
+// Replaces torch.nn.utils.clip_grad_norm_ (reference training/train.py:777) over the gradient buffers: ONE read pass for the sum
+// of squares, a one-workgroup finish that leaves norm and clip factor on the device, and either an in-place scale by that device
+// scalar or nothing at all (ug_adamw_flat_dev takes the factor).  A span = {byte address of its first fp32, element count}; an
+// address is a multiple of 4, not necessarily of 16: lanes of one fixed workgroup take the up to 3 + 3 head / tail elements, the
+// 16-byte aligned body goes in float4 loads.  Counts and indices are 64-bit (the backbone's gradient is one span of 1.56 G elements).
+// Every workgroup walks the whole table; for span r it plays workgroup (blockIdx + r) mod grid, so short spans spread over the grid.
+// The addresses come out of a table, so the compiler cannot see that they are global memory: the pointers say so (address space 1 --
+// global_load / global_store instead of flat accesses, which would also count against lgkmcnt).
+typedef __attribute__((address_space(1))) float gmem_f32_t;
+typedef __attribute__((address_space(1))) f32x4_t gmem_f32x4_t;
+struct SpanGeom { gmem_f32_t* base; gmem_f32x4_t* body; int64_t head, body4, tail0, n; };
+__device__ __forceinline__ SpanGeom span_geom(const int64_t* __restrict__ spans, int r) {
+  SpanGeom s;
+  const uintptr_t addr = (uintptr_t)spans[2 * r];
+  s.n = spans[2 * r + 1];
+  s.base = (gmem_f32_t*)addr;
+  s.head = std::min<int64_t>(s.n, (int64_t)(((16 - (addr & 15)) & 15) >> 2));
+  s.body4 = (s.n - s.head) >> 2;
+  s.tail0 = s.head + 4 * s.body4;
+  s.body = (gmem_f32x4_t*)(addr + 4 * (uintptr_t)s.head);
+  return s;
+}
+
+// Sum of squares.  Accumulation: fp64 per lane -- (double)x * (double)x is exact (48 bits), so a lane's sum carries only the fp64
+// additions' error; v_cvt_f64_f32 + v_fma_f64 per element stay far below the read stream's rate (docs/experiments.md, "gradient
+// clipping").  CHAIN32 is the measured alternative only: fp32 fused multiply-add chains of SUMSQ_U * 4 = 32 elements, each flushed
+// into the fp64 sum.  Order: lane sums in index order, wave_sum_d's xor tree, the four waves in order, partials[blockIdx] by a
+// plain store -- no atomics, the same bits on every run for a given grid.
+// Loads: two batches of SUMSQ_U float4 per lane in flight (batch k + 1 is issued before batch k is summed; the batches are separate
+// variables and the loop is unrolled by two, so no register of a load in flight is copied).  There are no stores, so hipcc counts
+// the waits itself (vmcnt(8) before a batch is summed); the scheduling barriers keep it from hoisting both batches' loads to the
+// top of the loop body, which ends every trip on vmcnt(0).  The trip count is uniform over the grid; lanes past the end re-read
+// the span's last float4 and drop it.
+constexpr int NT_SUMSQ = 2;        // non-temporal loads: the next reader (the optimizer) comes 6 GB later
+constexpr int SUMSQ_U = 8;
+struct SumsqBatch { f32x4_t v[SUMSQ_U]; };
+template <bool CHAIN32>
+__global__ __launch_bounds__(256) void sumsq_spans_kernel(const int64_t* __restrict__ spans, int n_spans, double* __restrict__ partials) {
+  __shared__ double red[4];
+  double s = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const int64_t step = SUMSQ_U * stride;
+  for (int r = 0; r < n_spans; ++r) {
+    const SpanGeom sp = span_geom(spans, r);
+    const unsigned vb = (blockIdx.x + (unsigned)r) % gridDim.x;
+    if (vb == 0) {                                                   // head (< 4 elements before the aligned body) and tail (< 4 after it)
+      const int64_t t = threadIdx.x;
+      const int64_t e = t < sp.head ? t : sp.tail0 + (t - sp.head);
+      if (e < sp.n) { const double x = (double)sp.base[e]; s += x * x; }
+    }
+    if ((int64_t)vb * 256 >= sp.body4) continue;                     // (uniform over the workgroup) none of its lanes has a float4 here
+    const int64_t last = sp.body4 - 1;
+    const int64_t trips = (sp.body4 + step - 1) / step;
+    auto load = [&](SumsqBatch& b, int64_t i) {
+#pragma unroll
+      for (int k = 0; k < SUMSQ_U; ++k) {
+        gmem_f32x4_t* q = sp.body + std::min<int64_t>(i + k * stride, last);
+        if constexpr (NT_SUMSQ & 2) b.v[k] = __builtin_nontemporal_load(q);
+        else b.v[k] = *q;
+      }
+    };
+    auto add = [&](const SumsqBatch& b, int64_t i) {
+      float c = 0.f;
+#pragma unroll
+      for (int k = 0; k < SUMSQ_U; ++k) {
+        const bool in = i + k * stride <= last;                       // a select, not a branch: the waits stay counted
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float x = in ? b.v[k][j] : 0.f;
+          if constexpr (CHAIN32) c = __builtin_fmaf(x, x, c);
+          else s = __builtin_fma((double)x, (double)x, s);
+        }
+      }
+      if constexpr (CHAIN32) s += (double)c;
+    };
+    SumsqBatch A, B;
+    int64_t i = (int64_t)vb * 256 + threadIdx.x;
+    load(A, i);
+    for (int64_t t = 0; t < trips; t += 2) {
+      load(B, i + step); __builtin_amdgcn_sched_barrier(0); add(A, i); __builtin_amdgcn_sched_barrier(0);
+      load(A, i + 2 * step); __builtin_amdgcn_sched_barrier(0); add(B, i + step); __builtin_amdgcn_sched_barrier(0);
+      i += 2 * step;
+    }
+  }
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// One workgroup: the partials in ascending order in fp64 (lanes stage 256 at a time in LDS, lane 0 adds them one after the other),
+// then torch's coefficient arithmetic in fp32, in torch's order.  result (8 fp32 words): [0] total_norm = float(sqrt(sum) *
+// |grad_scale|), [1] clip_coef = min(1, max_norm / (total_norm + 1e-6)) with NaN kept (torch.clamp), [2] grad_scale * clip_coef,
+// [3] 1.0 if total_norm is inf or NaN else 0.0, [4..5] the fp64 sum of squares itself, [6..7] zero.
+__global__ __launch_bounds__(256) void clip_finish_kernel(const double* __restrict__ partials, int n, float max_norm, float grad_scale,
+                                                          float* __restrict__ result) {
+#pragma clang fp contract(off)
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + (int)threadIdx.x;
+    sh[threadIdx.x] = i < n ? partials[i] : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int c = min(256, n - base);
+      for (int k = 0; k < c; ++k) s += sh[k];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float total = (float)(sqrt(s) * fabs((double)grad_scale));
+    const float raw = max_norm / (total + 1e-6f);
+    const float coef = raw > 1.f ? 1.f : raw;
+    result[0] = total;
+    result[1] = coef;
+    result[2] = grad_scale * coef;
+    result[3] = (total != total || fabsf(total) == INFINITY) ? 1.f : 0.f;
+    reinterpret_cast<double*>(result)[2] = s;
+    result[6] = 0.f;
+    result[7] = 0.f;
+  }
+}
+
+// g *= *coef over the span table.  *coef == 1.0f exactly (a step that does not clip): return at once -- the same bits as torch's
+// multiplication by its clamped 1.0, without reading and writing every gradient.  The branch is uniform over the grid.
+__global__ __launch_bounds__(256) void scale_spans_kernel(const int64_t* __restrict__ spans, int n_spans, const float* __restrict__ coef) {
+  const float c = *coef;
+  if (c == 1.0f) return;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int r = 0; r < n_spans; ++r) {
+    const SpanGeom sp = span_geom(spans, r);
+    const unsigned vb = (blockIdx.x + (unsigned)r) % gridDim.x;
+    if (vb == 0) {
+      const int64_t t = threadIdx.x;
+      const int64_t e = t < sp.head ? t : sp.tail0 + (t - sp.head);
+      if (e < sp.n) sp.base[e] *= c;
+    }
+    for (int64_t i = (int64_t)vb * 256 + threadIdx.x; i < sp.body4; i += stride) {
+      sp.body[i] = sp.body[i] * c;
+    }
   }
 }
 
@@ -735,9 +884,10 @@ extern "C" int ug_colsum_bf16(const void* in, int64_t ld, float* out, int64_t R,
   return UG_OK;
 }
 
-extern "C" int ug_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
+// ug_adamw_flat (gfac = null) and ug_adamw_flat_dev share the checks, the kernel choice and the kernels
+static int adamw_flat_launch(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
                              float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
-                             int max_blocks, hipStream_t st) {
+                             const float* gfac, int max_blocks, hipStream_t st) {
   UG_REQUIRE(n > 0 && step >= 1, "ug_adamw_flat: n=%ld step=%ld", (long)n, (long)step);
   UG_REQUIRE(ug_aligned16(p) && ug_aligned16(g) && ug_aligned16(m) && ug_aligned16(v) && ((uintptr_t)p_bf16 & 7) == 0,
              "ug_adamw_flat: buffers must be 16B aligned");
@@ -753,16 +903,59 @@ extern "C" int ug_adamw_flat(float* p, const float* g, float* m, float* v, void*
     dim3 lgrid(grid_for(n / 2 + 1, 256, max_blocks));
     if (n < (1LL << 29))
       hipLaunchKernelGGL(adamw_lean2_kernel<NT_ADAMW>, lgrid, block, 0, st, p, g, m, v, (bf16_t*)p_bf16, (uint32_t)n, lr, beta1, beta2, eps, weight_decay,
-                         (float)bc1, (float)sqrt(bc2), grad_scale);
+                         (float)bc1, (float)sqrt(bc2), grad_scale, gfac);
     else
       hipLaunchKernelGGL(adamw_lean_kernel<NT_ADAMW>, lgrid, block, 0, st, p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, weight_decay,
-                         (float)bc1, (float)sqrt(bc2), grad_scale);
+                         (float)bc1, (float)sqrt(bc2), grad_scale, gfac);
     UG_CHECK_LAUNCH("ug_adamw_flat(lean)");
     return UG_OK;
   }
   hipLaunchKernelGGL(adamw_kernel<NT_ADAMW>, dim3(grid_for(n / 4 + 1)), block, 0, st, p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps,
-                     weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale);
+                     weight_decay, (float)bc1, (float)sqrt(bc2), grad_scale, gfac);
   UG_CHECK_LAUNCH("ug_adamw_flat");
+  return UG_OK;
+}
+
+extern "C" int ug_adamw_flat(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                             int max_blocks, hipStream_t st) {
+  return adamw_flat_launch(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, nullptr, max_blocks, st);
+}
+
+extern "C" int ug_adamw_flat_dev(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
+                                 const float* grad_factor, int max_blocks, hipStream_t st) {
+  UG_REQUIRE(((uintptr_t)grad_factor & 3) == 0, "ug_adamw_flat_dev: grad_factor must be a 4-byte aligned device address (or null)");
+  return adamw_flat_launch(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, grad_factor, max_blocks, st);
+}
+
+extern "C" int ug_sumsq_spans_f32(const int64_t* spans, int64_t n_spans, double* partials, int blocks, int accum, hipStream_t st) {
+  UG_REQUIRE(spans && partials && ((uintptr_t)spans & 7) == 0 && ((uintptr_t)partials & 7) == 0 && n_spans > 0 && n_spans < 65536 &&
+                 blocks > 0 && blocks <= 4096 && (accum == 0 || accum == 1),
+             "ug_sumsq_spans_f32: a device span table of 1..65535 spans, a partial buffer of `blocks` doubles, 1 <= blocks <= 4096 and "
+             "accum 0 (fp64) or 1 (fp32 chains) required (n_spans=%ld blocks=%d accum=%d)", (long)n_spans, blocks, accum);
+  if (accum == 0) hipLaunchKernelGGL(sumsq_spans_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, spans, (int)n_spans, partials);
+  else hipLaunchKernelGGL(sumsq_spans_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, spans, (int)n_spans, partials);
+  UG_CHECK_LAUNCH("ug_sumsq_spans_f32");
+  return UG_OK;
+}
+
+extern "C" int ug_clip_finish(const double* partials, int64_t n_partials, float max_norm, float grad_scale, float* result, hipStream_t st) {
+  UG_REQUIRE(partials && result && ((uintptr_t)partials & 7) == 0 && ug_aligned16(result) && n_partials > 0 && n_partials <= 8192,
+             "ug_clip_finish: 1..8192 fp64 partials and a 16-byte aligned result block of 8 fp32 words required (n_partials=%ld)", (long)n_partials);
+  UG_REQUIRE(max_norm == max_norm && grad_scale == grad_scale, "ug_clip_finish: max_norm and grad_scale must not be NaN");
+  hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(256), 0, st, partials, (int)n_partials, max_norm, grad_scale, result);
+  UG_CHECK_LAUNCH("ug_clip_finish");
+  return UG_OK;
+}
+
+extern "C" int ug_scale_spans_f32(const int64_t* spans, int64_t n_spans, const float* coef, int blocks, hipStream_t st) {
+  UG_REQUIRE(spans && coef && ((uintptr_t)spans & 7) == 0 && ((uintptr_t)coef & 3) == 0 && n_spans > 0 && n_spans < 65536 && blocks >= 0 &&
+                 blocks <= 4096,
+             "ug_scale_spans_f32: a device span table of 1..65535 spans, a device scalar and 0 <= blocks <= 4096 required (n_spans=%ld blocks=%d)",
+             (long)n_spans, blocks);
+  hipLaunchKernelGGL(scale_spans_kernel, dim3((unsigned)(blocks ? blocks : 256 * 8)), dim3(256), 0, st, spans, (int)n_spans, coef);
+  UG_CHECK_LAUNCH("ug_scale_spans_f32");
   return UG_OK;
 }
 

@@ -85,6 +85,10 @@ SIGNATURES = {
     "ug_ce_fwd": [P, I64, I64, I64, P, I64, P, P, P, P, P],
     "ug_ce_bwd": [P, I64, I64, I64, P, I64, P, P, P, P, P],
     "ug_adamw_flat": [P, P, P, P, P, I64, F32, F32, F32, F32, F32, I64, F32, I32, P],
+    "ug_adamw_flat_dev": [P, P, P, P, P, I64, F32, F32, F32, F32, F32, I64, F32, P, I32, P],
+    "ug_sumsq_spans_f32": [P, I64, P, I32, I32, P],
+    "ug_clip_finish": [P, I64, F32, F32, P, P],
+    "ug_scale_spans_f32": [P, I64, P, I32, P],
     "ug_gemm_bf16_wgrad_group": [I32, P, P, P, P, P, P, P, P, P, P, P],
     "ug_grad_pack_bf16": [P, P, I64, F32, P],
     "ug_comm_unique_id": [P],
@@ -141,7 +145,7 @@ def family_of(name):
     if name.startswith(("ug_conv", "ug_groupnorm", "ug_amax", "ug_lfq", "ug_nchw", "ug_nhwc", "ug_gemm_f32", "ug_softmax_rows", "ug_linear_",
                         "ug_layernorm", "ug_siglip")):
         return "tokenizer_and_towers"
-    if name == "ug_adamw_flat":
+    if name in ("ug_adamw_flat", "ug_adamw_flat_dev"):
         return "adamw"
     return "elementwise"
 

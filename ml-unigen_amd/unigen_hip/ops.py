@@ -972,6 +972,38 @@ def adamw_flat_(p, g, m, v, p_bf16, lr, beta1, beta2, eps, wd, step, grad_scale=
                                      step, grad_scale, max_blocks, _stream()), "ug_adamw_flat")
 
 
+def adamw_flat_dev_(p, g, m, v, p_bf16, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, grad_factor=None, max_blocks=0):
+    """adamw_flat_ with the gradients multiplied by grad_scale * grad_factor[0] (a device fp32 scalar, e.g. clip_finish's factor)."""
+    _l.check(_l.load().ug_adamw_flat_dev(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), lr, beta1, beta2, eps, wd,
+                                         step, grad_scale, _p(grad_factor), max_blocks, _stream()), "ug_adamw_flat_dev")
+
+
+# ------------------------------------------------------------------------------------ gradient-norm clipping
+# grid of the sum-of-squares pass = length of its partial buffer: one workgroup per CU, as for AdamW -- 6.86 TB/s on the 1.56 G-element
+# gradient against 5.9 - 6.5 on 512 ... 4096 workgroups (docs/experiments.md, "gradient clipping")
+SUMSQ_BLOCKS = 256
+
+
+def sumsq_spans(spans, partials, blocks=None, accum=0):
+    """spans: int64 device table [n, 2] of {byte address, fp32 count}; partials: fp64 device buffer of at least `blocks` values."""
+    blocks = SUMSQ_BLOCKS if blocks is None else int(blocks)
+    if partials.dtype != torch.float64 or partials.numel() < blocks:
+        raise _l.UniGenHipError("sumsq_spans: the partial buffer needs `blocks` fp64 values")
+    _l.check(_l.load().ug_sumsq_spans_f32(_p(spans), spans.shape[0], _p(partials), blocks, accum, _stream()), "ug_sumsq_spans_f32")
+    return partials
+
+
+def clip_finish(partials, n_partials, max_norm, result, grad_scale=1.0):
+    """result (fp32 [8]): norm, clip coefficient, grad_scale * coefficient, non-finite flag, the fp64 sum (include/unigen_hip.h)."""
+    _l.check(_l.load().ug_clip_finish(_p(partials), int(n_partials), float(max_norm), float(grad_scale), _p(result), _stream()), "ug_clip_finish")
+    return result
+
+
+def scale_spans_(spans, coef, blocks=0):
+    """g *= coef[0] over the span table; a device-side 1.0 returns without touching memory."""
+    _l.check(_l.load().ug_scale_spans_f32(_p(spans), spans.shape[0], _p(coef), int(blocks), _stream()), "ug_scale_spans_f32")
+
+
 # ------------------------------------------------------------------------------------ tokenizer (fp32 NHWC)
 def pack_conv_weight(w):
     """torch Conv2d weight [Cout, Cin, k, k] -> ([k*k, Cin, cout_pad] fp32, cout_pad). Done once at load."""
