@@ -523,6 +523,27 @@ int ug_ce_bwd(void* logits_inout, int64_t ld, int64_t R, int64_t V, const int64_
               int64_t ignore_index, const float* lse, const float* loss_and_count, const float* gscale,
               const float* row_scale, hipStream_t stream);
 
+/* ---- scoring given labels without the logits ------------------------------------------------- */
+/* The head product and its softmax statistics in one launch pair; no [R, V] buffer exists anywhere (head_score.hip).
+ *   x bf16 [R][ldx]: final-norm hidden rows; W bf16 [V][ldw]: the row-major table; K <= ldx, ldw; K % 32 == 0; ldx % 8 == ldw % 8 == 0;
+ *   labels int64 [R]; ws: ug_head_score_ws_bytes(R, V) bytes, 16-byte aligned, need not be initialised;
+ *   logp, lse, best, best_logit: [R] each; lse / best / best_logit may be null.
+ * Per row r, with s[e] = bf16round(fp32 sum over k of x[r][k] * W[e][k]) for e < V (the rounding of the precision contract: a Linear
+ * output is rounded where autocast rounds it -- the number the host loop of generate(return_logprobs=True) and ug_text_pick pick from):
+ *   lse = max s + log(sum exp(s - max s));  best = the lowest index attaining max s (torch.argmax's tie rule, ug_text_pick's);
+ *   best_logit = max s;  logp = s[label] - lse.
+ * A row whose label equals ignore_index or lies outside [0, V) gets logp = 0.0; its other outputs are written as usual.  Finite
+ * inputs are a precondition.  V needs no alignment; table rows >= V and x rows >= R are never read; nothing past R is written.
+ * Workspace: 16 bytes per (row, 256-entry column tile) -- fp32 maximum, fp32 sum rescaled to it, int32 first index of it -- plus one
+ * fp32 per row for the label's logit, written once by the single tile that holds it.  A finishing launch merges a row's tiles in
+ * tile order.  No atomics, fixed orders: the same bits on every run; and a row's four outputs are the same bits whatever R is and
+ * whatever the other rows hold (only the row-tile height follows R, head_score_plan.h).
+ * ug_head_score_ws_bytes: > 0, or a negative status and an error string for R < 1 or V < 1 (or a problem too large for one call). */
+int ug_head_score_ws_bytes(int64_t R, int64_t V);
+int ug_head_score(const void* x, int64_t ldx, int64_t R, const void* W, int64_t ldw, int64_t V, int64_t K,
+                  const int64_t* labels, int64_t ignore_index, void* ws, float* logp, float* lse, int64_t* best, float* best_logit,
+                  hipStream_t stream);
+
 /* ---- optimizer ------------------------------------------------------------------------------- */
 /* replaces: torch.optim.AdamW.step (training/train.py:324-330,780) over one flat fp32 segment; also
  * refreshes the bf16 compute copy (p_bf16 may be null).  grads are multiplied by grad_scale first. */

@@ -17,6 +17,7 @@ Behavioural notes (all mirror the reference unless stated):
     unigen.py:74-92; off in every shipped config) is implemented for forward / training and MaskGIT
     generation; t2i_generate_ar with it raises.
 """
+import collections
 import json
 import math
 import os
@@ -219,6 +220,58 @@ def check_mmu_prefix_call(who, engine, prefix, idx, input_embeddings, attention_
         if not bool(tail_valid.any(0).all()):
             raise UniGenHipError(f"{who}: a tail position is a pad in every row (left-pad the tails to the longest one only)")
     return R, S, tail_valid
+
+
+ScoreResult = collections.namedtuple("ScoreResult", ["logprob", "is_greedy", "token_logprobs"])
+ScoreResult.__doc__ = """What `UniGen.score` returns: logprob fp32 [R] (the continuation's log-probability: the sum over its tokens, or
+their mean with average=True), is_greedy bool [R] (every token of the continuation is the argmax of its position: greedy decoding
+would have emitted it), token_logprobs fp32 [R, C] (0.0 at the pads of `targets`)."""
+
+
+def check_score_call(who, engine, prefix, idx, input_embeddings, targets, tail_valid, image_codes_from=None):
+    """The argument checks of `UniGen.score`, all on the host and before anything is launched
+    -> (rows, context length, continuation length, tail_valid as a bool tensor or None, the real-target mask bool [R, C] on the CPU)."""
+    if (idx is None) == (input_embeddings is None):
+        raise UniGenHipError(f"{who}: give the rows' contexts as idx [R, S] or input_embeddings [R, S, H] (one of the two)")
+    ctx = idx if input_embeddings is None else input_embeddings
+    if ctx.dim() != (2 if input_embeddings is None else 3) or ctx.shape[0] < 1 or ctx.shape[1] < 1:
+        raise UniGenHipError(f"{who}: the contexts must be [R, S] ids or [R, S, H] embeddings with R, S >= 1, got {tuple(ctx.shape)}")
+    R, S = int(ctx.shape[0]), int(ctx.shape[1])
+    if input_embeddings is not None and ctx.shape[2] != engine.dims.hidden_size:
+        raise UniGenHipError(f"{who}: input_embeddings must be {engine.dims.hidden_size} wide, got {tuple(ctx.shape)}")
+    if not torch.is_tensor(targets) or targets.dim() != 2 or targets.shape[0] != R or targets.shape[1] < 1 or targets.dtype != torch.int64:
+        raise UniGenHipError(f"{who}: targets must be an int64 [{R}, C] tensor of continuation ids, right-padded with -100, got "
+                             f"{tuple(targets.shape) if torch.is_tensor(targets) else type(targets).__name__}")
+    C = int(targets.shape[1])
+    on_host = targets.device.type == "cpu"
+    t = targets if on_host else targets.cpu()                # (a copy, not a launch: the pad pattern decides the shapes of the call)
+    real = t != -100
+    if not bool(real.any(1).all()):
+        raise UniGenHipError(f"{who}: row {int((~real.any(1)).nonzero()[0])} of targets has no real target (only -100)")
+    if not bool((real[:, 1:] <= real[:, :-1]).all()):
+        raise UniGenHipError(f"{who}: targets must be RIGHT-padded with -100 (a real id follows a pad)")
+    V = engine.dims.vocab_size
+    if on_host and bool(((t < 0) | (t >= V))[real].any()):
+        raise UniGenHipError(f"{who}: target ids must lie in [0, {V}) (or be the pad -100)")
+    if image_codes_from is not None and on_host and bool((t >= image_codes_from)[real].any()):
+        raise UniGenHipError(f"{who}: image-code targets (ids >= {image_codes_from}) cannot be scored on a model with a gen_projector: "
+                             f"their inputs go through gen_embed, which this call does not apply")
+    if prefix is not None:
+        if not isinstance(prefix, MmuPrefix):
+            raise UniGenHipError(f"{who}: prefix must be the object UniGen.mmu_prefix returns, got {type(prefix).__name__}")
+        if prefix.engine is not engine:
+            raise UniGenHipError(f"{who}: the prefix was built by another model")
+        pd, td = torch.device(prefix.device), ctx.device
+        if td.type != pd.type or (td.index is not None and pd.index is not None and td.index != pd.index):
+            raise UniGenHipError(f"{who}: the prefix lives on another device ({pd}) than the contexts ({td})")
+    if tail_valid is not None:
+        tail_valid = torch.as_tensor(tail_valid)
+        if tuple(tail_valid.shape) != (R, S):
+            raise UniGenHipError(f"{who}: tail_valid must be [{R}, {S}], got {tuple(tail_valid.shape)}")
+        tail_valid = tail_valid != 0
+        if not bool(tail_valid[:, -1].all()):
+            raise UniGenHipError(f"{who}: contexts are LEFT-padded: every row's last context position must be a real one")
+    return R, S, C, tail_valid, real
 
 
 class UniGen(ModelMixin, ConfigMixin):
@@ -1071,14 +1124,68 @@ class UniGen(ModelMixin, ConfigMixin):
         eng.check_errors()
         return MmuPrefix(self, st, P, key_valid, None if idx is None else idx.to(dev).long())
 
-    def _prefill_after_prefix(self, st, prefix, tails, key_valid):
+    def _prefill_after_prefix(self, st, prefix, tails, key_valid, hidden_at=None):
         """the prefill of a call that takes a prefix: the prefix's keys / values of every layer into positions [0, P) of every row of
-        `st`, then the rows' tails [R, S, H] onto them (Qwen2Engine.prefill_onto) -> final-norm hidden of the last tail position"""
+        `st`, then the rows' tails [R, S, H] onto them (Qwen2Engine.prefill_onto) -> final-norm hidden of the last tail position
+        (with hidden_at: prefill_onto's pair)"""
         P = prefix.P
         for i in range(len(st.k)):
             st.k[i][:, :, :P].copy_(prefix.st.k[i][:, :, :P])          # (one row, broadcast to the call's rows)
             st.v[i][:, :, :P].copy_(prefix.st.v[i][:, :, :P])
-        return self.llm.engine.prefill_onto(st, tails, P, key_valid)
+        if hidden_at is None:
+            return self.llm.engine.prefill_onto(st, tails, P, key_valid)
+        return self.llm.engine.prefill_onto(st, tails, P, key_valid, hidden_at=hidden_at)
+
+    @torch.no_grad()
+    def score(self, idx=None, input_embeddings=None, targets=None, prefix=None, tail_valid=None, average=False):
+        """Log-probability of GIVEN continuations (lmms-eval's `loglikelihood`; P("yes") against P("no") of a rating; the answers
+        of a multiple-choice question; DPO candidates): row r's context is idx[r] (ids [R, S]) or input_embeddings[r] ([R, S, H]),
+        LEFT-padded to a common length with tail_valid [R, S] marking the real positions (None: all), and behind an optional
+        `mmu_prefix` object shared by every row, as in `mmu_generate_batch(prefix=...)`; targets int64 [R, C] holds the
+        continuations' ids, RIGHT-padded with -100.  One teacher-forced pass over [context | targets[:, :-1]] (pads fed as id 0:
+        they sit behind every real position, causality hides them) through Qwen2Engine.prefill_onto, then ONE ug_head_score launch
+        pair over the R * C positions that predict a target: the [R * C, vocab] logits are never formed.
+        -> ScoreResult(logprob [R], is_greedy [R], token_logprobs [R, C]); every token's log-probability is log softmax of the
+        bf16-rounded head logits at its label -- the number `generate(return_logprobs=True)` reports for a token it drew greedily.
+        average=True: logprob is the mean over the row's real targets instead of the sum.  Any number of rows: beyond 32 they go
+        through the backbone 32 at a time inside the call.  Leaves the prefix unchanged and keeps no session.  Wrong arguments
+        (shapes, a row without a real target, a prefix of another model or device, target ids outside the vocabulary when
+        `targets` is on the CPU) raise UniGenHipError before any launch.  On a model with a gen_projector image-code targets raise."""
+        from unigen_hip.qwen2 import DecodeState
+        eng = self.llm.engine
+        codes_from = self.config.get("llm_vocab_size", None) if self._use_gen() else None
+        R, S, C, tail_valid, real = check_score_call("score", eng, prefix, idx, input_embeddings, targets, tail_valid, codes_from)
+        dev = eng.device
+        ctx = (self.llm.model.embed_tokens(idx.to(dev)) if input_embeddings is None else input_embeddings.to(dev)).float()
+        real = real.to(dev)
+        labels = torch.where(real, targets.to(dev), torch.full_like(real, -100, dtype=torch.int64))
+        seq = ctx
+        if C > 1:
+            fed = torch.where(real, labels, torch.zeros_like(labels))[:, :-1].contiguous()
+            seq = torch.cat([ctx, self.llm.model.embed_tokens(fed).float()], dim=1)
+        P, L = (0 if prefix is None else prefix.P), S + C - 1
+        tv = torch.ones((R, S), dtype=torch.bool, device=dev) if tail_valid is None else tail_valid.to(dev)
+        pre = torch.ones((R, 0), dtype=torch.bool, device=dev) if prefix is None else prefix.key_valid.to(dev).expand(R, P)
+        key_valid = torch.cat([pre, tv, torch.ones((R, C - 1), dtype=torch.bool, device=dev)], dim=1)
+        at = (S - 1) + torch.arange(C, device=dev)
+        token_logprobs = torch.empty((R, C), dtype=torch.float32, device=dev)
+        best = torch.empty((R, C), dtype=torch.int64, device=dev)
+        for r0 in range(0, R, MMU_MAX_ROWS):
+            n = min(MMU_MAX_ROWS, R - r0)
+            st = DecodeState(eng.dims, n, P + L, dev, key_valid=key_valid[r0:r0 + n])
+            hidden_at = (torch.arange(n, device=dev)[:, None] * L + at[None, :]).reshape(-1)
+            if prefix is None:
+                _, hn = eng.prefill_onto(st, seq[r0:r0 + n], 0, key_valid[r0:r0 + n], hidden_at=hidden_at)
+            else:
+                _, hn = self._prefill_after_prefix(st, prefix, seq[r0:r0 + n], key_valid[r0:r0 + n], hidden_at=hidden_at)
+            logp, _, b = eng.score_rows(hn, labels[r0:r0 + n].reshape(-1))
+            token_logprobs[r0:r0 + n] = logp.view(n, C)
+            best[r0:r0 + n] = b.view(n, C)
+        eng.check_errors()
+        logprob = token_logprobs.sum(dim=1)
+        if average:
+            logprob = logprob / real.sum(dim=1).to(torch.float32)
+        return ScoreResult(logprob, ((best == labels) | ~real).all(dim=1), token_logprobs)
 
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,

@@ -84,6 +84,8 @@ SIGNATURES = {
     "ug_decode_finish_resid_norm_ord": [P, I64, I64, P, P, P, I64, I64, F32, P, P, P],
     "ug_ce_fwd": [P, I64, I64, I64, P, I64, P, P, P, P, P],
     "ug_ce_bwd": [P, I64, I64, I64, P, I64, P, P, P, P, P],
+    "ug_head_score_ws_bytes": [I64, I64],
+    "ug_head_score": [P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P, P],
     "ug_adamw_flat": [P, P, P, P, P, I64, F32, F32, F32, F32, F32, I64, F32, I32, P],
     "ug_adamw_flat_dev": [P, P, P, P, P, I64, F32, F32, F32, F32, F32, I64, F32, P, I32, P],
     "ug_sumsq_spans_f32": [P, I64, P, I32, I32, P],

@@ -941,6 +941,50 @@ def ce_bwd_(logits, V, labels, lse, lc, gscale=None, ignore_index=-100, row_scal
     return logits
 
 
+_HEAD_SCORE_WS = {}
+HEAD_SCORE_WANT = ("lse", "best", "best_logit")
+
+
+def head_score_ws_bytes(R, V):
+    """bytes of ug_head_score's workspace (csrc/head_score_plan.h): 16 per (row, 256-entry column tile) + 4 per row"""
+    n = _l.load().ug_head_score_ws_bytes(R, V)
+    if n <= 0:
+        _l.check(n, "ug_head_score_ws_bytes")
+    return n
+
+
+def _head_score_workspace(nbytes, device):
+    """one uint8 scratch per device, grown on demand and kept (the kernels initialise what they read)"""
+    ws = _HEAD_SCORE_WS.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = _HEAD_SCORE_WS[device] = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    return ws
+
+
+def head_score(x, W, V, labels, ignore_index=-100, want=("lse", "best")):
+    """Score labels against the first V rows of the table W without forming logits (include/unigen_hip.h: ug_head_score).
+    x bf16 [R, K] (row stride >= K), W bf16 [>=V, K], labels int64 [R] -> (logp fp32 [R], then the tensors named in `want`, in its
+    order: "lse" fp32, "best" int64, "best_logit" fp32).  logp is 0.0 where the label is ignore_index or outside [0, V)."""
+    _need_cuda(x, W, labels)
+    bad = [n for n in want if n not in HEAD_SCORE_WANT]
+    if bad or x.dim() != 2 or W.dim() != 2 or x.dtype != torch.bfloat16 or W.dtype != torch.bfloat16 or x.stride(1) != 1 or W.stride(1) != 1 \
+            or x.shape[1] != W.shape[1] or not 1 <= V <= W.shape[0] or labels.dtype != torch.int64 or labels.dim() != 1 \
+            or labels.shape[0] != x.shape[0] or not labels.is_contiguous():
+        raise _l.UniGenHipError(f"head_score: need bf16 x [R, K] and W [>=V, K] with unit inner stride, int64 labels [R] and want within "
+                                f"{HEAD_SCORE_WANT} (x {tuple(x.shape)} {x.dtype}, W {tuple(W.shape)} {W.dtype}, V {V}, labels "
+                                f"{tuple(labels.shape)} {labels.dtype}, want {tuple(want)})")
+    R, K = x.shape
+    dev = x.device
+    ws = _head_score_workspace(head_score_ws_bytes(R, V), dev)
+    logp = torch.empty((R,), dtype=torch.float32, device=dev)
+    out = {"lse": None, "best": None, "best_logit": None}
+    for n in want:
+        out[n] = torch.empty((R,), dtype=torch.int64 if n == "best" else torch.float32, device=dev)
+    _l.check(_l.load().ug_head_score(_p(x), x.stride(0), R, _p(W), W.stride(0), V, K, _p(labels), ignore_index, _p(ws), _p(logp),
+                                     _p(out["lse"]), _p(out["best"]), _p(out["best_logit"]), _stream()), "ug_head_score")
+    return (logp,) + tuple(out[n] for n in want)
+
+
 # flat fp32 master buffers that keep a bf16 compute mirror (FlatParams registers itself); FusedAdamW writes the
 # mirror in the same pass so no separate cast pass follows an optimizer step
 BF16_MIRRORS = []

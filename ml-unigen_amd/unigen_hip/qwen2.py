@@ -544,6 +544,12 @@ class Qwen2Engine:
         out = torch.empty((hn_rows.shape[0], d.vocab_pad), dtype=torch.bfloat16, device=self.device)
         return ops.gemm_nt(hn_rows, self.fp.w("embed"), out=out, N=d.vocab_size, K=d.hidden_size)
 
+    def score_rows(self, hn_rows, labels, ignore_index=-100):
+        """hn_rows bf16 [R, H], labels int64 [R] -> (logp fp32 [R], lse fp32 [R], best int64 [R]) against the tied table, without the
+        [R, vocab] logits logits_rows would write (ops.head_score); logp is 0.0 where the label is ignore_index."""
+        self.fp.refresh_compute_copies()
+        return ops.head_score(hn_rows, self.fp.w("embed"), self.dims.vocab_size, labels, ignore_index=ignore_index, want=("lse", "best"))
+
     def head_bwd(self, dlogits, hn_rows):
         """dlogits bf16 [R, vocab_pad] (pad columns zero) -> dhn_rows bf16 [R,H]; embed grad accumulated."""
         d, fp = self.dims, self.fp
@@ -640,19 +646,24 @@ class Qwen2Engine:
         hn, _ = ops.rmsnorm_fwd(h, self.fp.p("norm"), d.rms_norm_eps, want_rstd=False)
         return hn.view(R, P, H)[:, -1].contiguous()
 
-    def prefill_onto(self, st, embeds, P, key_valid=None):
+    def prefill_onto(self, st, embeds, P, key_valid=None, hidden_at=None):
         """Causal prefill of S more positions onto a cache whose first P positions are filled (a shared prompt prefix, the next
         chunk of a chunked prefill, the next turn of a conversation): embeds fp32 [rows, S, H], P + S <= st.Tmax, key_valid
         [rows, P+S] (0 = a key no row may see) or None -> final-norm hidden of the last new position, bf16 [rows, H].  New row s
         sits at position P + s and sees the cache keys [0, P + s] that key_valid allows (ug_attn_prefill_cached, the only
         multi-row attention that reads the cache).  Leaves st.pos = P + S, st.len = P + S + 1 -- what prefill leaves for a prompt
-        of P + S positions, so every decode form continues unchanged; prefill_onto(st, x, 0) is a plain causal prefill."""
+        of P + S positions, so every decode form continues unchanged; prefill_onto(st, x, 0) is a plain causal prefill.
+        hidden_at (optional): int64 indices into the flattened [rows * S] new positions -> (hn_last, hn_sel), hn_sel bf16 [n, H] the
+        final-norm hidden of those positions (the same ug_rmsnorm_fwd on the gathered rows: asking for a row's last position gives
+        the bits of hn_last's row); what score_rows scores a given continuation from."""
         d, fp = self.dims, self.fp
         R, S, H = embeds.shape
         P = int(P)
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
         if R != st.rows or S < 1 or P < 0 or P + S > st.Tmax:
             raise UniGenHipError(f"prefill_onto: {R} rows of {S} positions at {P} do not fit a state of {st.rows} rows, {st.Tmax} positions")
+        if hidden_at is not None and (hidden_at.dtype != torch.int64 or hidden_at.dim() != 1 or hidden_at.numel() < 1):
+            raise UniGenHipError(f"prefill_onto: hidden_at must be a non-empty int64 vector of indices into the {R * S} new positions")
         kv = None
         if key_valid is not None:
             if tuple(key_valid.shape) != (R, P + S):
@@ -675,7 +686,10 @@ class Qwen2Engine:
         st.pos.fill_(P + S)
         st.len.fill_(P + S + 1)
         hn, _ = ops.rmsnorm_fwd(h.view(R, S, H)[:, -1].contiguous(), fp.p("norm"), d.rms_norm_eps, want_rstd=False)
-        return hn
+        if hidden_at is None:
+            return hn
+        hn_sel, _ = ops.rmsnorm_fwd(h.index_select(0, hidden_at.to(self.device)), fp.p("norm"), d.rms_norm_eps, want_rstd=False)
+        return hn, hn_sel
 
     def decode_form(self, rows, deterministic):
         """The layer form of a decode step on `rows` rows -- the ONE place that chooses it; recomputed on every call, since
