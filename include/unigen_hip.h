@@ -509,6 +509,52 @@ int ug_text_seen_mark(int* seen, int64_t ld_words, const int64_t* ids, int64_t l
 int ug_text_penalize(float* logits, int64_t ld, int64_t R, int64_t V, float penalty, int* seen, int64_t ld_words, const int64_t* tok,
                      hipStream_t stream);
 
+/* Constraints of the text loops: logit_bias, suppress_tokens, min_new_tokens, no_repeat_ngram_size, stop_sequences
+ * (UniGen.generate / mmu_generate / mmu_generate_batch; host side models/sampling.py + models/unigen.py: with_constraints).
+ * THE ORDER is transformers': sequence bias, repetition penalty, the -inf writers (n-gram block, min-new-tokens, suppress), then
+ * temperature / top-k / top-p.  The -inf writers commute with the penalty (-inf * p == -inf / p == -inf for p > 0), so both loops
+ * apply all of them in front of the penalty; on the device that is ONE launch ahead of ug_text_penalize.
+ *   logit_bias {id: b}: b finite, added to the id's score in every row (SequenceBiasLogitsProcessor with keys of length 1).
+ *   suppress_tokens:    the id's score becomes -inf (SuppressTokensLogitsProcessor).  An id in both lists, twice in one, or outside
+ *                       [0, V) is refused by the callers before any launch.
+ *   min_new_tokens m:   while fewer than m tokens have been emitted every single stop id scores -inf
+ *                       (MinNewTokensLengthLogitsProcessor); stop sequences are not held back.
+ *   no_repeat_ngram_size n (0: off): NoRepeatNGramLogitsProcessor on the row's HISTORY h = the ids the repetition penalty counts, in
+ *                       order: the prompt ids inside [0, V) at mask-valid positions, compacted (a prompt given as embeddings: nothing; a
+ *                       prefix + tail prompt: the prefix's ids if it has them, then the tail's), then the tokens emitted (fed back) so
+ *                       far.  With T = len h: if T >= n - 1, every t = h[i + n - 1] with h[i .. i + n - 1) == h[T - n + 1 .. T) for
+ *                       0 <= i <= T - n scores -inf.  (n = 1: every id of the history.)
+ *   stop_sequences:     entries of length 1 join the stop ids (at most 8 in all on the device).  A longer entry finishes a row at the
+ *                       step whose emitted token completes it, matched on EMITTED tokens only (a match never reaches into the prompt);
+ *                       the completing token is kept, lengths[r] = step + 1, and from the next step on the row is what it is behind a
+ *                       stop id: pad fill if there is a pad id, log-probability 0.0, the loop ends once every row is done.
+ * The host loop has no size limits.  The device loop: 1024 bias + suppress entries, n <= 16, 8 stop sequences of at most 16 ids. */
+
+/* One launch per step between the head and ug_text_penalize, R <= 32, one workgroup per row; logits / ld as ug_text_pick has them (no
+ * alignment needed).
+ * bias: n_bias <= 1024 pairs {int32 id, fp32 bias} in device memory, ids DISTINCT; a suppressed id carries bias = -inf.
+ * stop_ids / n_stop: the session's single stop ids (ug_text_pick's).  ngram = n <= 16 (0: off).
+ * hist int32 [R][ld_hist], hist_len int32 [R]: the prompt part of every row's history, written by the host at the start of a call,
+ * outside the captured step (ld_hist == 0: none; a length is clamped to [0, ld_hist]).  out_tokens int32 [R][nsteps]: the pick's
+ * records.  state: the pick's state block; step = state[0] is read, nothing of the block is written.
+ * Phase 1, thread j -> entry j:  logits[r][id] = bias == -inf ? -inf : fp32(bf16round(logits[r][id]) + bias)   (round to nearest).
+ * Workgroup barrier.  Phase 2, the -inf stores: the stop ids while step < min_new; the n-gram bans over the combined history =
+ * hist[r][0 .. len) followed by out_tokens[r][0 .. step).  An id outside [0, V) found in a list or a history takes part in the n-gram
+ * comparison as the number it is and is never used as an index.  Only the named entries of the logits are read or written; entries
+ * V .. ld-1 are never touched.  No atomics, no float reductions: a bit-reproducible function of its inputs. */
+int ug_text_constrain(float* logits, int64_t ld, int64_t R, int64_t V, const void* bias, int64_t n_bias, int64_t min_new,
+                      const int64_t* stop_ids, int64_t n_stop, int64_t ngram, const int* hist, int64_t ld_hist, const int* hist_len,
+                      const int* out_tokens, int64_t nsteps, const int* state, hipStream_t stream);
+
+/* One launch per step BEHIND the pick launch(es), R <= 32: the stop sequences.  seq_ids int32 [n_ids] = the ns <= 8 sequences (2 .. 16
+ * ids each) back to back, seq_off int32 [ns + 1] their offsets (seq_off[ns] == n_ids); an entry whose offsets do not fit is skipped.
+ * step = state[0] - 1, the step the pick has just recorded.  For every row that is not done and whose last m emitted tokens
+ * out_tokens[r][step - m + 1 .. step] equal a sequence of length m <= step + 1 (never a column before 0), exactly step 5 of ug_text_pick:
+ * lengths[r] = step + 1 (lengths may be null), done[r] = 1, --remaining, and when remaining reaches zero steps_used = step + 1.  A row
+ * that is done -- by a stop id of this very step too -- is left alone: a row never finishes twice, whatever number of sequences match. */
+int ug_text_stop_seq(const int* seq_ids, const int* seq_off, int64_t ns, int64_t n_ids, const int* out_tokens, int64_t nsteps, int64_t R,
+                     int* state, int* lengths, hipStream_t stream);
+
 /* ---- loss ------------------------------------------------------------------------------------ */
 /* replaces: F.cross_entropy(ignore_index=-100) x3 in UniGen.forward (models/unigen.py:310-338) and
  * get_batch_logps (training/train_dpo.py:51-90).  logits bf16 [R, ld], ld % 8 == 0.

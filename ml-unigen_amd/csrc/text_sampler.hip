@@ -1,7 +1,8 @@
 // Token pick of a text decode step over the WHOLE vocabulary, on the device (UniGen.generate / mmu_generate / mmu_generate_batch with
 // on_device=True): the head's fp32 logits [R][ld] -> one token per row, the stop rule of models/unigen.py: emit_until_stop, the
 // token's slot in the output buffer and the embedding row that feeds the next step.  Contract: include/unigen_hip.h (ug_text_pick,
-// ug_text_sample; the repetition penalty in front of the pick: ug_text_seen_mark, ug_text_penalize).  Plain HIP C++: no inline assembly,
+// ug_text_sample; the repetition penalty in front of the pick: ug_text_seen_mark, ug_text_penalize; the constraints in front of the
+// penalty and the stop sequences behind the pick: ug_text_constrain, ug_text_stop_seq).  Plain HIP C++: no inline assembly,
 // no float atomics; integer atomics only where their order cannot change the result (histogram counts, a maximum, a minimum, the count
 // of unfinished rows, the arrival ticket that advances the step counter, the OR of a prompt id's bit into the seen bitmap).
 //
@@ -25,6 +26,7 @@ constexpr int TXT_BINS = 65536;        // one bin per bf16 pattern
 constexpr int TXT_MAXV = 262144;       // ug_text_sample: launch C keeps one 64-bit match mask per 64 entries in LDS (32 KiB)
 constexpr int TXT_SEG = 8192;          // entries per workgroup of the histogram launch
 constexpr int TXT_HT = 256;
+constexpr int TXT_NEGINF_POS = TXT_BINS - 1 - 0x7f;   // text_select_kernel's position of the key of -inf (bf16 0xff80 -> key 0x007f)
 
 struct TextOut {
   const int64_t* stop_ids;
@@ -232,7 +234,7 @@ __global__ __launch_bounds__(TXT_T) void text_select_kernel(int* __restrict__ hi
                                                            int nsteps, int R, float* __restrict__ stats) {
   __shared__ int wt_i[TXT_W];
   __shared__ float wt_f[TXT_W];
-  __shared__ int s_step, s_pk, s_pc, s_kept, s_hit;
+  __shared__ int s_step, s_pk, s_pc, s_kept, s_hit, s_pf;
   __shared__ float s_T;
   const int r = blockIdx.x, t = threadIdx.x;
   const int step = min(txt_read_step(state, &s_step), nsteps - 1);
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(TXT_T) void text_select_kernel(int* __restrict__ hi
   for (int j = 0; j < 16; ++j) h4[v0 + j] = make_int4(0, 0, 0, 0);                 // the bins are ready for the next step
   const float vmax = txt_val((uint32_t)meta[r], inv_temp);
   const float u01 = uniforms[(int64_t)step * R + r];
-  if (t == 0) { s_pk = TXT_BINS - 1; s_pc = 0; s_kept = 0; s_hit = TXT_BINS; }
+  if (t == 0) { s_pk = TXT_BINS - 1; s_pc = 0; s_kept = 0; s_hit = TXT_BINS; s_pf = -1; }
   const int p0 = 64 * t;
   // ---- top-k: the position of the k-th largest entry, duplicates counted (exact: integer sums)
   int nloc = 0;
@@ -284,14 +286,18 @@ __global__ __launch_bounds__(TXT_T) void text_select_kernel(int* __restrict__ hi
   const float lim = top_p * Z;
   {
     float run = mbase;
-    int last = -1, kept = 0;
+    int last = -1, lastf = -1, kept = 0;
 #pragma unroll
     for (int i = 0; i < 64; ++i)
       if (cnt[i] > 0 && p0 + i <= pk) {
-        if (top_p >= 1.f || run <= lim) { last = p0 + i; kept += cnt[i]; }
+        if (top_p >= 1.f || run <= lim) {
+          last = p0 + i; kept += cnt[i];
+          if (p0 + i != TXT_NEGINF_POS) lastf = last;                // (the last kept key that is not -inf: see `hit` below)
+        }
         run += mass(i);
       }
     if (last >= 0) { atomicMax(&s_pc, last); atomicAdd(&s_kept, kept); }
+    if (lastf >= 0) atomicMax(&s_pf, lastf);
   }
   __syncthreads();
   const int pc = s_pc;
@@ -318,7 +324,9 @@ __global__ __launch_bounds__(TXT_T) void text_select_kernel(int* __restrict__ hi
     if (hit < TXT_BINS) atomicMin(&s_hit, hit);
   }
   __syncthreads();
-  const int hit = s_hit < TXT_BINS ? s_hit : pc;                   // (rounding left the target behind the last bound: the last kept key)
+  // rounding left the target behind the last bound: the last kept key -- but never the key of -inf while another is kept: an entry a
+  // logits processor wrote -inf into (ug_text_constrain) has mass 0 and is never drawn
+  const int hit = s_hit < TXT_BINS ? s_hit : (pc == TXT_NEGINF_POS && s_pf >= 0 ? s_pf : pc);
   if (hit >= p0 && hit < p0 + 64) {
     float run = mbase, e = 1.f;
     int c = 1;
@@ -455,6 +463,77 @@ __global__ __launch_bounds__(TXT_HT) void text_penalize_kernel(float* __restrict
   }
 }
 
+// ------------------------------------------------------------------ constraints: the logits processor in front of the penalty
+// One workgroup per row; a row's logits are touched by its workgroup alone.  Phase 1: thread j owns bias entry j (the ids of the list are
+// distinct, so no two threads share a logit).  Barrier.  Phase 2: the -inf stores -- several threads may store -inf into one entry, the
+// same bits whatever their order.  Plain loads and stores, no atomics, no float reductions: the launch is a function of its inputs.
+constexpr int TXT_MAX_BIAS = 1024;
+constexpr int TXT_MAX_NGRAM = 16;
+constexpr int TXT_MAX_SEQS = 8;
+constexpr int TXT_MAX_SEQ_LEN = 16;
+
+struct TextBias { int id; float bias; };
+
+__global__ __launch_bounds__(TXT_HT) void text_constrain_kernel(float* __restrict__ logits, int64_t ld, int V, const TextBias* __restrict__ bias,
+                                                               int n_bias, int min_new, const int64_t* __restrict__ stop_ids, int n_stop,
+                                                               int n, const int* __restrict__ hist, int64_t ld_hist,
+                                                               const int* __restrict__ hist_len, const int* __restrict__ out_tokens,
+                                                               int nsteps, const int* __restrict__ state) {
+  __shared__ int s_suf[TXT_MAX_NGRAM];
+  const int r = blockIdx.x, t = threadIdx.x;
+  const int step = max(0, min(*reinterpret_cast<const volatile int*>(state), nsteps));      // (read, never advanced: the pick does that)
+  float* row = logits + (int64_t)r * ld;
+  const int P = (hist && hist_len) ? max(0, min(hist_len[r], (int)ld_hist)) : 0;
+  const int T = P + step;                                          // the combined history: prompt ids, then out_tokens[r][0 .. step)
+  const int* hp = P ? hist + (int64_t)r * ld_hist : nullptr;
+  const int* ho = out_tokens ? out_tokens + (int64_t)r * nsteps : nullptr;        // (null only with n == 0: h is then never called)
+  auto h = [&](int j) -> int { return j < P ? hp[j] : ho[j - P]; };
+  for (int j = t; j < n_bias; j += TXT_HT) {
+    const TextBias b = bias[j];
+    if (b.id < 0 || b.id >= V) continue;
+    row[b.id] = b.bias == -INFINITY ? -INFINITY : __fadd_rn(bf2f(f2bf(row[b.id])), b.bias);
+  }
+  const bool grams = n > 0 && T >= n - 1;
+  if (grams && t < n - 1) s_suf[t] = h(T - n + 1 + t);             // the last n - 1 ids of the history
+  __syncthreads();
+  if (step < min_new && t < n_stop) {
+    const int64_t e = stop_ids[t];
+    if (e >= 0 && e < V) row[e] = -INFINITY;
+  }
+  if (!grams) return;
+  for (int i = t; i + n <= T; i += TXT_HT) {
+    bool same = true;
+    for (int k = 0; k < n - 1; ++k) same &= h(i + k) == s_suf[k];
+    if (!same) continue;
+    const int e = h(i + n - 1);
+    if (e >= 0 && e < V) row[e] = -INFINITY;                       // (an id outside [0, V) is compared, never used as an index)
+  }
+}
+
+// Stop sequences: thread r owns row r.  The row's last m emitted tokens against every sequence of length m <= step + 1; what a match
+// does is txt_finish_row's stop branch.  One workgroup: `remaining` needs an atomic only for the symmetry with the pick.
+__global__ __launch_bounds__(64) void text_stop_seq_kernel(const int* __restrict__ seq_ids, const int* __restrict__ seq_off, int ns, int n_ids,
+                                                          const int* __restrict__ out_tokens, int nsteps, int R, int* __restrict__ state,
+                                                          int* __restrict__ lengths) {
+  const int r = threadIdx.x;
+  const int step = *reinterpret_cast<const volatile int*>(state) - 1;        // the step the pick launch has just finished
+  if (r >= R || step < 0 || step >= nsteps) return;
+  int* done = state + 4;
+  if (done[r]) return;                                             // (a row never finishes twice)
+  const int* row = out_tokens + (int64_t)r * nsteps;
+  for (int s = 0; s < ns; ++s) {
+    const int o0 = seq_off[s], m = seq_off[s + 1] - o0;
+    if (o0 < 0 || m < 1 || m > TXT_MAX_SEQ_LEN || o0 + m > n_ids || m > step + 1) continue;      // (never a column before 0)
+    bool same = true;
+    for (int k = 0; k < m; ++k) same &= row[step - m + 1 + k] == seq_ids[o0 + k];
+    if (!same) continue;
+    if (lengths) lengths[r] = step + 1;
+    done[r] = 1;
+    if (atomicSub(&state[1], 1) == 1) state[2] = step + 1;
+    return;
+  }
+}
+
 int txt_check_out(const char* who, float* logits, int64_t ld, int64_t R, int64_t V, const int64_t* stop_ids, int64_t n_stop, int64_t pad_id,
                   const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t nsteps, int64_t* tok,
                   int* out_tokens, float* x) {
@@ -585,5 +664,38 @@ extern "C" int ug_text_penalize(float* logits, int64_t ld, int64_t R, int64_t V,
   hipLaunchKernelGGL(text_penalize_kernel, dim3((unsigned)((W + TXT_HT - 1) / TXT_HT), (unsigned)R), dim3(TXT_HT), 0, st, logits, ld, (int)V,
                      penalty, seen, ld_words, tok);
   UG_CHECK_LAUNCH("ug_text_penalize");
+  return UG_OK;
+}
+
+extern "C" int ug_text_constrain(float* logits, int64_t ld, int64_t R, int64_t V, const void* bias, int64_t n_bias, int64_t min_new,
+                                 const int64_t* stop_ids, int64_t n_stop, int64_t ngram, const int* hist, int64_t ld_hist,
+                                 const int* hist_len, const int* out_tokens, int64_t nsteps, const int* state, hipStream_t st) {
+  UG_REQUIRE(logits && state && (n_bias == 0 || bias) && (n_stop == 0 || stop_ids) && (ngram == 0 || out_tokens) &&
+                 (ld_hist == 0 || (hist && hist_len)),
+             "ug_text_constrain: null argument");
+  UG_REQUIRE(R > 0 && R <= TXT_MAX_ROWS && V > 0 && V < (1ll << 31) && ld >= V && R * ld < (1ll << 31) && nsteps > 0 && nsteps < (1ll << 31) &&
+                 ld_hist >= 0 && R * ld_hist < (1ll << 31),
+             "ug_text_constrain: bad sizes (R=%ld <= %d, V=%ld <= ld=%ld, R*ld < 2^31, nsteps=%ld, ld_hist=%ld, R*ld_hist < 2^31)", (long)R,
+             TXT_MAX_ROWS, (long)V, (long)ld, (long)nsteps, (long)ld_hist);
+  UG_REQUIRE(n_bias >= 0 && n_bias <= TXT_MAX_BIAS && min_new >= 0 && min_new < (1ll << 31) && n_stop >= 0 && n_stop <= TXT_MAX_STOP &&
+                 ngram >= 0 && ngram <= TXT_MAX_NGRAM,
+             "ug_text_constrain: bad constraints (n_bias=%ld <= %d, min_new=%ld >= 0, n_stop=%ld <= %d, ngram=%ld <= %d)", (long)n_bias,
+             TXT_MAX_BIAS, (long)min_new, (long)n_stop, TXT_MAX_STOP, (long)ngram, TXT_MAX_NGRAM);
+  hipLaunchKernelGGL(text_constrain_kernel, dim3((unsigned)R), dim3(TXT_HT), 0, st, logits, ld, (int)V, static_cast<const TextBias*>(bias),
+                     (int)n_bias, (int)min_new, stop_ids, (int)n_stop, (int)ngram, hist, ld_hist, hist_len, out_tokens, (int)nsteps, state);
+  UG_CHECK_LAUNCH("ug_text_constrain");
+  return UG_OK;
+}
+
+extern "C" int ug_text_stop_seq(const int* seq_ids, const int* seq_off, int64_t ns, int64_t n_ids, const int* out_tokens, int64_t nsteps,
+                                int64_t R, int* state, int* lengths, hipStream_t st) {
+  UG_REQUIRE(seq_ids && seq_off && out_tokens && state, "ug_text_stop_seq: null argument");
+  UG_REQUIRE(R > 0 && R <= TXT_MAX_ROWS && nsteps > 0 && nsteps < (1ll << 31) && R * nsteps < (1ll << 31) && ns > 0 && ns <= TXT_MAX_SEQS &&
+                 n_ids >= 2 * ns && n_ids <= ns * TXT_MAX_SEQ_LEN,
+             "ug_text_stop_seq: bad sizes (R=%ld <= %d, nsteps=%ld, 0 < ns=%ld <= %d sequences of 2 .. %d ids, n_ids=%ld)", (long)R,
+             TXT_MAX_ROWS, (long)nsteps, (long)ns, TXT_MAX_SEQS, TXT_MAX_SEQ_LEN, (long)n_ids);
+  hipLaunchKernelGGL(text_stop_seq_kernel, dim3(1), dim3(64), 0, st, seq_ids, seq_off, (int)ns, (int)n_ids, out_tokens, (int)nsteps, (int)R,
+                     state, lengths);
+  UG_CHECK_LAUNCH("ug_text_stop_seq");
   return UG_OK;
 }

@@ -160,6 +160,64 @@ def seen_mask_of(ids, valid, rows, vocab, device):
     return seen[:, :vocab]
 
 
+def apply_logit_bias(logits, ids, values):
+    """transformers' SequenceBiasLogitsProcessor with keys of length 1 on [R, V] logits: values[j] is added to column ids[j] of every
+    row (ids distinct).  Returns a new tensor.  The on-device loop's kernel adds to the bf16-rounded score (include/unigen_hip.h:
+    ug_text_constrain)."""
+    out = logits.clone()
+    if len(ids):
+        cols = torch.as_tensor(ids, dtype=torch.long, device=logits.device)
+        out[:, cols] += torch.as_tensor(values, dtype=logits.dtype, device=logits.device)
+    return out
+
+
+def history_of(ids, valid, rows, vocab):
+    """the rows' histories at the start of a call, as lists: the ids the repetition penalty counts (seen_mask_of), in order -- ids
+    [rows, L] (None: no ids, empty histories) inside [0, vocab) at the positions `valid` [rows, L] marks real (None: all)"""
+    if ids is None:
+        return [[] for _ in range(rows)]
+    ids = ids.long().cpu()
+    ok = (ids >= 0) & (ids < vocab)
+    if valid is not None:
+        ok &= valid.cpu() != 0
+    return [ids[r][ok[r]].tolist() for r in range(rows)]
+
+
+def ngram_banned(history, n):
+    """transformers' NoRepeatNGramLogitsProcessor for one row: the ids that would complete an n-gram the history (a list of ids)
+    already holds -- every history[i + n - 1] with history[i : i + n - 1] == the history's last n - 1 ids, 0 <= i <= len - n; nothing
+    while the history is shorter than n - 1.  n = 1 bans every id of the history.  -> a list (duplicates possible)."""
+    T = len(history)
+    if n < 1 or T < n - 1:
+        return []
+    tail = history[T - n + 1:]
+    return [history[i + n - 1] for i in range(T - n + 1) if history[i:i + n - 1] == tail]
+
+
+def stop_sequence_hit(emitted, sequences):
+    """whether the emitted tokens of one row (a list; the prompt is no part of it) end with one of `sequences` (lists of ids)"""
+    return any(0 < len(s) <= len(emitted) and emitted[len(emitted) - len(s):] == list(s) for s in sequences)
+
+
+def apply_constraints(logits, bias=(), banned=None, histories=None, ngram=0):
+    """The constraints of one step on [R, V] logits, ahead of the repetition penalty (the -inf stores commute with it): bias =
+    [(id, b), ...] with b = -inf for a suppressed id (apply_logit_bias / transformers' SuppressTokensLogitsProcessor), `banned` = ids
+    that score -inf in every row (the stop ids while min_new_tokens holds: MinNewTokensLengthLogitsProcessor), and ngram_banned of
+    every row's history.  Returns a new tensor."""
+    add = [(e, b) for e, b in bias if b != float("-inf")]
+    out = apply_logit_bias(logits, [e for e, _ in add], [b for _, b in add])
+    cols = [e for e, b in bias if b == float("-inf")] + list(banned or ())
+    if cols:
+        out[:, torch.as_tensor(cols, dtype=torch.long, device=out.device)] = float("-inf")
+    if ngram:
+        V = out.shape[1]
+        for r, h in enumerate(histories):
+            ban = [e for e in ngram_banned(h, ngram) if 0 <= e < V]
+            if ban:
+                out[r, torch.as_tensor(ban, dtype=torch.long, device=out.device)] = float("-inf")
+    return out
+
+
 def token_logprobs(scores, tokens, done=None):
     """The log-probability of every row's picked token under the distribution it was picked from: the log-softmax of the PROCESSED
     scores [R, V] (after the repetition penalty, the temperature and top-k / top-p / min-p written as -inf -- whatever the pick saw) at

@@ -148,6 +148,77 @@ def with_repetition_penalty(pick, emit, penalty, seen):
     return (lambda last: pick(apply_repetition_penalty(last, seen, penalty))), emit_and_mark
 
 
+def checked_constraints(who, vocab, logit_bias=None, suppress_tokens=None, min_new_tokens=None, no_repeat_ngram_size=None,
+                        stop_sequences=None):
+    """A call's constraints, checked before any launch (include/unigen_hip.h: "Constraints of the text loops") -> (None when all five
+    are off, else {"bias": [(id, bias), ...] sorted by id with -inf for a suppressed id, "min_new": m, "ngram": n, "stop_seqs": the
+    stop sequences of two or more ids as tuples}, the ids of the stop sequences of length 1 -- they join the call's stop ids).
+    vocab: a callable that returns V, asked only when there are ids to check.  An id in both lists, twice in one or outside [0, V), a
+    bias that is not finite, a negative count or an empty stop sequence raises UniGenHipError."""
+    bias = {}
+    for name, items in (("logit_bias", list((logit_bias or {}).items())), ("suppress_tokens", [(e, float("-inf")) for e in (suppress_tokens or ())])):
+        for e, b in items:
+            e, b = int(e), float(b)
+            if e in bias:
+                raise UniGenHipError(f"{who}: id {e} occurs twice in logit_bias / suppress_tokens")
+            if name == "logit_bias" and not math.isfinite(b):
+                raise UniGenHipError(f"{who}: logit_bias[{e}]={b} must be finite (suppress_tokens bans an id)")
+            bias[e] = b
+    m = 0 if min_new_tokens is None else int(min_new_tokens)
+    n = 0 if no_repeat_ngram_size is None else int(no_repeat_ngram_size)
+    if m < 0 or n < 0:
+        raise UniGenHipError(f"{who}: min_new_tokens={m} and no_repeat_ngram_size={n} must be at least 0 (0 is off)")
+    seqs = [tuple(int(t) for t in s) for s in (stop_sequences or ())]
+    if any(len(s) == 0 for s in seqs):
+        raise UniGenHipError(f"{who}: an empty stop sequence")
+    ids = list(bias) + [t for s in seqs for t in s]
+    if ids:
+        V = int(vocab())
+        bad = [e for e in ids if not 0 <= e < V]
+        if bad:
+            raise UniGenHipError(f"{who}: ids {sorted(set(bad))} of logit_bias / suppress_tokens / stop_sequences are outside [0, {V})")
+    singles = [s[0] for s in seqs if len(s) == 1]
+    longer = [s for s in seqs if len(s) > 1]
+    if not (bias or m or n or longer):
+        return None, singles
+    return {"bias": sorted(bias.items()), "min_new": m, "ngram": n, "stop_seqs": longer}, singles
+
+
+def with_constraints(pick, emit, constraints, done, histories, stop_ids=(), lengths=None):
+    """`pick` and `emit` of text_token_loop with the constraints of checked_constraints in front of everything else (models/sampling.py:
+    apply_constraints; the order is include/unigen_hip.h's: the -inf stores commute with the repetition penalty, so wrap the result of
+    with_repetition_penalty, which wraps with_logprobs' -- the log-probabilities are then those of the fully processed scores).
+    done: emit_until_stop's `emit.done`; histories: sampling.history_of's lists, which take every token `emit` feeds back (a finished
+    row's pad id included, as on the device); stop_ids: the single stop ids min_new_tokens holds back; lengths: emit_until_stop's.
+    A stop sequence is matched on the emitted tokens alone and finishes a row exactly as a stop id does -- once, at the step whose
+    token completes it; a row a stop id finished at that very step is left alone."""
+    from .sampling import apply_constraints, stop_sequence_hit
+    bias, min_new, ngram, seqs = constraints["bias"], constraints["min_new"], constraints["ngram"], constraints["stop_seqs"]
+    stop_ids = [int(s) for s in stop_ids]
+    emitted = [[] for _ in histories]
+    count = [0]
+
+    def constrained_pick(last):
+        return pick(apply_constraints(last, bias, stop_ids if count[0] < min_new else (), histories, ngram))
+
+    def emit_and_match(i, nxt):
+        feed, stop = emit(i, nxt)
+        count[0] = i + 1
+        if ngram or seqs:
+            for r, t in enumerate(feed[:, 0].tolist()):
+                histories[r].append(t)
+                emitted[r].append(t)
+        if seqs:
+            was = done.tolist()
+            hit = torch.tensor([not was[r] and stop_sequence_hit(emitted[r], seqs) for r in range(len(emitted))], device=done.device)
+            if lengths is not None:
+                lengths.masked_fill_(hit, i + 1)
+            done.logical_or_(hit)
+            stop = bool(done.all())
+        return feed, stop
+    return constrained_pick, emit_and_match
+
+
 MMU_MAX_ROWS = 32
 
 
@@ -1011,13 +1082,27 @@ class UniGen(ModelMixin, ConfigMixin):
         no temperature.  The host loop computes it in fp32 on the scores it picks from (models/sampling.py: token_logprobs), the
         on-device loop in its pick launches (include/unigen_hip.h: ug_text_pick_logp, ug_text_sample_logp) on the bf16-rounded
         scores; each is exact to its own formula, the two heads round differently.
+        logit_bias={id: b}, suppress_tokens=[ids], min_new_tokens=m, no_repeat_ngram_size=n, stop_sequences=[[ids], ...] (kwargs; the
+        semantics are stated once, in include/unigen_hip.h: "Constraints of the text loops"): transformers' SequenceBiasLogitsProcessor
+        with keys of length 1, SuppressTokensLogitsProcessor, MinNewTokensLengthLogitsProcessor (every eos id scores -inf while fewer than
+        m tokens have been emitted; stop sequences are not held back) and NoRepeatNGramLogitsProcessor on the row's history (the ids the
+        repetition penalty counts, in order), in transformers' order: bias, repetition penalty, the -inf writers, then temperature /
+        top-k / top-p.  A stop sequence of one id is an eos id; a longer one finishes a row at the step whose token completes it, matched
+        on the emitted tokens only, the completing token kept, pad fill from the next step on; it needs an eos_token_id or a pad_token_id.
+        return_logprobs reports the log-softmax of the constrained scores.  Both loops; the on-device loop serves 1024 bias + suppress
+        entries, n <= 16 and 8 stop sequences of at most 16 ids (an explicit on_device=True beyond that raises, a default-derived one
+        falls back to the host loop).  An id in both lists, twice in one, or outside [0, V) raises before any launch.
         num_beams and penalty_alpha are refused."""
         from unigen_hip.qwen2 import DecodeState, resolve_deterministic
-        from .sampling import seen_mask_of, top_k_top_p_filtering
+        from .sampling import history_of, seen_mask_of, top_k_top_p_filtering
         unsupported = [k for k in ("num_beams", "penalty_alpha") if kwargs.get(k) not in (None, 1, 1.0)]
         if unsupported:
             raise UniGenHipError(f"generate: {unsupported} are not implemented (greedy / sampling only)")
         penalty = checked_repetition_penalty(kwargs.get("repetition_penalty"), "generate")
+        cons, single_stops = checked_constraints("generate", lambda: self.config.vocab_size, kwargs.get("logit_bias"), kwargs.get("suppress_tokens"),
+                                                 kwargs.get("min_new_tokens"), kwargs.get("no_repeat_ngram_size"), kwargs.get("stop_sequences"))
+        if kwargs.get("stop_sequences") and eos_token_id is None and pad_token_id is None:
+            raise UniGenHipError("generate: stop_sequences need an eos_token_id or a pad_token_id (a finished row is filled with it)")
         n_ret = kwargs.get("num_return_sequences")
         n_ret = 1 if n_ret is None else int(n_ret)
         if n_ret < 1:
@@ -1043,17 +1128,20 @@ class UniGen(ModelMixin, ConfigMixin):
         eos = [] if eos_token_id is None else ([int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple)) else [int(eos_token_id)])
         if eos and pad_token_id is None:
             pad_token_id = eos[0]
+        eos = eos + [e for e in single_stops if e not in eos]       # stop sequences of one id are stop ids
+        stops = bool(eos or (cons and cons["stop_seqs"]))
         det = resolve_deterministic(deterministic)
         eng.last_decode_deterministic = det
-        eng.last_text_decode_on_device = self._text_on_device(on_device, "generate", R, bool(use_cache), eos, max_new_tokens)
+        eng.last_text_decode_on_device = self._text_on_device(on_device, "generate", R, bool(use_cache), eos, max_new_tokens, constraints=cons)
         if eng.last_text_decode_on_device:
             sampling = None
             if do_sample:
                 sampling = (float(1.0 if temperature is None else temperature), int(top_k or 0), float(1.0 if top_p is None else top_p))
             out, _, _, logp = self._decode_text_on_device(
-                prompt, max_new_tokens, det, key_valid=key_valid, sampling=sampling, stop=eos, pad_token_id=pad_token_id if eos else None,
+                prompt, max_new_tokens, det, key_valid=key_valid, sampling=sampling, stop=eos, pad_token_id=pad_token_id if stops else None,
                 generator=generator, use_graph=bool(kwargs.get("use_graph", True)), trace=kwargs.get("trace"), repetition_penalty=penalty,
-                prompt_ids=None if input_embeddings is not None else input_ids.to(dev), return_logprobs=bool(return_logprobs))
+                prompt_ids=None if input_embeddings is not None else input_ids.to(dev), return_logprobs=bool(return_logprobs),
+                **self._constraint_kwargs(cons))
             seqs = torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
             return (seqs, logp) if return_logprobs else seqs
         st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
@@ -1077,8 +1165,9 @@ class UniGen(ModelMixin, ConfigMixin):
         def pick(last):
             return choose(process(last))
 
-        stop = torch.tensor(eos, device=dev) if eos else None
+        stop = torch.tensor(eos, dtype=torch.long, device=dev) if stops else None        # (stop sequences alone: no ids, rows still finish)
         emit = emit_until_stop(out, stop, pad_token_id)
+        done = emit.done
         logp = None
         if return_logprobs:
             logp = torch.zeros((R, max_new_tokens), dtype=torch.float32, device=dev)
@@ -1086,6 +1175,9 @@ class UniGen(ModelMixin, ConfigMixin):
         if penalty != 1.0:
             seen = seen_mask_of(None if input_embeddings is not None else input_ids, key_valid, R, self.config.vocab_size, dev)
             pick, emit = with_repetition_penalty(pick, emit, penalty, seen)
+        if cons is not None:
+            hist = history_of(None if input_embeddings is not None else input_ids, key_valid, R, self.config.vocab_size)
+            pick, emit = with_constraints(pick, emit, cons, done, hist, stop_ids=eos)
         steps = self._decode_text(st, hn, max_new_tokens, pick, emit)
         out = out[:, :steps]
         seqs = torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
@@ -1190,7 +1282,8 @@ class UniGen(ModelMixin, ConfigMixin):
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
                      top_k=None, eot_token=None, use_cache=True, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0,
-                     return_logprobs=False, trace=None, prefix=None):
+                     return_logprobs=False, trace=None, prefix=None, logit_bias=None, suppress_tokens=None, min_new_tokens=None,
+                     no_repeat_ngram_size=None, stop_sequences=None):
         """Greedy / top-k text continuation (reference models/unigen.py:523-581).  The reference re-runs the whole
         growing sequence every step and extends the additive mask by one row that copies the previous last row;
         here the prompt is prefilled once under its mask into the static KV cache and every new token is one decode
@@ -1205,6 +1298,8 @@ class UniGen(ModelMixin, ConfigMixin):
         return_logprobs: returns (token list, fp32 1-D device tensor of the same length): every token's log-probability as in `generate`
         (temperature 0: the greedy form; temperature > 0: behind temperature and top-k).  Cached form only.
         trace: a list that receives every eager on-device step's raw fp32 head logits (use_graph=False).
+        logit_bias, suppress_tokens, min_new_tokens, no_repeat_ngram_size, stop_sequences: as in `generate`, cached form only (both loops);
+        min_new_tokens holds `eot_token` back, a stop sequence ends the list like `eot_token` does.  The recompute form raises for them.
         prefix: an `mmu_prefix` object; `idx` / `input_embeddings` are then only the continuation [1, S], which is causal (no
         attention_mask) and sees of the prefix what its mask's last row saw.  Cached form only; everything else as without."""
         from unigen_hip.qwen2 import resolve_deterministic
@@ -1215,22 +1310,30 @@ class UniGen(ModelMixin, ConfigMixin):
             if not use_cache:
                 raise UniGenHipError("mmu_generate: a prefix needs the cached form (use_cache=True)")
         penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate")
+        cons, single_stops = checked_constraints("mmu_generate", lambda: self.config.vocab_size, logit_bias, suppress_tokens, min_new_tokens,
+                                                 no_repeat_ngram_size, stop_sequences)
+        if single_stops:
+            eot_token = self._stop_list(eot_token) + single_stops
+        ckw = self._constraint_kwargs(cons)
         det = resolve_deterministic(deterministic)
         self.llm.engine.last_decode_deterministic = det
         if prefix is not None:
-            dev_loop = self._text_on_device(on_device, "mmu_generate", 1, True, eot_token, max_new_tokens)
+            dev_loop = self._text_on_device(on_device, "mmu_generate", 1, True, eot_token, max_new_tokens, constraints=cons)
             self.llm.engine.last_text_decode_on_device = dev_loop
             tokens, _, steps, logp = self._mmu_decode(idx, input_embeddings, None, max_new_tokens, temperature, top_k, eot_token, det,
                                                       on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace,
-                                                      return_logprobs=bool(return_logprobs), prefix=prefix)
+                                                      return_logprobs=bool(return_logprobs), prefix=prefix, **ckw)
             return (list(tokens[0, :steps]), logp[0, :steps].clone()) if return_logprobs else list(tokens[0, :steps])
         cached = bool(use_cache and attention_mask is not None and attention_mask.shape[0] == 1)
-        dev_loop = self._text_on_device(on_device, "mmu_generate", 1, cached, eot_token, max_new_tokens)
+        dev_loop = self._text_on_device(on_device, "mmu_generate", 1, cached, eot_token, max_new_tokens, constraints=cons)
         self.llm.engine.last_text_decode_on_device = dev_loop
         if cached:
             return self._mmu_generate_cached(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
                                              on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty,
-                                             return_logprobs=bool(return_logprobs), trace=trace)
+                                             return_logprobs=bool(return_logprobs), trace=trace, **ckw)
+        if cons is not None or single_stops:
+            raise UniGenHipError("mmu_generate: logit_bias / suppress_tokens / min_new_tokens / no_repeat_ngram_size / stop_sequences need "
+                                 "the cached form (use_cache=True and a one-row mask); the recompute form does not apply them")
         if return_logprobs:
             raise UniGenHipError("mmu_generate: return_logprobs needs the cached form (use_cache=True and a one-row mask)")
         if penalty != 1.0:
@@ -1269,10 +1372,21 @@ class UniGen(ModelMixin, ConfigMixin):
             return [int(v) for v in stop]
         return [int(stop)]
 
-    def _text_on_device(self, on_device, who, rows, cached, stop, max_new_tokens):
+    @staticmethod
+    def _constraint_kwargs(cons):
+        """checked_constraints' dict back as the five keyword arguments (what the public entry points hand down)"""
+        if cons is None:
+            return {}
+        ninf = float("-inf")
+        return dict(logit_bias={e: b for e, b in cons["bias"] if b != ninf}, suppress_tokens=[e for e, b in cons["bias"] if b == ninf],
+                    min_new_tokens=cons["min_new"], no_repeat_ngram_size=cons["ngram"], stop_sequences=cons["stop_seqs"])
+
+    def _text_on_device(self, on_device, who, rows, cached, stop, max_new_tokens, constraints=None):
         """Whether this call runs the on-device token loop.  An explicit bool wins over `self.text_decode_on_device`; the loop serves
         what the AR path's fused step serves (up to 32 rows, hidden size >= 256 and a multiple of 32, cached path) with up to 8 stop
-        ids.  An explicit True on anything else raises with the reason; a default-derived True falls back to the host loop."""
+        ids and constraints (checked_constraints' dict) within ops.TEXT_MAX_BIAS / TEXT_MAX_NGRAM / TEXT_MAX_STOP_SEQS /
+        TEXT_MAX_STOP_SEQ_LEN.  An explicit True on anything else raises with the reason; a default-derived True falls back to the host
+        loop."""
         if not (self.text_decode_on_device if on_device is None else bool(on_device)):
             return False
         H = self.llm.engine.dims.hidden_size
@@ -1288,6 +1402,17 @@ class UniGen(ModelMixin, ConfigMixin):
             why = f"{n_stop} stop ids (at most {ops.TEXT_MAX_STOP})"
         elif max_new_tokens < 1:
             why = f"max_new_tokens={max_new_tokens}"
+        elif constraints is not None:
+            c = constraints
+            longest = max([len(q) for q in c["stop_seqs"]], default=0)
+            if len(c["bias"]) > ops.TEXT_MAX_BIAS:
+                why = f"{len(c['bias'])} logit_bias + suppress_tokens entries (at most {ops.TEXT_MAX_BIAS})"
+            elif c["ngram"] > ops.TEXT_MAX_NGRAM:
+                why = f"no_repeat_ngram_size={c['ngram']} (at most {ops.TEXT_MAX_NGRAM})"
+            elif len(c["stop_seqs"]) > ops.TEXT_MAX_STOP_SEQS:
+                why = f"{len(c['stop_seqs'])} stop sequences (at most {ops.TEXT_MAX_STOP_SEQS})"
+            elif longest > ops.TEXT_MAX_STOP_SEQ_LEN:
+                why = f"a stop sequence of {longest} ids (at most {ops.TEXT_MAX_STOP_SEQ_LEN})"
         if why is None:
             return True
         if on_device is None:
@@ -1296,7 +1421,8 @@ class UniGen(ModelMixin, ConfigMixin):
 
     def _decode_text_on_device(self, prompt, max_new_tokens, det, key_valid=None, mask_bits=None, sampling=None, stop=(), pad_token_id=None,
                                generator=None, use_graph=True, trace=None, repetition_penalty=1.0, prompt_ids=None, return_logprobs=False,
-                               prefix=None, prompt_valid=None):
+                               prefix=None, prompt_valid=None, logit_bias=None, suppress_tokens=None, min_new_tokens=None,
+                               no_repeat_ngram_size=None, stop_sequences=None):
         """The token loop of `text_token_loop` + `emit_until_stop` with nothing but launches per token: prefill, token 0 eagerly from
         the prefill's hidden state (GEMV head + pick), then unigen_hip/qwen2.py: decode_loop (step 1 eagerly, step 2 captured, replays
         from there).  The pick launch applies the stop rule on the device; with stop ids the host reads `remaining` every 8 tokens and
@@ -1318,6 +1444,11 @@ class UniGen(ModelMixin, ConfigMixin):
         plus Qwen2Engine.prefill_onto on the tails.  The session key needs nothing more: rows, capacity and the presence of
         key_valid cover it, and the copy rewrites every prefix position of a reused session.
         prompt_valid [R, L]: the positions of prompt_ids that count for the penalty (default: key_valid).
+        logit_bias / suppress_tokens / min_new_tokens / no_repeat_ngram_size / stop_sequences (include/unigen_hip.h: "Constraints of
+        the text loops"): the session owns the bias list, the n-gram block's prompt history (written in begin() from prompt_ids /
+        prompt_valid, outside the captured step) and the packed stop sequences; every step launches ug_text_constrain ahead of the
+        penalty and ug_text_stop_seq behind the pick.  The constraint constants are part of the session key: a call never replays a
+        graph captured with other constraints.  All off: nothing allocated, nothing launched, the key is what it was.
         -> (tokens int64 [R, steps], lengths int64 [R], steps, log-probabilities fp32 [R, steps] or None)."""
         from unigen_hip.qwen2 import TextDecodeSession, decode_loop, put_session, take_session
         eng = self.llm.engine
@@ -1327,7 +1458,11 @@ class UniGen(ModelMixin, ConfigMixin):
             L += prefix.P
         prompt_valid = key_valid if prompt_valid is None else prompt_valid
         n, V = int(max_new_tokens), self.config.vocab_size
+        cons, single_stops = checked_constraints("on-device text decode", lambda: V, logit_bias, suppress_tokens, min_new_tokens,
+                                                 no_repeat_ngram_size, stop_sequences)
         stop = [int(s) for s in stop]
+        stop += [e for e in single_stops if e not in stop]
+        stops = bool(stop or (cons and cons["stop_seqs"]))
         if sampling is not None and sampling[1] >= V:
             sampling = (sampling[0], 0, sampling[2])
         if sampling is not None and not (sampling[0] > 0 and sampling[1] >= 0 and 0.0 < sampling[2] <= 1.0):
@@ -1339,10 +1474,12 @@ class UniGen(ModelMixin, ConfigMixin):
                str(dev)) + eng.storage_key(cap)
         if return_logprobs:
             key += ("logprobs",)
+        if cons is not None:
+            key += ("constraints", tuple(cons["bias"]), cons["min_new"], cons["ngram"], tuple(cons["stop_seqs"]))
         sess = take_session(eng, "_text_session", key, use_graph)
         if sess is None:
             sess = TextDecodeSession(eng, R, cap, width, V, deterministic=det, sampling=sampling, stop_ids=stop, pad_id=pad, key_valid=key_valid,
-                                     repetition_penalty=penalty, logprobs=bool(return_logprobs))
+                                     repetition_penalty=penalty, logprobs=bool(return_logprobs), constraints=cons)
             sess.key = key
             sess.begin(n, prompt_ids=prompt_ids, prompt_valid=prompt_valid)
         else:
@@ -1356,10 +1493,10 @@ class UniGen(ModelMixin, ConfigMixin):
             hn = eng.prefill(sess.st, prompt, key_valid, mask_bits=mask_bits)
         eng.check_errors()
         eng.text_first_token(sess, hn, trace)
-        done = (lambda emitted: emitted % 8 == 0 and int(sess.state[1]) == 0) if stop else None    # (the one host read per 8 tokens)
+        done = (lambda emitted: emitted % 8 == 0 and int(sess.state[1]) == 0) if stops else None   # (the one host read per 8 tokens)
         if decode_loop(sess, lambda: eng.text_step(sess, trace), range(1, n), use_graph, stop=done):
             eng.text_graph_captures = getattr(eng, "text_graph_captures", 0) + 1
-        used = int(sess.state[2]) if stop else 0
+        used = int(sess.state[2]) if stops else 0
         steps = used if used > 0 else n
         eng.last_decode_graph = sess.graph is not None
         tokens, lengths = sess.out_tokens[:, :steps].long(), sess.lengths.long()       # (copies: the next call overwrites the session's)
@@ -1376,7 +1513,8 @@ class UniGen(ModelMixin, ConfigMixin):
                                step=lambda x: eng.decode_step(st, x))            # (also advances the cache position)
 
     def _mmu_decode(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det, on_device=False,
-                    use_graph=True, repetition_penalty=1.0, trace=None, return_logprobs=False, prefix=None, tail_valid=None):
+                    use_graph=True, repetition_penalty=1.0, trace=None, return_logprobs=False, prefix=None, tail_valid=None,
+                    logit_bias=None, suppress_tokens=None, min_new_tokens=None, no_repeat_ngram_size=None, stop_sequences=None):
         """Prefill R left-padded rows under their dense [R, 1, L, L] masks, then decode -> (tokens [R, max_new_tokens] on the device,
         the rows' lengths cut after `eot_token` [R], the number of steps taken, and with return_logprobs the tokens' log-probabilities fp32
         [R, max_new_tokens] (0.0 behind a row's `eot_token` and behind the last step taken), else None).  repetition_penalty: the prompt
@@ -1384,10 +1522,15 @@ class UniGen(ModelMixin, ConfigMixin):
         prefix (an MmuPrefix, already checked: check_mmu_prefix_call): idx / input_embeddings are the rows' tails [R, S], causal behind
         the prefix and left-padded where tail_valid [R, S] is False; there is no dense mask.  The prompt is then prefix + tail: L = P + S
         positions, key validity = the prefix's, then tail_valid; penalty ids = the prefix's ids (if it has any) and the tail ids (if given
-        as ids) at the valid positions."""
+        as ids) at the valid positions.  logit_bias ... stop_sequences: the constraints of `generate`; the n-gram block's history is the
+        penalty's ids in order, a stop sequence of one id joins `eot_token`."""
         from unigen_hip.qwen2 import DecodeState
-        from .sampling import seen_mask_of
+        from .sampling import history_of, seen_mask_of
         eng = self.llm.engine
+        cons, single_stops = checked_constraints("mmu decode", lambda: self.config.vocab_size, logit_bias, suppress_tokens, min_new_tokens,
+                                                 no_repeat_ngram_size, stop_sequences)
+        if single_stops:
+            eot_token = self._stop_list(eot_token) + [e for e in single_stops if e not in self._stop_list(eot_token)]
         prompt = (self.llm.model.embed_tokens(idx) if input_embeddings is None else input_embeddings).float()
         dev = prompt.device
         R, L = prompt.shape[0], prompt.shape[1]
@@ -1416,7 +1559,8 @@ class UniGen(ModelMixin, ConfigMixin):
             tokens, lengths, steps, logp = self._decode_text_on_device(
                 prompt, max_new_tokens, det, key_valid=key_valid, mask_bits=mb, sampling=sampling, stop=self._stop_list(eot_token),
                 use_graph=use_graph, trace=trace, repetition_penalty=repetition_penalty,
-                prompt_ids=prompt_ids, return_logprobs=return_logprobs, prefix=prefix, prompt_valid=prompt_valid)
+                prompt_ids=prompt_ids, return_logprobs=return_logprobs, prefix=prefix, prompt_valid=prompt_valid,
+                **self._constraint_kwargs(cons))
             if steps < max_new_tokens:              # (the host loop's shapes: the buffer is max_new_tokens wide)
                 tokens = torch.cat([tokens, tokens.new_zeros((R, max_new_tokens - steps))], dim=1)
                 if return_logprobs:
@@ -1430,7 +1574,11 @@ class UniGen(ModelMixin, ConfigMixin):
             hn = eng.prefill(st, prompt, mask_bits=mb)
         tokens = torch.zeros((R, max_new_tokens), dtype=torch.long, device=dev)
         lengths = torch.full((R,), max_new_tokens, dtype=torch.long, device=dev)
+        stop_ids = self._stop_list(eot_token) if cons is not None or isinstance(eot_token, (list, tuple)) else None
+        if stop_ids is not None:                    # (a list of ids, possibly empty: rows can still finish on a stop sequence)
+            eot_token = torch.tensor(stop_ids, dtype=torch.long, device=dev)
         pick, emit = (lambda last: self._pick_next(last, temperature, top_k)), emit_until_stop(tokens, eot_token, lengths=lengths)
+        done = emit.done
         logp = None
         if return_logprobs:
             logp = torch.zeros((R, max_new_tokens), dtype=torch.float32, device=dev)
@@ -1439,24 +1587,29 @@ class UniGen(ModelMixin, ConfigMixin):
         if repetition_penalty != 1.0:
             seen = seen_mask_of(prompt_ids, prompt_valid, R, self.config.vocab_size, dev)
             pick, emit = with_repetition_penalty(pick, emit, repetition_penalty, seen)
+        if cons is not None:
+            hist = history_of(prompt_ids, prompt_valid, R, self.config.vocab_size)
+            pick, emit = with_constraints(pick, emit, cons, done, hist, stop_ids=stop_ids, lengths=lengths)
         steps = self._decode_text(st, hn, max_new_tokens, pick, emit)
         return tokens, lengths, steps, logp
 
     @torch.no_grad()
     def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False,
-                             on_device=False, use_graph=True, repetition_penalty=1.0, return_logprobs=False, trace=None):
+                             on_device=False, use_graph=True, repetition_penalty=1.0, return_logprobs=False, trace=None, **constraints):
         """The one-row case of the batch path -> list of 0-d device tensors (one row: it ends at its `eot_token`, so every step counts);
         return_logprobs: (that list, the tokens' log-probabilities fp32 [steps])."""
         L = attention_mask.shape[-1]
         tokens, _, steps, logp = self._mmu_decode(idx, input_embeddings, attention_mask.reshape(1, 1, L, L), max_new_tokens, temperature, top_k,
                                                   eot_token, det, on_device=on_device, use_graph=use_graph,
-                                                  repetition_penalty=repetition_penalty, trace=trace, return_logprobs=return_logprobs)
+                                                  repetition_penalty=repetition_penalty, trace=trace, return_logprobs=return_logprobs,
+                                                  **constraints)
         return (list(tokens[0, :steps]), logp[0, :steps].clone()) if return_logprobs else list(tokens[0, :steps])
 
     @torch.no_grad()
     def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=0.0,
                            top_k=None, eot_token=None, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0, trace=None,
-                           return_logprobs=False, prefix=None, tail_valid=None):
+                           return_logprobs=False, prefix=None, tail_valid=None, logit_bias=None, suppress_tokens=None, min_new_tokens=None,
+                           no_repeat_ngram_size=None, stop_sequences=None):
         """`mmu_generate` for up to 32 prompts at once -- the rating loop of CoT-V (reference
         evaluation/inference_unigen_cot.py:308-415 calls mmu_generate once per (image, question) pair; every decode
         step streams the whole backbone whatever the row count, so R pairs cost about one).  Rows are LEFT-padded to a
@@ -1469,6 +1622,8 @@ class UniGen(ModelMixin, ConfigMixin):
         loops.  trace: a list that receives every eager on-device step's raw fp32 head logits (use_graph=False).
         return_logprobs: returns (the token lists, a list of fp32 1-D device tensors, row r's cut at its length): every token's
         log-probability as in `mmu_generate`.
+        logit_bias, suppress_tokens, min_new_tokens, no_repeat_ngram_size, stop_sequences: as in `mmu_generate`, both loops; a row's list is
+        cut behind the token that completes a stop sequence.
         prefix: an `mmu_prefix` object shared by every row -- one image, R questions: the image is prefilled once, not R times.
         `idx` / `input_embeddings` are then only the rows' tails [R, S], causal behind the prefix (no attention_mask: a dense one
         raises) and seeing of the prefix what its mask's last row saw.  tail_valid [R, S] (bool, None: all) marks the real tokens of
@@ -1484,6 +1639,10 @@ class UniGen(ModelMixin, ConfigMixin):
         elif tail_valid is not None:
             raise UniGenHipError("mmu_generate_batch: tail_valid belongs to a call with a prefix")
         penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate_batch")
+        cons, single_stops = checked_constraints("mmu_generate_batch", lambda: self.config.vocab_size, logit_bias, suppress_tokens,
+                                                 min_new_tokens, no_repeat_ngram_size, stop_sequences)
+        if single_stops:
+            eot_token = self._stop_list(eot_token) + [e for e in single_stops if e not in self._stop_list(eot_token)]
         det = resolve_deterministic(deterministic)
         self.llm.engine.last_decode_deterministic = det
         if prefix is None:
@@ -1492,11 +1651,12 @@ class UniGen(ModelMixin, ConfigMixin):
                 raise ValueError("mmu_generate_batch: at most 32 rows per call")
             if attention_mask is None or tuple(attention_mask.shape) != (R, 1, L, L):
                 raise ValueError("mmu_generate_batch: attention_mask must be the rows' dense [R, 1, L, L] additive masks")
-        dev_loop = self._text_on_device(on_device, "mmu_generate_batch", R, True, eot_token, max_new_tokens)
+        dev_loop = self._text_on_device(on_device, "mmu_generate_batch", R, True, eot_token, max_new_tokens, constraints=cons)
         self.llm.engine.last_text_decode_on_device = dev_loop
         tokens, lengths, _, logp = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
                                                     on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace,
-                                                    return_logprobs=bool(return_logprobs), prefix=prefix, tail_valid=tail_valid)
+                                                    return_logprobs=bool(return_logprobs), prefix=prefix, tail_valid=tail_valid,
+                                                    **self._constraint_kwargs(cons))
         tokens, lengths = tokens.cpu(), lengths.cpu()
         lists = [list(tokens[r, :int(lengths[r])]) for r in range(R)]
         if return_logprobs:

@@ -73,6 +73,8 @@ SIGNATURES = {
     "ug_text_sample_logp": [P, I64, I64, I64, I32, F32, I64, F32, P, P, P, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P, P],
     "ug_text_seen_mark": [P, I64, P, I64, I64, I64, P, I64, P],
     "ug_text_penalize": [P, I64, I64, I64, F32, P, I64, P, P],
+    "ug_text_constrain": [P, I64, I64, I64, P, I64, I64, P, I64, I64, P, I64, P, P, I64, P, P],
+    "ug_text_stop_seq": [P, P, I64, I64, P, I64, I64, P, P, P],
     "ug_maskgit_step": [P, I64, I64, I64, I64, I32, F32, P, P, P, I64, I64, I64, F32, P, P, P, P, P, P],
     "ug_maskgit_step_ex": [P, I64, I64, I64, I64, I32, F32, P, P, P, I64, I64, I64, F32, F32, I64, F32, F32, P, P, P, P, P, P, P, P],
     "ug_skinny_finish": [P, P, P, P, I64, I64, I32, P],

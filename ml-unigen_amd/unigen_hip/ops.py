@@ -920,6 +920,64 @@ def text_penalize_(logits, V, penalty, seen, tok=None):
                                         _p(tok), _stream()), "ug_text_penalize")
 
 
+# the on-device loop's limits for the constraints (include/unigen_hip.h: ug_text_constrain, ug_text_stop_seq); the host loop has none
+TEXT_MAX_BIAS, TEXT_MAX_NGRAM, TEXT_MAX_STOP_SEQS, TEXT_MAX_STOP_SEQ_LEN = 1024, 16, 8, 16
+
+
+def text_bias_pairs(entries, device):
+    """the device list of ug_text_constrain: int32 [n, 2] = (id, the fp32 bias's bits) for entries [(id, bias), ...]; a suppressed id
+    carries -inf.  None for an empty list."""
+    if not entries:
+        return None
+    pairs = torch.empty((len(entries), 2), dtype=torch.int32)
+    pairs[:, 0] = torch.tensor([int(e) for e, _ in entries], dtype=torch.int32)
+    pairs[:, 1] = torch.tensor([float(b) for _, b in entries], dtype=torch.float32).view(torch.int32)
+    return pairs.to(device)
+
+
+def text_stop_seqs(seqs, device):
+    """the packed stop sequences of ug_text_stop_seq -> (ids int32 [sum of lengths], offsets int32 [ns + 1]) on the device"""
+    ids = [int(t) for s in seqs for t in s]
+    off = [0]
+    for s in seqs:
+        off.append(off[-1] + len(s))
+    return torch.tensor(ids, dtype=torch.int32, device=device), torch.tensor(off, dtype=torch.int32, device=device)
+
+
+def text_constrain_(logits, V, state, out_tokens, bias=None, min_new=0, stop_ids=None, ngram=0, hist=None, hist_len=None):
+    """The constraints of a text step on fp32 logits [R, ld >= V] in place, ahead of text_penalize_ (include/unigen_hip.h:
+    ug_text_constrain): bias = ops.text_bias_pairs or None; the single stop ids (int64 device tensor or None) score -inf while the state
+    block's step is below min_new; ngram = n bans the n-grams of the history hist int32 [R, ld_hist] / hist_len int32 [R] (None: no
+    prompt part) followed by out_tokens int32 [R, nsteps] up to the step."""
+    _need_cuda(logits, state, out_tokens, bias, stop_ids, hist, hist_len)
+    R = logits.shape[0]
+    if logits.stride(1) != 1 or out_tokens.shape[0] != R or not out_tokens.is_contiguous() or out_tokens.dtype != torch.int32:
+        raise _l.UniGenHipError(f"text_constrain_: out_tokens {tuple(out_tokens.shape)} {out_tokens.dtype} against logits {tuple(logits.shape)}")
+    if bias is not None and not (bias.dtype == torch.int32 and bias.dim() == 2 and bias.shape[1] == 2 and bias.is_contiguous()):
+        raise _l.UniGenHipError("text_constrain_: bias must be ops.text_bias_pairs' contiguous int32 [n, 2]")
+    if (hist is None) != (hist_len is None) or (hist is not None and not (
+            hist.dtype == torch.int32 and hist_len.dtype == torch.int32 and hist.dim() == 2 and hist.shape[0] == R and hist.stride(1) == 1 and
+            hist_len.is_contiguous() and hist_len.numel() == R)):
+        raise _l.UniGenHipError("text_constrain_: hist int32 [R, ld_hist] and hist_len int32 [R] come together")
+    _l.check(_l.load().ug_text_constrain(_p(logits), logits.stride(0), R, int(V), _p(bias), 0 if bias is None else bias.shape[0], int(min_new),
+                                         _p(stop_ids), 0 if stop_ids is None else stop_ids.numel(), int(ngram), _p(hist),
+                                         0 if hist is None else hist.stride(0), _p(hist_len), _p(out_tokens), out_tokens.shape[1], _p(state),
+                                         _stream()), "ug_text_constrain")
+
+
+def text_stop_seq_(seq_ids, seq_off, out_tokens, state, lengths=None):
+    """The stop sequences behind the pick of a text step (include/unigen_hip.h: ug_text_stop_seq): seq_ids / seq_off =
+    ops.text_stop_seqs; out_tokens int32 [R, nsteps]; state: ops.text_state; lengths int32 [R] or None."""
+    _need_cuda(seq_ids, seq_off, out_tokens, state, lengths)
+    if not (seq_ids.dtype == seq_off.dtype == out_tokens.dtype == torch.int32 and seq_ids.is_contiguous() and seq_off.is_contiguous() and
+            out_tokens.dim() == 2 and out_tokens.is_contiguous() and seq_off.numel() >= 2):
+        raise _l.UniGenHipError("text_stop_seq_: int32 contiguous seq_ids, seq_off [ns + 1] and out_tokens [R, nsteps]")
+    if lengths is not None and not (lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == out_tokens.shape[0]):
+        raise _l.UniGenHipError("text_stop_seq_: lengths must be int32 [R]")
+    _l.check(_l.load().ug_text_stop_seq(_p(seq_ids), _p(seq_off), seq_off.numel() - 1, seq_ids.numel(), _p(out_tokens), out_tokens.shape[1],
+                                        out_tokens.shape[0], _p(state), _p(lengths), _stream()), "ug_text_stop_seq")
+
+
 # ------------------------------------------------------------------------------------ loss
 def ce_fwd(logits, V, labels, ignore_index=-100, want_logp=False):
     """logits bf16 [R, ld>=V]; -> (loss_and_count [2], lse [R], loss_row [R], logp|None)"""

@@ -249,10 +249,15 @@ class TextDecodeSession:
     repetition_penalty p != 1: the session owns the logits processor's `seen` bitmap [rows, ceil(vocab / 32)] (include/unigen_hip.h:
     ug_text_penalize) and every step launches the processor between head and pick; p == 1 allocates and launches nothing.
     logprobs: the session owns `logp` fp32 [rows, width] and every pick launch is the entry point that also writes the emitted token's
-    log-probability into it (ug_text_pick_logp / ug_text_sample_logp); off: no buffer, the entry points without the output."""
+    log-probability into it (ug_text_pick_logp / ug_text_sample_logp); off: no buffer, the entry points without the output.
+    constraints: None, or the dict models/unigen.py: checked_constraints returns (bias = [(id, bias or -inf), ...], min_new, ngram,
+    stop_seqs = [[ids], ...] of two or more ids each).  With a bias list, min_new or ngram the session owns the bias pairs and, for
+    ngram, the prompt history `hist` int32 [rows, capacity] + `hist_len` [rows], and every step launches ug_text_constrain ahead of the
+    penalty; with stop sequences it owns their packed ids and offsets and every step launches ug_text_stop_seq behind the pick.  All
+    off: nothing allocated, nothing launched."""
 
     def __init__(self, eng, rows, capacity, width, vocab, deterministic=False, sampling=None, stop_ids=(), pad_id=None, key_valid=None,
-                 repetition_penalty=1.0, logprobs=False):
+                 repetition_penalty=1.0, logprobs=False, constraints=None):
         dev, d = eng.device, eng.dims
         self.rows, self.width, self.V, self.sampling = rows, width, vocab, sampling
         self.form = eng.decode_form(rows, deterministic)
@@ -272,6 +277,13 @@ class TextDecodeSession:
         self.penalty = float(repetition_penalty)
         self.seen = ops.text_seen(rows, vocab, dev) if self.penalty != 1.0 else None
         self.logp = torch.zeros((rows, width), dtype=torch.float32, device=dev) if logprobs else None
+        c = constraints or {}
+        self.bias = ops.text_bias_pairs(c.get("bias"), dev)
+        self.min_new, self.ngram = int(c.get("min_new", 0)) if len(stop_ids) else 0, int(c.get("ngram", 0))
+        self.constrained = self.bias is not None or self.min_new > 0 or self.ngram > 0
+        self.hist = torch.zeros((rows, capacity), dtype=torch.int32, device=dev) if self.ngram else None
+        self.hist_len = torch.zeros((rows,), dtype=torch.int32, device=dev) if self.ngram else None
+        self.stop_seqs = ops.text_stop_seqs(c["stop_seqs"], dev) if c.get("stop_seqs") else None
         self.graph, self.key = None, None
 
     def begin(self, new_tokens, key_valid=None, prompt_len=0, prompt_ids=None, prompt_valid=None):
@@ -290,6 +302,16 @@ class TextDecodeSession:
             self.seen.zero_()
             if prompt_ids is not None and prompt_ids.shape[1] > 0:
                 ops.text_seen_mark_(self.seen, prompt_ids, self.V, prompt_valid)
+        if self.hist is not None:                   # the n-gram block's prompt history: the ids the penalty counts, compacted, in order
+            self.hist_len.zero_()
+            if prompt_ids is not None and prompt_ids.shape[1] > 0:
+                ids = prompt_ids.to(self.hist.device).long()
+                ok = (ids >= 0) & (ids < self.V)
+                if prompt_valid is not None:
+                    ok &= prompt_valid.to(ok.device) != 0
+                order = torch.argsort((~ok).to(torch.int8), dim=1, stable=True)
+                self.hist[:, :ids.shape[1]].copy_(torch.gather(ids, 1, order))
+                self.hist_len.copy_(ok.sum(1))
 
 
 class ArDecodeSession:
@@ -912,27 +934,43 @@ class Qwen2Engine:
         if sess.seen is not None:
             ops.text_penalize_(sess.logits, sess.V, sess.penalty, sess.seen, tok=None if first else sess.tok)
 
+    def text_constrain(self, sess):
+        """the constraints of a text step, ahead of the penalty (include/unigen_hip.h: ug_text_constrain); nothing without any"""
+        if sess.constrained:
+            ops.text_constrain_(sess.logits, sess.V, sess.state, sess.out_tokens, bias=sess.bias, min_new=sess.min_new,
+                                stop_ids=sess.stop_ids if sess.min_new else None, ngram=sess.ngram, hist=sess.hist, hist_len=sess.hist_len)
+
+    def text_stop_seq(self, sess):
+        """the stop sequences of a text step, behind the pick (include/unigen_hip.h: ug_text_stop_seq); nothing without any"""
+        if sess.stop_seqs is not None:
+            ops.text_stop_seq_(sess.stop_seqs[0], sess.stop_seqs[1], sess.out_tokens, sess.state, lengths=sess.lengths)
+
     def text_first_token(self, sess, hn, trace=None):
-        """token 0 from the prefill's final-norm hidden state: the GEMV head (ordered in deterministic mode) + the logits processor +
-        the pick.  trace takes the RAW head logits."""
+        """token 0 from the prefill's final-norm hidden state: the GEMV head (ordered in deterministic mode) + the constraints + the
+        logits processor + the pick + the stop sequences.  trace takes the RAW head logits."""
         if not sess.st.deterministic:
             sess.logits.zero_()                     # (the atomic GEMV adds into it)
         self.first_head(sess.st, hn, self.fp.w("embed")[:sess.V], sess.logits)
         if trace is not None:
             trace.append(sess.logits[:, :sess.V].clone())
+        self.text_constrain(sess)
         self.text_penalize(sess, first=True)
         self.text_pick(sess)
+        self.text_stop_seq(sess)
 
     def text_step(self, sess, trace=None):
         """One text decode step into the session's static buffers: the decoder stack on sess.x, the head over the whole vocabulary and
-        the pick (token, stop rule, records, next sess.x), the session's logits processor between them; advances the cache position.  No host sync, no shape depends on the step:
+        the pick (token, stop rule, records, next sess.x), the session's constraints and logits processor between them, its stop
+        sequences behind the pick; advances the cache position.  No host sync, no shape depends on the step:
         capturable.  The head is decode_step_head's, into the logits the pick leaves zeroed where the form's head adds.  trace: optional
         list taking the step's raw head logits (eager runs only)."""
         self.decode_step_head(sess.form, sess.st, sess.x, self.fp.w("embed")[:sess.V], sess.logits)
         if trace is not None and not torch.cuda.is_current_stream_capturing():
             trace.append(sess.logits[:, :sess.V].clone())
+        self.text_constrain(sess)
         self.text_penalize(sess)
         self.text_pick(sess)
+        self.text_stop_seq(sess)
 
     def decode_step(self, st, x):
         """x fp32 [rows, H] = embedding of the newest token (updated in place as the residual stream);

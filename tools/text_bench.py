@@ -14,7 +14,14 @@ One JSON line: per rows and setting, every call's tokens/s and ms per step for b
 times the ON-DEVICE loop alone, greedy, with the logits processor (repetition_penalty=P: one ug_text_penalize launch per step, one
 ug_text_seen_mark per call) against the same build without it, alternating in one process.  The penalty is part of the kept
 session's key, so each visit to a mode makes two calls and times the second (it replays the graph the first one captured), then
-one one-token call of the same session for the prefill + first token.  Five visits per mode after one untimed visit each."""
+one one-token call of the same session for the prefill + first token.  Five visits per mode after one untimed visit each.
+
+    python tools/text_bench.py --constraints
+
+the same pairing for the constraints (one ug_text_constrain launch per step ahead of the penalty, one ug_text_stop_seq launch behind the
+pick): all off against logit_bias (64 ids), suppress_tokens (64 ids), min_new_tokens (with a stop id no row produces, which the "off"
+of that pair carries too), no_repeat_ngram_size=3 (the 768 prompt ids are the history), stop_sequences (8 of 16 ids no row produces), and
+all five at once."""
 import json
 import os
 import statistics
@@ -37,6 +44,21 @@ SETTINGS = {
 
 
 def penalty_pair(penalty, rounds=5):
+    paired((("off", {}), ("on", dict(repetition_penalty=float(penalty)))), {"repetition_penalty": penalty}, rounds)
+
+
+def constraint_modes():
+    ids = list(range(1000, 1064))
+    never = VOCAB - 1                                # (the mask token: the backbone's argmax never lands there)
+    seqs = [[never - 1 - j for j in range(16)] for _ in range(8)]
+    each = {"logit_bias": dict(logit_bias={e: 0.5 for e in ids}), "suppress_tokens": dict(suppress_tokens=[e + 1000 for e in ids]),
+            "min_new_tokens": dict(min_new_tokens=32, eot_token=never), "no_repeat_ngram_size": dict(no_repeat_ngram_size=3),
+            "stop_sequences": dict(stop_sequences=seqs)}
+    every = {k: v for kw in each.values() for k, v in kw.items()}
+    return (("off", {}), ("off_with_stop_id", dict(eot_token=never))) + tuple(each.items()) + (("all", every),)
+
+
+def paired(modes, label, rounds=5):
     dev = torch.device("cuda:0")
     rows = [int(r) for r in os.environ.get("ROWS", "1,16").split(",")]
     model = UniGen(w_und_encoder=False, vocab_size=VOCAB, llm_vocab_size=TEXT_VOCAB, llm_model_path="Qwen2.5-1.5B-Instruct",
@@ -46,16 +68,15 @@ def penalty_pair(penalty, rounds=5):
     g = torch.Generator(device=dev).manual_seed(2)
     r = torch.arange(L, device=dev)
     allow = (r[None, :] <= r[:, None]) | ((r[None, :] >= 20) & (r[None, :] < 749))
-    result = {"prompt": L, "new_tokens": NEW, "repetition_penalty": penalty, "loop": "device", "setting": "greedy", "rows": {}}
-    modes = (("off", 1.0), ("on", float(penalty)))
+    result = {"prompt": L, "new_tokens": NEW, **label, "loop": "device", "setting": "greedy", "rows": {}}
     for R in rows:
         idx = torch.randint(0, 151643, (R, L), device=dev, generator=g)
         mask = torch.where(allow, 0.0, torch.finfo(torch.float32).min)[None, None].expand(R, 1, L, L).contiguous()
 
-        def call(p, new=NEW):
+        def call(kw, new=NEW):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            out = model.mmu_generate_batch(idx=idx, attention_mask=mask, max_new_tokens=new, temperature=0.0, on_device=True, repetition_penalty=p)
+            out = model.mmu_generate_batch(idx=idx, attention_mask=mask, max_new_tokens=new, temperature=0.0, on_device=True, **kw)
             torch.cuda.synchronize()
             assert all(len(o) == new for o in out) and model.llm.engine.last_text_decode_on_device
             return time.perf_counter() - t0
@@ -75,8 +96,9 @@ def penalty_pair(penalty, rounds=5):
             rec[name] = {"call_s": [round(t, 4) for t in times[name]], "first_token_call_s": round(f, 4),
                          "ms_per_step": [round(m, 4) for m in step_ms], "tokens_per_s": [round(1e3 * R / m, 1) for m in step_ms]}
         med = lambda name: statistics.median(rec[name]["ms_per_step"])
-        rec["on_over_off_tokens_per_s"] = round(med("off") / med("on"), 4)
-        rec["extra_us_per_step"] = round(1e3 * (med("on") - med("off")), 2)
+        for name, _ in modes[1:]:
+            rec[name]["over_off_tokens_per_s"] = round(med("off") / med(name), 4)
+            rec[name]["extra_us_per_step"] = round(1e3 * (med(name) - med("off")), 2)
         result["rows"][str(R)] = rec
         model.drop_decode_session()
     print(json.dumps(result))
@@ -133,5 +155,7 @@ def main():
 if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--repetition-penalty":
         penalty_pair(float(sys.argv[2]))
+    elif len(sys.argv) > 1 and sys.argv[1] == "--constraints":
+        paired(constraint_modes(), {"constraints": True})
     else:
         main()
