@@ -18,6 +18,7 @@ Behavioural notes (all mirror the reference unless stated):
     generation; t2i_generate_ar with it raises.
 """
 import collections
+import dataclasses
 import json
 import math
 import os
@@ -119,7 +120,7 @@ def with_logprobs(process, choose, emit, logp):
     """`pick` and `emit` of text_token_loop that also record every emitted token's log-probability into logp fp32 [R, new]
     (models/sampling.py: token_logprobs): pick = choose(process(last)), where `process` turns the scores it is handed (behind the
     repetition penalty, if any) into the ones `choose` picks from (temperature, top-k / top-p as -inf).  `emit` is emit_until_stop's: a
-    row that had finished before the step records 0.0.  Wrap the result in with_repetition_penalty, not the other way round."""
+    row that had finished before the step records 0.0.  The innermost wrapper (text_pick_emit holds the order)."""
     from .sampling import token_logprobs
     last_lp = [None]
 
@@ -186,8 +187,8 @@ def checked_constraints(who, vocab, logit_bias=None, suppress_tokens=None, min_n
 
 def with_constraints(pick, emit, constraints, done, histories, stop_ids=(), lengths=None):
     """`pick` and `emit` of text_token_loop with the constraints of checked_constraints in front of everything else (models/sampling.py:
-    apply_constraints; the order is include/unigen_hip.h's: the -inf stores commute with the repetition penalty, so wrap the result of
-    with_repetition_penalty, which wraps with_logprobs' -- the log-probabilities are then those of the fully processed scores).
+    apply_constraints; the order is include/unigen_hip.h's: the -inf stores commute with the repetition penalty, so this is the
+    outermost wrapper -- text_pick_emit holds the order -- and the log-probabilities are those of the fully processed scores).
     done: emit_until_stop's `emit.done`; histories: sampling.history_of's lists, which take every token `emit` feeds back (a finished
     row's pad id included, as on the device); stop_ids: the single stop ids min_new_tokens holds back; lengths: emit_until_stop's.
     A stop sequence is matched on the emitted tokens alone and finishes a row exactly as a stop id does -- once, at the step whose
@@ -217,6 +218,149 @@ def with_constraints(pick, emit, constraints, done, histories, stop_ids=(), leng
             stop = bool(done.all())
         return feed, stop
     return constrained_pick, emit_and_match
+
+
+def stop_list(stop):
+    """the stop ids of a call (None, an id, a list, or a 0-d / 1-D tensor of ids) as a list of ints"""
+    if stop is None:
+        return []
+    if torch.is_tensor(stop):
+        return [int(v) for v in stop.reshape(-1).tolist()]
+    if isinstance(stop, (list, tuple)):
+        return [int(v) for v in stop]
+    return [int(stop)]
+
+
+@dataclasses.dataclass(frozen=True)
+class TextCall:
+    """How one call of `generate` / `mmu_generate` / `mmu_generate_batch` decodes: everything that does not depend on the prompt,
+    checked and resolved once (text_call) and read by both loops.  The entry points' docstrings say what each option means."""
+    who: str                        # the entry point's name, for error messages
+    sampling: Optional[tuple]       # the on-device loop's constants: None (greedy) or (temperature, top_k, top_p)
+    process: object                 # the host loop's rule (generate_rule / mmu_rule): scores -> the scores `choose` picks from,
+    choose: object                  # and those -> token ids [R, 1]
+    generator: Optional[torch.Generator]
+    stop: list                      # the stop ids, stop sequences of one id merged in
+    host_stop: object               # what the host loop's emit_until_stop compares a token with (text_call)
+    pad_token_id: Optional[int]
+    penalty: float                  # checked_repetition_penalty's
+    constraints: Optional[dict]     # checked_constraints' dict
+    return_logprobs: bool
+    deterministic: bool
+    use_graph: bool
+    trace: Optional[list]
+
+    @property
+    def stops(self):
+        """whether a row can finish before max_new_tokens (a stop id, or a stop sequence of two or more ids)"""
+        return bool(self.stop or (self.constraints and self.constraints["stop_seqs"]))
+
+
+def generate_rule(do_sample, temperature, top_k, top_p, generator):
+    """`generate`'s host sampling rule -> (process, choose): temperature, then top_k_top_p_filtering, then torch.multinomial with the
+    caller's generator on the generator's device; greedy: the scores as they are, argmax"""
+    from .sampling import top_k_top_p_filtering
+
+    def process(last):
+        if not do_sample:
+            return last
+        if temperature is not None and temperature != 1.0:
+            last = last / temperature
+        return top_k_top_p_filtering(last, top_k=int(top_k or 0), top_p=float(1.0 if top_p is None else top_p))
+
+    def choose(scores):
+        if not do_sample:
+            return scores.argmax(-1, keepdim=True)
+        u_dev = scores.device if generator is None else generator.device
+        return torch.multinomial(torch.softmax(scores, dim=-1).to(u_dev), num_samples=1, generator=generator).to(scores.device)
+    return process, choose
+
+
+def mmu_rule(temperature, top_k):
+    """the mmu entry points' host sampling rule -> (process, choose): UniGen._process_next / _choose_next (temperature, an in-place
+    top-k threshold, torch.multinomial from the default generator; temperature 0: argmax)"""
+    return (lambda last: UniGen._process_next(last, temperature, top_k)), (lambda scores: UniGen._choose_next(scores, temperature))
+
+
+def text_call(who, vocab, sampling, rule, stop, pad_finished=False, pad_token_id=None, generator=None, repetition_penalty=None,
+              deterministic=None, return_logprobs=False, use_graph=True, trace=None, logit_bias=None, suppress_tokens=None,
+              min_new_tokens=None, no_repeat_ngram_size=None, stop_sequences=None):
+    """The TextCall of one public call, with every check that needs no prompt, before any launch.  vocab: a callable that returns V
+    (checked_constraints).  rule: the (process, choose) of generate_rule / mmu_rule.  stop: the caller's stop ids in any form
+    stop_list takes -- a device tensor is read here, once; the stop sequences of one id join them unless already there (the caller's
+    own list is kept as given).  pad_finished (`generate`): finished rows are filled with pad_token_id, which defaults to the first
+    stop id, and stop sequences need one of the two.
+    host_stop keeps the operand of the host loop's per-token compare what each entry point has always handed emit_until_stop (the
+    same launches): `generate` a tensor of the ids, or None when no row can finish; the mmu entry points the caller's own id or
+    tensor while nothing was merged into it and no constraint is on, else the list (a list becomes a tensor: text_pick_emit)."""
+    from unigen_hip.qwen2 import resolve_deterministic
+    penalty = checked_repetition_penalty(repetition_penalty, who)
+    cons, singles = checked_constraints(who, vocab, logit_bias, suppress_tokens, min_new_tokens, no_repeat_ngram_size, stop_sequences)
+    ids = stop_list(stop)
+    if pad_finished:
+        if stop_sequences and stop is None and pad_token_id is None:
+            raise UniGenHipError(f"{who}: stop_sequences need an eos_token_id or a pad_token_id (a finished row is filled with it)")
+        if ids and pad_token_id is None:
+            pad_token_id = ids[0]
+    ids = ids + [e for e in singles if e not in ids]
+    if pad_finished:
+        host_stop = ids if ids or (cons and cons["stop_seqs"]) else None
+    else:
+        host_stop = ids if cons is not None or singles or isinstance(stop, (list, tuple)) else stop
+    return TextCall(who, sampling, rule[0], rule[1], generator, ids, host_stop, pad_token_id, penalty, cons, bool(return_logprobs),
+                    resolve_deterministic(deterministic), bool(use_graph), trace)
+
+
+def generate_call(vocab, do_sample, temperature, top_k, top_p, eos_token_id, pad_token_id, generator, deterministic, return_logprobs,
+                  kwargs):
+    """`generate`'s arguments -> (TextCall, num_return_sequences)"""
+    unsupported = [k for k in ("num_beams", "penalty_alpha") if kwargs.get(k) not in (None, 1, 1.0)]
+    if unsupported:
+        raise UniGenHipError(f"generate: {unsupported} are not implemented (greedy / sampling only)")
+    sampling = None
+    if do_sample:
+        sampling = (float(1.0 if temperature is None else temperature), int(top_k or 0), float(1.0 if top_p is None else top_p))
+    call = text_call("generate", vocab, sampling, generate_rule(do_sample, temperature, top_k, top_p, generator), eos_token_id,
+                     pad_finished=True, pad_token_id=pad_token_id, generator=generator, deterministic=deterministic,
+                     return_logprobs=return_logprobs, use_graph=kwargs.get("use_graph", True), trace=kwargs.get("trace"),
+                     **{k: kwargs.get(k) for k in ("repetition_penalty", "logit_bias", "suppress_tokens", "min_new_tokens",
+                                                   "no_repeat_ngram_size", "stop_sequences")})
+    n_ret = kwargs.get("num_return_sequences")
+    n_ret = 1 if n_ret is None else int(n_ret)
+    if n_ret < 1:
+        raise UniGenHipError(f"generate: num_return_sequences={n_ret} must be at least 1")
+    if n_ret > 1 and not do_sample:
+        raise UniGenHipError(f"generate: num_return_sequences={n_ret} needs do_sample=True (greedy rows would all be equal)")
+    return call, n_ret
+
+
+def mmu_call(who, vocab, temperature, top_k, eot_token, **how):
+    """the arguments of `mmu_generate` / `mmu_generate_batch` -> TextCall (temperature 0 is greedy; `how`: text_call's keywords)"""
+    sampling = (float(temperature), int(top_k or 0), 1.0) if temperature > 0 else None
+    return text_call(who, vocab, sampling, mmu_rule(temperature, top_k), eot_token, **how)
+
+
+def text_pick_emit(call, out, vocab, logp=None, lengths=None, prompt_ids=None, prompt_valid=None):
+    """`pick` and `emit` of text_token_loop for a call: the one place that holds the wrap order -- emit_until_stop, then with_logprobs,
+    then with_repetition_penalty, then with_constraints, so that a step runs the constraints, the penalty, the call's process / choose
+    and the log-probability of the fully processed scores (the order of include/unigen_hip.h: "Constraints of the text loops").
+    out long [R, new] takes the tokens, logp fp32 [R, new] (or None) their log-probabilities, lengths [R] (or None) is
+    emit_until_stop's; prompt_ids / prompt_valid [R, L] are what the penalty and the n-gram history count of the prompt."""
+    from .sampling import history_of, seen_mask_of
+    R, dev = out.shape[0], out.device
+    stop = torch.tensor(call.host_stop, dtype=torch.long, device=dev) if isinstance(call.host_stop, list) else call.host_stop
+    emit = emit_until_stop(out, stop, call.pad_token_id, lengths)
+    done = emit.done
+    if logp is None:
+        pick = lambda last: call.choose(call.process(last))
+    else:
+        pick, emit = with_logprobs(call.process, call.choose, emit, logp)
+    if call.penalty != 1.0:
+        pick, emit = with_repetition_penalty(pick, emit, call.penalty, seen_mask_of(prompt_ids, prompt_valid, R, vocab, dev))
+    if call.constraints is not None:
+        pick, emit = with_constraints(pick, emit, call.constraints, done, history_of(prompt_ids, prompt_valid, R, vocab),
+                                      stop_ids=call.stop, lengths=lengths)
+    return pick, emit
 
 
 MMU_MAX_ROWS = 32
@@ -262,19 +406,62 @@ class MmuPrefix:
         return self
 
 
-def check_mmu_prefix_call(who, engine, prefix, idx, input_embeddings, attention_mask, tail_valid):
-    """The argument checks of a generation call that takes `prefix`, all on the host and before anything is launched
-    -> (rows, tail length, tail_valid as a bool tensor or None)."""
+def check_prefix(who, engine, prefix, rows=None, what=None):
+    """what every call that takes `prefix` checks of it: its type, that this engine built it, and (when the call's rows are at hand:
+    a tensor, named `what` in the message) that they live on its device"""
     if not isinstance(prefix, MmuPrefix):
         raise UniGenHipError(f"{who}: prefix must be the object UniGen.mmu_prefix returns, got {type(prefix).__name__}")
     if prefix.engine is not engine:
         raise UniGenHipError(f"{who}: the prefix was built by another model")
+    if rows is not None:
+        pd, td = torch.device(prefix.device), rows.device
+        if td.type != pd.type or (td.index is not None and pd.index is not None and td.index != pd.index):
+            raise UniGenHipError(f"{who}: the prefix lives on another device ({pd}) than the {what} ({td})")
+
+
+def _prefill_after_prefix(engine, st, prefix, tails, key_valid, hidden_at=None):
+    """the prefill of a call that takes a prefix: the prefix's keys / values of every layer into positions [0, P) of every row of
+    `st`, then the rows' tails [R, S, H] onto them (Qwen2Engine.prefill_onto) -> final-norm hidden of the last tail position
+    (with hidden_at: prefill_onto's pair)"""
+    P = prefix.P
+    for i in range(len(st.k)):
+        st.k[i][:, :, :P].copy_(prefix.st.k[i][:, :, :P])          # (one row, broadcast to the call's rows)
+        st.v[i][:, :, :P].copy_(prefix.st.v[i][:, :, :P])
+    if hidden_at is None:
+        return engine.prefill_onto(st, tails, P, key_valid)
+    return engine.prefill_onto(st, tails, P, key_valid, hidden_at=hidden_at)
+
+
+@dataclasses.dataclass(frozen=True)
+class TextPrompt:
+    """The prompt of one text generation call, as both loops read it (built by UniGen._generate_prompt / _dense_prompt /
+    _prefix_prompt)."""
+    embeds: torch.Tensor                     # fp32 [R, L, H] to prefill; behind a prefix the rows' tails [R, S, H]
+    L: int                                   # positions of the prompt (P + S with a prefix)
+    key_valid: Optional[torch.Tensor]        # bool [R, L]: the keys every later position sees (None: all)
+    mask_bits: Optional[object]              # the compressed dense mask to prefill under (None: causal with key_valid)
+    prompt_ids: Optional[torch.Tensor]       # [R, L]: the ids the repetition penalty and the n-gram history count (None: no ids),
+    prompt_valid: Optional[torch.Tensor]     # at the positions this marks real
+    prefix: Optional[MmuPrefix] = None
+
+    @property
+    def rows(self):
+        return int(self.embeds.shape[0])
+
+    def prefill(self, engine, st):
+        """prefill the prompt into `st` -> final-norm hidden state of its last position, bf16 [R, H]"""
+        if self.prefix is not None:
+            return _prefill_after_prefix(engine, st, self.prefix, self.embeds, self.key_valid)
+        return engine.prefill(st, self.embeds, self.key_valid, mask_bits=self.mask_bits)
+
+
+def check_mmu_prefix_call(who, engine, prefix, idx, input_embeddings, attention_mask, tail_valid):
+    """The argument checks of a generation call that takes `prefix`, all on the host and before anything is launched
+    -> (rows, tail length, tail_valid as a bool tensor or None)."""
+    tail = idx if input_embeddings is None else input_embeddings
+    check_prefix(who, engine, prefix, tail, "tails")
     if (idx is None) == (input_embeddings is None):
         raise UniGenHipError(f"{who}: with a prefix, give the rows' tails as idx [R, S] or input_embeddings [R, S, H]")
-    tail = idx if input_embeddings is None else input_embeddings
-    pd, td = torch.device(prefix.device), tail.device
-    if td.type != pd.type or (td.index is not None and pd.index is not None and td.index != pd.index):
-        raise UniGenHipError(f"{who}: the prefix lives on another device ({pd}) than the tails ({td})")
     if tail.dim() != (2 if input_embeddings is None else 3) or tail.shape[1] < 1:
         raise UniGenHipError(f"{who}: the tails must be [R, S] ids or [R, S, H] embeddings with S >= 1, got {tuple(tail.shape)}")
     R, S = int(tail.shape[0]), int(tail.shape[1])
@@ -328,13 +515,7 @@ def check_score_call(who, engine, prefix, idx, input_embeddings, targets, tail_v
         raise UniGenHipError(f"{who}: image-code targets (ids >= {image_codes_from}) cannot be scored on a model with a gen_projector: "
                              f"their inputs go through gen_embed, which this call does not apply")
     if prefix is not None:
-        if not isinstance(prefix, MmuPrefix):
-            raise UniGenHipError(f"{who}: prefix must be the object UniGen.mmu_prefix returns, got {type(prefix).__name__}")
-        if prefix.engine is not engine:
-            raise UniGenHipError(f"{who}: the prefix was built by another model")
-        pd, td = torch.device(prefix.device), ctx.device
-        if td.type != pd.type or (td.index is not None and pd.index is not None and td.index != pd.index):
-            raise UniGenHipError(f"{who}: the prefix lives on another device ({pd}) than the contexts ({td})")
+        check_prefix(who, engine, prefix, ctx, "contexts")
     if tail_valid is not None:
         tail_valid = torch.as_tensor(tail_valid)
         if tuple(tail_valid.shape) != (R, S):
@@ -1093,22 +1274,8 @@ class UniGen(ModelMixin, ConfigMixin):
         entries, n <= 16 and 8 stop sequences of at most 16 ids (an explicit on_device=True beyond that raises, a default-derived one
         falls back to the host loop).  An id in both lists, twice in one, or outside [0, V) raises before any launch.
         num_beams and penalty_alpha are refused."""
-        from unigen_hip.qwen2 import DecodeState, resolve_deterministic
-        from .sampling import history_of, seen_mask_of, top_k_top_p_filtering
-        unsupported = [k for k in ("num_beams", "penalty_alpha") if kwargs.get(k) not in (None, 1, 1.0)]
-        if unsupported:
-            raise UniGenHipError(f"generate: {unsupported} are not implemented (greedy / sampling only)")
-        penalty = checked_repetition_penalty(kwargs.get("repetition_penalty"), "generate")
-        cons, single_stops = checked_constraints("generate", lambda: self.config.vocab_size, kwargs.get("logit_bias"), kwargs.get("suppress_tokens"),
-                                                 kwargs.get("min_new_tokens"), kwargs.get("no_repeat_ngram_size"), kwargs.get("stop_sequences"))
-        if kwargs.get("stop_sequences") and eos_token_id is None and pad_token_id is None:
-            raise UniGenHipError("generate: stop_sequences need an eos_token_id or a pad_token_id (a finished row is filled with it)")
-        n_ret = kwargs.get("num_return_sequences")
-        n_ret = 1 if n_ret is None else int(n_ret)
-        if n_ret < 1:
-            raise UniGenHipError(f"generate: num_return_sequences={n_ret} must be at least 1")
-        if n_ret > 1 and not do_sample:
-            raise UniGenHipError(f"generate: num_return_sequences={n_ret} needs do_sample=True (greedy rows would all be equal)")
+        call, n_ret = generate_call(lambda: self.config.vocab_size, do_sample, temperature, top_k, top_p, eos_token_id, pad_token_id, generator,
+                                    deterministic, return_logprobs, kwargs)
         if n_ret > 1:
             input_ids = None if input_ids is None else input_ids.repeat_interleave(n_ret, dim=0)
             input_embeddings = None if input_embeddings is None else input_embeddings.repeat_interleave(n_ret, dim=0)
@@ -1116,71 +1283,13 @@ class UniGen(ModelMixin, ConfigMixin):
         if "max_length" in kwargs and kwargs["max_length"] is not None and input_ids is not None:
             max_new_tokens = int(kwargs["max_length"]) - input_ids.shape[1]
         eng = self.llm.engine
-        embed = self.llm.model.embed_tokens
-        dev = eng.device
-        prompt = (embed(input_ids.to(dev)) if input_embeddings is None else input_embeddings.to(dev)).float()
-        R, L, _ = prompt.shape
-        key_valid = None
-        if attention_mask is not None:
-            if attention_mask.dim() != 2:
-                raise UniGenHipError("generate expects a 2-D [rows, L] attention mask (1 = real token)")
-            key_valid = attention_mask.to(dev) != 0
-        eos = [] if eos_token_id is None else ([int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple)) else [int(eos_token_id)])
-        if eos and pad_token_id is None:
-            pad_token_id = eos[0]
-        eos = eos + [e for e in single_stops if e not in eos]       # stop sequences of one id are stop ids
-        stops = bool(eos or (cons and cons["stop_seqs"]))
-        det = resolve_deterministic(deterministic)
-        eng.last_decode_deterministic = det
-        eng.last_text_decode_on_device = self._text_on_device(on_device, "generate", R, bool(use_cache), eos, max_new_tokens, constraints=cons)
-        if eng.last_text_decode_on_device:
-            sampling = None
-            if do_sample:
-                sampling = (float(1.0 if temperature is None else temperature), int(top_k or 0), float(1.0 if top_p is None else top_p))
-            out, _, _, logp = self._decode_text_on_device(
-                prompt, max_new_tokens, det, key_valid=key_valid, sampling=sampling, stop=eos, pad_token_id=pad_token_id if stops else None,
-                generator=generator, use_graph=bool(kwargs.get("use_graph", True)), trace=kwargs.get("trace"), repetition_penalty=penalty,
-                prompt_ids=None if input_embeddings is not None else input_ids.to(dev), return_logprobs=bool(return_logprobs),
-                **self._constraint_kwargs(cons))
-            seqs = torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
-            return (seqs, logp) if return_logprobs else seqs
-        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
-        hn = eng.prefill(st, prompt, key_valid)
-        eng.check_errors()
-        out = torch.full((R, max_new_tokens), int(pad_token_id or 0), dtype=torch.long, device=dev)
-
-        def process(last):                           # the scores the pick chooses from (greedy: no temperature, no filter)
-            if not do_sample:
-                return last
-            if temperature is not None and temperature != 1.0:
-                last = last / temperature
-            return top_k_top_p_filtering(last, top_k=int(top_k or 0), top_p=float(1.0 if top_p is None else top_p))
-
-        def choose(scores):
-            if not do_sample:
-                return scores.argmax(-1, keepdim=True)
-            u_dev = dev if generator is None else generator.device
-            return torch.multinomial(torch.softmax(scores, dim=-1).to(u_dev), num_samples=1, generator=generator).to(dev)
-
-        def pick(last):
-            return choose(process(last))
-
-        stop = torch.tensor(eos, dtype=torch.long, device=dev) if stops else None        # (stop sequences alone: no ids, rows still finish)
-        emit = emit_until_stop(out, stop, pad_token_id)
-        done = emit.done
-        logp = None
-        if return_logprobs:
-            logp = torch.zeros((R, max_new_tokens), dtype=torch.float32, device=dev)
-            pick, emit = with_logprobs(process, choose, emit, logp)
-        if penalty != 1.0:
-            seen = seen_mask_of(None if input_embeddings is not None else input_ids, key_valid, R, self.config.vocab_size, dev)
-            pick, emit = with_repetition_penalty(pick, emit, penalty, seen)
-        if cons is not None:
-            hist = history_of(None if input_embeddings is not None else input_ids, key_valid, R, self.config.vocab_size)
-            pick, emit = with_constraints(pick, emit, cons, done, hist, stop_ids=eos)
-        steps = self._decode_text(st, hn, max_new_tokens, pick, emit)
+        prompt = self._generate_prompt(input_ids, input_embeddings, attention_mask)
+        eng.last_decode_deterministic = call.deterministic
+        eng.last_text_decode_on_device = self._text_on_device(on_device, call, prompt.rows, bool(use_cache), max_new_tokens)
+        run = self._decode_text_on_device if eng.last_text_decode_on_device else self._run_text_host
+        out, _, steps, logp = run(call, prompt, max_new_tokens)
         out = out[:, :steps]
-        seqs = torch.cat([input_ids.to(dev), out], dim=1) if input_embeddings is None else out
+        seqs = torch.cat([prompt.prompt_ids, out], dim=1) if input_embeddings is None else out
         return (seqs, logp[:, :steps]) if return_logprobs else seqs
 
     # ------------------------------------------------------------------ text decoding for understanding
@@ -1215,18 +1324,6 @@ class UniGen(ModelMixin, ConfigMixin):
         eng.prefill(st, prompt, mask_bits=mb)
         eng.check_errors()
         return MmuPrefix(self, st, P, key_valid, None if idx is None else idx.to(dev).long())
-
-    def _prefill_after_prefix(self, st, prefix, tails, key_valid, hidden_at=None):
-        """the prefill of a call that takes a prefix: the prefix's keys / values of every layer into positions [0, P) of every row of
-        `st`, then the rows' tails [R, S, H] onto them (Qwen2Engine.prefill_onto) -> final-norm hidden of the last tail position
-        (with hidden_at: prefill_onto's pair)"""
-        P = prefix.P
-        for i in range(len(st.k)):
-            st.k[i][:, :, :P].copy_(prefix.st.k[i][:, :, :P])          # (one row, broadcast to the call's rows)
-            st.v[i][:, :, :P].copy_(prefix.st.v[i][:, :, :P])
-        if hidden_at is None:
-            return self.llm.engine.prefill_onto(st, tails, P, key_valid)
-        return self.llm.engine.prefill_onto(st, tails, P, key_valid, hidden_at=hidden_at)
 
     @torch.no_grad()
     def score(self, idx=None, input_embeddings=None, targets=None, prefix=None, tail_valid=None, average=False):
@@ -1269,7 +1366,7 @@ class UniGen(ModelMixin, ConfigMixin):
             if prefix is None:
                 _, hn = eng.prefill_onto(st, seq[r0:r0 + n], 0, key_valid[r0:r0 + n], hidden_at=hidden_at)
             else:
-                _, hn = self._prefill_after_prefix(st, prefix, seq[r0:r0 + n], key_valid[r0:r0 + n], hidden_at=hidden_at)
+                _, hn = _prefill_after_prefix(eng, st, prefix, seq[r0:r0 + n], key_valid[r0:r0 + n], hidden_at=hidden_at)
             logp, _, b = eng.score_rows(hn, labels[r0:r0 + n].reshape(-1))
             token_logprobs[r0:r0 + n] = logp.view(n, C)
             best[r0:r0 + n] = b.view(n, C)
@@ -1302,41 +1399,31 @@ class UniGen(ModelMixin, ConfigMixin):
         min_new_tokens holds `eot_token` back, a stop sequence ends the list like `eot_token` does.  The recompute form raises for them.
         prefix: an `mmu_prefix` object; `idx` / `input_embeddings` are then only the continuation [1, S], which is causal (no
         attention_mask) and sees of the prefix what its mask's last row saw.  Cached form only; everything else as without."""
-        from unigen_hip.qwen2 import resolve_deterministic
         if prefix is not None:
             check_mmu_prefix_call("mmu_generate", self.llm.engine, prefix, idx, input_embeddings, attention_mask, None)
             if (idx if input_embeddings is None else input_embeddings).shape[0] != 1:
                 raise UniGenHipError("mmu_generate: one row per call (mmu_generate_batch takes several)")
             if not use_cache:
                 raise UniGenHipError("mmu_generate: a prefix needs the cached form (use_cache=True)")
-        penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate")
-        cons, single_stops = checked_constraints("mmu_generate", lambda: self.config.vocab_size, logit_bias, suppress_tokens, min_new_tokens,
-                                                 no_repeat_ngram_size, stop_sequences)
-        if single_stops:
-            eot_token = self._stop_list(eot_token) + single_stops
-        ckw = self._constraint_kwargs(cons)
-        det = resolve_deterministic(deterministic)
-        self.llm.engine.last_decode_deterministic = det
-        if prefix is not None:
-            dev_loop = self._text_on_device(on_device, "mmu_generate", 1, True, eot_token, max_new_tokens, constraints=cons)
-            self.llm.engine.last_text_decode_on_device = dev_loop
-            tokens, _, steps, logp = self._mmu_decode(idx, input_embeddings, None, max_new_tokens, temperature, top_k, eot_token, det,
-                                                      on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace,
-                                                      return_logprobs=bool(return_logprobs), prefix=prefix, **ckw)
-            return (list(tokens[0, :steps]), logp[0, :steps].clone()) if return_logprobs else list(tokens[0, :steps])
-        cached = bool(use_cache and attention_mask is not None and attention_mask.shape[0] == 1)
-        dev_loop = self._text_on_device(on_device, "mmu_generate", 1, cached, eot_token, max_new_tokens, constraints=cons)
-        self.llm.engine.last_text_decode_on_device = dev_loop
+        call = mmu_call("mmu_generate", lambda: self.config.vocab_size, temperature, top_k, eot_token, repetition_penalty=repetition_penalty,
+                        deterministic=deterministic, return_logprobs=return_logprobs, use_graph=use_graph, trace=trace, logit_bias=logit_bias,
+                        suppress_tokens=suppress_tokens, min_new_tokens=min_new_tokens, no_repeat_ngram_size=no_repeat_ngram_size,
+                        stop_sequences=stop_sequences)
+        eng = self.llm.engine
+        eng.last_decode_deterministic = call.deterministic
+        cached = prefix is not None or bool(use_cache and attention_mask is not None and attention_mask.shape[0] == 1)
+        eng.last_text_decode_on_device = self._text_on_device(on_device, call, 1, cached, max_new_tokens)
         if cached:
-            return self._mmu_generate_cached(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
-                                             on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty,
-                                             return_logprobs=bool(return_logprobs), trace=trace, **ckw)
-        if cons is not None or single_stops:
+            mask = None if prefix is not None else attention_mask.reshape(1, 1, attention_mask.shape[-1], attention_mask.shape[-1])
+            tokens, _, steps, logp = self._mmu_decode(call, idx, input_embeddings, mask, max_new_tokens, eng.last_text_decode_on_device, prefix)
+            # (one row: it ends at its `eot_token`, so every step counts)
+            return (list(tokens[0, :steps]), logp[0, :steps].clone()) if return_logprobs else list(tokens[0, :steps])
+        if call.constraints is not None or stop_sequences:
             raise UniGenHipError("mmu_generate: logit_bias / suppress_tokens / min_new_tokens / no_repeat_ngram_size / stop_sequences need "
                                  "the cached form (use_cache=True and a one-row mask); the recompute form does not apply them")
         if return_logprobs:
             raise UniGenHipError("mmu_generate: return_logprobs needs the cached form (use_cache=True and a one-row mask)")
-        if penalty != 1.0:
+        if call.penalty != 1.0:
             raise UniGenHipError("mmu_generate: repetition_penalty needs the cached form (use_cache=True and a one-row mask); the recompute "
                                  "form does not apply it")
         return self._mmu_generate_recompute(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token)
@@ -1361,36 +1448,17 @@ class UniGen(ModelMixin, ConfigMixin):
     def _pick_next(last, temperature, top_k):
         return UniGen._choose_next(UniGen._process_next(last, temperature, top_k), temperature)
 
-    @staticmethod
-    def _stop_list(stop):
-        """the stop ids of a call (None, an id, a list, or a 0-d / 1-D tensor of ids) as a list of ints"""
-        if stop is None:
-            return []
-        if torch.is_tensor(stop):
-            return [int(v) for v in stop.reshape(-1).tolist()]
-        if isinstance(stop, (list, tuple)):
-            return [int(v) for v in stop]
-        return [int(stop)]
+    _stop_list = staticmethod(stop_list)
 
-    @staticmethod
-    def _constraint_kwargs(cons):
-        """checked_constraints' dict back as the five keyword arguments (what the public entry points hand down)"""
-        if cons is None:
-            return {}
-        ninf = float("-inf")
-        return dict(logit_bias={e: b for e, b in cons["bias"] if b != ninf}, suppress_tokens=[e for e, b in cons["bias"] if b == ninf],
-                    min_new_tokens=cons["min_new"], no_repeat_ngram_size=cons["ngram"], stop_sequences=cons["stop_seqs"])
-
-    def _text_on_device(self, on_device, who, rows, cached, stop, max_new_tokens, constraints=None):
-        """Whether this call runs the on-device token loop.  An explicit bool wins over `self.text_decode_on_device`; the loop serves
-        what the AR path's fused step serves (up to 32 rows, hidden size >= 256 and a multiple of 32, cached path) with up to 8 stop
-        ids and constraints (checked_constraints' dict) within ops.TEXT_MAX_BIAS / TEXT_MAX_NGRAM / TEXT_MAX_STOP_SEQS /
-        TEXT_MAX_STOP_SEQ_LEN.  An explicit True on anything else raises with the reason; a default-derived True falls back to the host
-        loop."""
+    def _text_on_device(self, on_device, call, rows, cached, max_new_tokens):
+        """Whether this call (a TextCall) runs the on-device token loop.  An explicit bool wins over `self.text_decode_on_device`; the
+        loop serves what the AR path's fused step serves (up to 32 rows, hidden size >= 256 and a multiple of 32, cached path) with up
+        to 8 stop ids and constraints within ops.TEXT_MAX_BIAS / TEXT_MAX_NGRAM / TEXT_MAX_STOP_SEQS / TEXT_MAX_STOP_SEQ_LEN.  An
+        explicit True on anything else raises with the reason; a default-derived True falls back to the host loop."""
         if not (self.text_decode_on_device if on_device is None else bool(on_device)):
             return False
         H = self.llm.engine.dims.hidden_size
-        n_stop = len(self._stop_list(stop))          # (read only once the loop is wanted: a device tensor of ids costs a host sync)
+        n_stop = len(call.stop)
         why = None
         if not cached:
             why = "the recompute form (use_cache=False, or several rows / no mask in mmu_generate) has no on-device loop"
@@ -1402,8 +1470,8 @@ class UniGen(ModelMixin, ConfigMixin):
             why = f"{n_stop} stop ids (at most {ops.TEXT_MAX_STOP})"
         elif max_new_tokens < 1:
             why = f"max_new_tokens={max_new_tokens}"
-        elif constraints is not None:
-            c = constraints
+        elif call.constraints is not None:
+            c = call.constraints
             longest = max([len(q) for q in c["stop_seqs"]], default=0)
             if len(c["bias"]) > ops.TEXT_MAX_BIAS:
                 why = f"{len(c['bias'])} logit_bias + suppress_tokens entries (at most {ops.TEXT_MAX_BIAS})"
@@ -1417,91 +1485,61 @@ class UniGen(ModelMixin, ConfigMixin):
             return True
         if on_device is None:
             return False
-        raise UniGenHipError(f"{who}: on_device=True cannot serve this call: {why}")
+        raise UniGenHipError(f"{call.who}: on_device=True cannot serve this call: {why}")
 
-    def _decode_text_on_device(self, prompt, max_new_tokens, det, key_valid=None, mask_bits=None, sampling=None, stop=(), pad_token_id=None,
-                               generator=None, use_graph=True, trace=None, repetition_penalty=1.0, prompt_ids=None, return_logprobs=False,
-                               prefix=None, prompt_valid=None, logit_bias=None, suppress_tokens=None, min_new_tokens=None,
-                               no_repeat_ngram_size=None, stop_sequences=None):
-        """The token loop of `text_token_loop` + `emit_until_stop` with nothing but launches per token: prefill, token 0 eagerly from
-        the prefill's hidden state (GEMV head + pick), then unigen_hip/qwen2.py: decode_loop (step 1 eagerly, step 2 captured, replays
-        from there).  The pick launch applies the stop rule on the device; with stop ids the host reads `remaining` every 8 tokens and
-        stops replaying at zero.  The result is cut at `steps_used` (the step at which the last row finished), else at
-        max_new_tokens: rows that overshoot a poll interval emit pad ids / have their lengths set exactly as the host loop's rows,
-        so the cut result is the host loop's.  No decode step follows the last token.
-        The session (Qwen2Engine.text_step's buffers + the graph) is kept across calls like the AR path's: reused when rows, the KV
-        capacity (prompt + new tokens rounded up to 128), the token-buffer width (new tokens rounded up to 64), layer form, mode,
-        sampling constants, the repetition penalty (a kernel argument of the captured step), stop ids, pad id, presence of a
-        key-validity mask and the weight storage agree; `drop_decode_session()` and `train()` drop it, UNIGEN_AR_GRAPH_CACHE=0 turns
-        the reuse off.
-        repetition_penalty p != 1: the session's logits processor runs between head and pick of every step (ug_text_penalize); its
-        `seen` bitmap is zeroed here and takes prompt_ids [R, L] (None: no ids) at the positions key_valid marks real, one launch
-        outside the captured step.  p == 1 allocates and launches nothing.
-        return_logprobs: the session owns a log-probability buffer and its pick launches are the entry points that fill it (part of the
-        session key: such a call never replays the graph of a call without it, nor the reverse).
-        prefix (an MmuPrefix): `prompt` holds only the rows' tails [R, S, H]; the prompt is prefix + tail (L = P + S positions, which
-        is what key_valid [R, L] and prompt_ids [R, L] cover) and the prefill is the prefix's rows copied into the session's cache
-        plus Qwen2Engine.prefill_onto on the tails.  The session key needs nothing more: rows, capacity and the presence of
-        key_valid cover it, and the copy rewrites every prefix position of a reused session.
-        prompt_valid [R, L]: the positions of prompt_ids that count for the penalty (default: key_valid).
-        logit_bias / suppress_tokens / min_new_tokens / no_repeat_ngram_size / stop_sequences (include/unigen_hip.h: "Constraints of
-        the text loops"): the session owns the bias list, the n-gram block's prompt history (written in begin() from prompt_ids /
-        prompt_valid, outside the captured step) and the packed stop sequences; every step launches ug_text_constrain ahead of the
-        penalty and ug_text_stop_seq behind the pick.  The constraint constants are part of the session key: a call never replays a
-        graph captured with other constraints.  All off: nothing allocated, nothing launched, the key is what it was.
+    def _decode_text_on_device(self, call, prompt, max_new_tokens):
+        """The token loop of `text_token_loop` + `emit_until_stop` for a TextCall and a TextPrompt with nothing but launches per token:
+        prefill, token 0 eagerly from the prefill's hidden state (GEMV head + pick), then unigen_hip/qwen2.py: decode_loop (step 1
+        eagerly, step 2 captured, replays from there).  The pick launch applies the stop rule on the device; when a row can finish the
+        host reads `remaining` every 8 tokens and stops replaying at zero.  The result is cut at `steps_used` (the step at which the
+        last row finished), else at max_new_tokens: rows that overshoot a poll interval emit pad ids / have their lengths set exactly
+        as the host loop's rows, so the cut result is the host loop's.  No decode step follows the last token.
+        The session (TextDecodeSession: Qwen2Engine.text_step's buffers + the graph) is kept across calls like the AR path's and reused
+        when `key` below agrees -- every size and every constant of the call that is a kernel argument of the captured step or decides
+        which launches it holds; `drop_decode_session()` and `train()` drop it, UNIGEN_AR_GRAPH_CACHE=0 turns the reuse off.  What the
+        options launch: include/unigen_hip.h and TextDecodeSession.
         -> (tokens int64 [R, steps], lengths int64 [R], steps, log-probabilities fp32 [R, steps] or None)."""
         from unigen_hip.qwen2 import TextDecodeSession, decode_loop, put_session, take_session
         eng = self.llm.engine
         dev = eng.device
-        R, L, _ = prompt.shape
-        if prefix is not None:
-            L += prefix.P
-        prompt_valid = key_valid if prompt_valid is None else prompt_valid
+        R, L, key_valid, cons, det = prompt.rows, prompt.L, prompt.key_valid, call.constraints, call.deterministic
         n, V = int(max_new_tokens), self.config.vocab_size
-        cons, single_stops = checked_constraints("on-device text decode", lambda: V, logit_bias, suppress_tokens, min_new_tokens,
-                                                 no_repeat_ngram_size, stop_sequences)
-        stop = [int(s) for s in stop]
-        stop += [e for e in single_stops if e not in stop]
-        stops = bool(stop or (cons and cons["stop_seqs"]))
+        sampling = call.sampling
         if sampling is not None and sampling[1] >= V:
             sampling = (sampling[0], 0, sampling[2])
         if sampling is not None and not (sampling[0] > 0 and sampling[1] >= 0 and 0.0 < sampling[2] <= 1.0):
             raise UniGenHipError(f"on-device sampling needs temperature > 0, top_k >= 0 and 0 < top_p <= 1 (got {sampling})")
         cap, width = ops.round_up(L + n, 128), ops.round_up(n, 64)
-        pad = None if pad_token_id is None else int(pad_token_id)
-        penalty = float(repetition_penalty)
-        key = (R, cap, width, V, eng.decode_form(R, det), det, sampling, penalty, tuple(stop), pad, key_valid is None,
+        pad = None if call.pad_token_id is None or not call.stops else int(call.pad_token_id)
+        key = (R, cap, width, V, eng.decode_form(R, det), det, sampling, call.penalty, tuple(call.stop), pad, key_valid is None,
                str(dev)) + eng.storage_key(cap)
-        if return_logprobs:
+        if call.return_logprobs:
             key += ("logprobs",)
         if cons is not None:
             key += ("constraints", tuple(cons["bias"]), cons["min_new"], cons["ngram"], tuple(cons["stop_seqs"]))
-        sess = take_session(eng, "_text_session", key, use_graph)
+        sess = take_session(eng, "_text_session", key, call.use_graph)
         if sess is None:
-            sess = TextDecodeSession(eng, R, cap, width, V, deterministic=det, sampling=sampling, stop_ids=stop, pad_id=pad, key_valid=key_valid,
-                                     repetition_penalty=penalty, logprobs=bool(return_logprobs), constraints=cons)
+            sess = TextDecodeSession(eng, R, cap, width, V, deterministic=det, sampling=sampling, stop_ids=call.stop, pad_id=pad, key_valid=key_valid,
+                                     repetition_penalty=call.penalty, logprobs=call.return_logprobs, constraints=cons)
             sess.key = key
-            sess.begin(n, prompt_ids=prompt_ids, prompt_valid=prompt_valid)
+            sess.begin(n, prompt_ids=prompt.prompt_ids, prompt_valid=prompt.prompt_valid)
         else:
-            sess.begin(n, key_valid, L, prompt_ids=prompt_ids, prompt_valid=prompt_valid)
+            sess.begin(n, key_valid, L, prompt_ids=prompt.prompt_ids, prompt_valid=prompt.prompt_valid)
         if sampling is not None:
-            u_dev = dev if generator is None else generator.device
-            sess.uniforms[:n].copy_(torch.rand((n, R), device=u_dev, generator=generator))
-        if prefix is not None:
-            hn = self._prefill_after_prefix(sess.st, prefix, prompt, key_valid)
-        else:
-            hn = eng.prefill(sess.st, prompt, key_valid, mask_bits=mask_bits)
+            u_dev = dev if call.generator is None else call.generator.device
+            sess.uniforms[:n].copy_(torch.rand((n, R), device=u_dev, generator=call.generator))
+        hn = prompt.prefill(eng, sess.st)
         eng.check_errors()
-        eng.text_first_token(sess, hn, trace)
-        done = (lambda emitted: emitted % 8 == 0 and int(sess.state[1]) == 0) if stops else None   # (the one host read per 8 tokens)
-        if decode_loop(sess, lambda: eng.text_step(sess, trace), range(1, n), use_graph, stop=done):
+        eng.text_first_token(sess, hn, call.trace)
+        done = (lambda emitted: emitted % 8 == 0 and int(sess.state[1]) == 0) if call.stops else None   # (the one host read per 8 tokens)
+        if decode_loop(sess, lambda: eng.text_step(sess, call.trace), range(1, n), call.use_graph, stop=done):
             eng.text_graph_captures = getattr(eng, "text_graph_captures", 0) + 1
-        used = int(sess.state[2]) if stops else 0
+        used = int(sess.state[2]) if call.stops else 0
         steps = used if used > 0 else n
         eng.last_decode_graph = sess.graph is not None
         tokens, lengths = sess.out_tokens[:, :steps].long(), sess.lengths.long()       # (copies: the next call overwrites the session's)
-        logp = sess.logp[:, :steps].clone() if return_logprobs else None
-        put_session(eng, "_text_session", sess, use_graph)
+        logp = sess.logp[:, :steps].clone() if call.return_logprobs else None
+        put_session(eng, "_text_session", sess, call.use_graph)
         return tokens, lengths, steps, logp
 
     def _decode_text(self, st, hn, max_new_tokens, pick, emit):
@@ -1512,98 +1550,80 @@ class UniGen(ModelMixin, ConfigMixin):
                                embed=lambda ids: x.copy_(embed(ids)[:, 0]),
                                step=lambda x: eng.decode_step(st, x))            # (also advances the cache position)
 
-    def _mmu_decode(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det, on_device=False,
-                    use_graph=True, repetition_penalty=1.0, trace=None, return_logprobs=False, prefix=None, tail_valid=None,
-                    logit_bias=None, suppress_tokens=None, min_new_tokens=None, no_repeat_ngram_size=None, stop_sequences=None):
-        """Prefill R left-padded rows under their dense [R, 1, L, L] masks, then decode -> (tokens [R, max_new_tokens] on the device,
-        the rows' lengths cut after `eot_token` [R], the number of steps taken, and with return_logprobs the tokens' log-probabilities fp32
-        [R, max_new_tokens] (0.0 behind a row's `eot_token` and behind the last step taken), else None).  repetition_penalty: the prompt
-        ids are `idx` (when the prompt is not given as embeddings) at the keys the prompt's last row sees.
-        prefix (an MmuPrefix, already checked: check_mmu_prefix_call): idx / input_embeddings are the rows' tails [R, S], causal behind
-        the prefix and left-padded where tail_valid [R, S] is False; there is no dense mask.  The prompt is then prefix + tail: L = P + S
-        positions, key validity = the prefix's, then tail_valid; penalty ids = the prefix's ids (if it has any) and the tail ids (if given
-        as ids) at the valid positions.  logit_bias ... stop_sequences: the constraints of `generate`; the n-gram block's history is the
-        penalty's ids in order, a stop sequence of one id joins `eot_token`."""
+    def _run_text_host(self, call, prompt, max_new_tokens, lengths=False):
+        """The host token loop for a TextCall and a TextPrompt: prefill, then text_token_loop with text_pick_emit's pick / emit.
+        -> (tokens long [R, max_new_tokens]: zeros, or the call's pad id, behind the last step taken; with `lengths` the rows' lengths
+        cut after their stop [R], else None; the number of steps taken; the tokens' log-probabilities fp32 [R, max_new_tokens] (0.0
+        behind a row's stop and behind the last step taken) or None)."""
         from unigen_hip.qwen2 import DecodeState
-        from .sampling import history_of, seen_mask_of
         eng = self.llm.engine
-        cons, single_stops = checked_constraints("mmu decode", lambda: self.config.vocab_size, logit_bias, suppress_tokens, min_new_tokens,
-                                                 no_repeat_ngram_size, stop_sequences)
-        if single_stops:
-            eot_token = self._stop_list(eot_token) + [e for e in single_stops if e not in self._stop_list(eot_token)]
-        prompt = (self.llm.model.embed_tokens(idx) if input_embeddings is None else input_embeddings).float()
-        dev = prompt.device
-        R, L = prompt.shape[0], prompt.shape[1]
-        if prefix is None:
-            mb = eng.mask_bits(attention_mask, R, L)
+        dev, R = prompt.embeds.device, prompt.rows
+        st = DecodeState(eng.dims, R, prompt.L + max_new_tokens, dev, key_valid=prompt.key_valid, deterministic=call.deterministic)
+        hn = prompt.prefill(eng, st)
+        if prompt.mask_bits is None:               # (under a dense mask the flags were read where it was compressed: _dense_prompt)
             eng.check_errors()
-            key_valid = attention_mask[:, 0, -1, :] == 0
-            prompt_ids, prompt_valid = (idx if input_embeddings is None else None), key_valid
-        else:
-            mb, P, S = None, prefix.P, L
-            L = P + S
-            tv = torch.ones((R, S), dtype=torch.bool, device=dev) if tail_valid is None else tail_valid.to(dev)
-            key_valid = torch.cat([prefix.key_valid.to(dev).expand(R, P), tv], dim=1)
-            prompt_ids = prompt_valid = None
-            if prefix.ids is not None or input_embeddings is None:
-                nothing = torch.zeros((R, 1), dtype=torch.long, device=dev)
-                prompt_ids = torch.cat([(nothing if prefix.ids is None else prefix.ids.to(dev)).expand(R, P),
-                                        idx.to(dev).long() if input_embeddings is None else nothing.expand(R, S)], dim=1)
-                prompt_valid = key_valid.clone()
-                if prefix.ids is None:
-                    prompt_valid[:, :P] = False
-                if input_embeddings is not None:
-                    prompt_valid[:, P:] = False
-        if on_device:
-            sampling = (float(temperature), int(top_k or 0), 1.0) if temperature > 0 else None
-            tokens, lengths, steps, logp = self._decode_text_on_device(
-                prompt, max_new_tokens, det, key_valid=key_valid, mask_bits=mb, sampling=sampling, stop=self._stop_list(eot_token),
-                use_graph=use_graph, trace=trace, repetition_penalty=repetition_penalty,
-                prompt_ids=prompt_ids, return_logprobs=return_logprobs, prefix=prefix, prompt_valid=prompt_valid,
-                **self._constraint_kwargs(cons))
-            if steps < max_new_tokens:              # (the host loop's shapes: the buffer is max_new_tokens wide)
-                tokens = torch.cat([tokens, tokens.new_zeros((R, max_new_tokens - steps))], dim=1)
-                if return_logprobs:
-                    logp = torch.cat([logp, logp.new_zeros((R, max_new_tokens - steps))], dim=1)
-            return tokens, lengths, steps, logp
-        st = DecodeState(eng.dims, R, L + max_new_tokens, dev, key_valid=key_valid, deterministic=det)
-        if prefix is not None:
-            hn = self._prefill_after_prefix(st, prefix, prompt, key_valid)
-            eng.check_errors()
-        else:
-            hn = eng.prefill(st, prompt, mask_bits=mb)
-        tokens = torch.zeros((R, max_new_tokens), dtype=torch.long, device=dev)
-        lengths = torch.full((R,), max_new_tokens, dtype=torch.long, device=dev)
-        stop_ids = self._stop_list(eot_token) if cons is not None or isinstance(eot_token, (list, tuple)) else None
-        if stop_ids is not None:                    # (a list of ids, possibly empty: rows can still finish on a stop sequence)
-            eot_token = torch.tensor(stop_ids, dtype=torch.long, device=dev)
-        pick, emit = (lambda last: self._pick_next(last, temperature, top_k)), emit_until_stop(tokens, eot_token, lengths=lengths)
-        done = emit.done
-        logp = None
-        if return_logprobs:
-            logp = torch.zeros((R, max_new_tokens), dtype=torch.float32, device=dev)
-            pick, emit = with_logprobs(lambda last: self._process_next(last, temperature, top_k),
-                                       lambda scores: self._choose_next(scores, temperature), emit, logp)
-        if repetition_penalty != 1.0:
-            seen = seen_mask_of(prompt_ids, prompt_valid, R, self.config.vocab_size, dev)
-            pick, emit = with_repetition_penalty(pick, emit, repetition_penalty, seen)
-        if cons is not None:
-            hist = history_of(prompt_ids, prompt_valid, R, self.config.vocab_size)
-            pick, emit = with_constraints(pick, emit, cons, done, hist, stop_ids=stop_ids, lengths=lengths)
-        steps = self._decode_text(st, hn, max_new_tokens, pick, emit)
-        return tokens, lengths, steps, logp
+        tokens = torch.full((R, max_new_tokens), int(call.pad_token_id or 0), dtype=torch.long, device=dev)
+        lengths = torch.full((R,), max_new_tokens, dtype=torch.long, device=dev) if lengths else None
+        logp = torch.zeros((R, max_new_tokens), dtype=torch.float32, device=dev) if call.return_logprobs else None
+        pick, emit = text_pick_emit(call, tokens, self.config.vocab_size, logp, lengths, prompt.prompt_ids, prompt.prompt_valid)
+        return tokens, lengths, self._decode_text(st, hn, max_new_tokens, pick, emit), logp
 
-    @torch.no_grad()
-    def _mmu_generate_cached(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det=False,
-                             on_device=False, use_graph=True, repetition_penalty=1.0, return_logprobs=False, trace=None, **constraints):
-        """The one-row case of the batch path -> list of 0-d device tensors (one row: it ends at its `eot_token`, so every step counts);
-        return_logprobs: (that list, the tokens' log-probabilities fp32 [steps])."""
-        L = attention_mask.shape[-1]
-        tokens, _, steps, logp = self._mmu_decode(idx, input_embeddings, attention_mask.reshape(1, 1, L, L), max_new_tokens, temperature, top_k,
-                                                  eot_token, det, on_device=on_device, use_graph=use_graph,
-                                                  repetition_penalty=repetition_penalty, trace=trace, return_logprobs=return_logprobs,
-                                                  **constraints)
-        return (list(tokens[0, :steps]), logp[0, :steps].clone()) if return_logprobs else list(tokens[0, :steps])
+    def _generate_prompt(self, input_ids, input_embeddings, attention_mask):
+        """`generate`'s prompt: ids [R, L] or embeddings [R, L, H] under a 2-D [R, L] key-validity mask (None: all real)"""
+        dev = self.llm.engine.device
+        embeds = (self.llm.model.embed_tokens(input_ids.to(dev)) if input_embeddings is None else input_embeddings.to(dev)).float()
+        key_valid = None
+        if attention_mask is not None:
+            if attention_mask.dim() != 2:
+                raise UniGenHipError("generate expects a 2-D [rows, L] attention mask (1 = real token)")
+            key_valid = attention_mask.to(dev) != 0
+        return TextPrompt(embeds, int(embeds.shape[1]), key_valid, None, None if input_embeddings is not None else input_ids.to(dev), key_valid)
+
+    def _dense_prompt(self, idx, input_embeddings, attention_mask):
+        """the mmu entry points' prompt without a prefix: R left-padded rows under their dense additive [R, 1, L, L] masks; the keys
+        every later position sees, and the ids that count, are those of the mask's last row"""
+        eng = self.llm.engine
+        embeds = (self.llm.model.embed_tokens(idx) if input_embeddings is None else input_embeddings).float()
+        R, L = int(embeds.shape[0]), int(embeds.shape[1])
+        mb = eng.mask_bits(attention_mask, R, L)
+        eng.check_errors()
+        key_valid = attention_mask[:, 0, -1, :] == 0
+        return TextPrompt(embeds, L, key_valid, mb, idx if input_embeddings is None else None, key_valid)
+
+    def _prefix_prompt(self, prefix, idx, input_embeddings, tail_valid):
+        """the mmu entry points' prompt behind a prefix (already checked: check_mmu_prefix_call): the rows' tails [R, S], causal and
+        left-padded where tail_valid [R, S] is False.  Key validity = the prefix's, then tail_valid; the ids that count = the prefix's
+        (if it has any) and the tails' (if given as ids), zero-filled and marked invalid where one side came as embeddings."""
+        embeds = (self.llm.model.embed_tokens(idx) if input_embeddings is None else input_embeddings).float()
+        dev = embeds.device
+        R, S, P = int(embeds.shape[0]), int(embeds.shape[1]), prefix.P
+        tv = torch.ones((R, S), dtype=torch.bool, device=dev) if tail_valid is None else tail_valid.to(dev)
+        key_valid = torch.cat([prefix.key_valid.to(dev).expand(R, P), tv], dim=1)
+        prompt_ids = prompt_valid = None
+        if prefix.ids is not None or input_embeddings is None:
+            nothing = torch.zeros((R, 1), dtype=torch.long, device=dev)
+            prompt_ids = torch.cat([(nothing if prefix.ids is None else prefix.ids.to(dev)).expand(R, P),
+                                    idx.to(dev).long() if input_embeddings is None else nothing.expand(R, S)], dim=1)
+            prompt_valid = key_valid.clone()
+            if prefix.ids is None:
+                prompt_valid[:, :P] = False
+            if input_embeddings is not None:
+                prompt_valid[:, P:] = False
+        return TextPrompt(embeds, P + S, key_valid, None, prompt_ids, prompt_valid, prefix)
+
+    def _mmu_decode(self, call, idx, input_embeddings, attention_mask, max_new_tokens, on_device, prefix=None, tail_valid=None):
+        """The cached form of the mmu entry points: the prompt (behind `prefix`, or under its dense masks), then one of the two loops
+        -> _run_text_host's tuple; the on-device loop's result is padded to the same max_new_tokens width."""
+        prompt = self._dense_prompt(idx, input_embeddings, attention_mask) if prefix is None \
+            else self._prefix_prompt(prefix, idx, input_embeddings, tail_valid)
+        if not on_device:
+            return self._run_text_host(call, prompt, max_new_tokens, lengths=True)
+        tokens, lengths, steps, logp = self._decode_text_on_device(call, prompt, max_new_tokens)
+        if steps < max_new_tokens:
+            tokens = torch.cat([tokens, tokens.new_zeros((prompt.rows, max_new_tokens - steps))], dim=1)
+            if logp is not None:
+                logp = torch.cat([logp, logp.new_zeros((prompt.rows, max_new_tokens - steps))], dim=1)
+        return tokens, lengths, steps, logp
 
     @torch.no_grad()
     def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=0.0,
@@ -1632,31 +1652,26 @@ class UniGen(ModelMixin, ConfigMixin):
         The call copies the prefix's keys / values into its own state and leaves the object unchanged.  Wrong arguments (a prefix of
         another model or device, more than 32 rows, a tail position that is a pad in every row) raise UniGenHipError before any
         launch."""
-        from unigen_hip.qwen2 import resolve_deterministic
         if prefix is not None:
             R, _, tail_valid = check_mmu_prefix_call("mmu_generate_batch", self.llm.engine, prefix, idx, input_embeddings, attention_mask,
                                                      tail_valid)
         elif tail_valid is not None:
             raise UniGenHipError("mmu_generate_batch: tail_valid belongs to a call with a prefix")
-        penalty = checked_repetition_penalty(repetition_penalty, "mmu_generate_batch")
-        cons, single_stops = checked_constraints("mmu_generate_batch", lambda: self.config.vocab_size, logit_bias, suppress_tokens,
-                                                 min_new_tokens, no_repeat_ngram_size, stop_sequences)
-        if single_stops:
-            eot_token = self._stop_list(eot_token) + [e for e in single_stops if e not in self._stop_list(eot_token)]
-        det = resolve_deterministic(deterministic)
-        self.llm.engine.last_decode_deterministic = det
+        call = mmu_call("mmu_generate_batch", lambda: self.config.vocab_size, temperature, top_k, eot_token, repetition_penalty=repetition_penalty,
+                        deterministic=deterministic, return_logprobs=return_logprobs, use_graph=use_graph, trace=trace, logit_bias=logit_bias,
+                        suppress_tokens=suppress_tokens, min_new_tokens=min_new_tokens, no_repeat_ngram_size=no_repeat_ngram_size,
+                        stop_sequences=stop_sequences)
+        eng = self.llm.engine
+        eng.last_decode_deterministic = call.deterministic
         if prefix is None:
             R, L = (idx if input_embeddings is None else input_embeddings).shape[:2]
             if R > 32:
                 raise ValueError("mmu_generate_batch: at most 32 rows per call")
             if attention_mask is None or tuple(attention_mask.shape) != (R, 1, L, L):
                 raise ValueError("mmu_generate_batch: attention_mask must be the rows' dense [R, 1, L, L] additive masks")
-        dev_loop = self._text_on_device(on_device, "mmu_generate_batch", R, True, eot_token, max_new_tokens, constraints=cons)
-        self.llm.engine.last_text_decode_on_device = dev_loop
-        tokens, lengths, _, logp = self._mmu_decode(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, det,
-                                                    on_device=dev_loop, use_graph=use_graph, repetition_penalty=penalty, trace=trace,
-                                                    return_logprobs=bool(return_logprobs), prefix=prefix, tail_valid=tail_valid,
-                                                    **self._constraint_kwargs(cons))
+        eng.last_text_decode_on_device = self._text_on_device(on_device, call, R, True, max_new_tokens)
+        tokens, lengths, _, logp = self._mmu_decode(call, idx, input_embeddings, attention_mask, max_new_tokens, eng.last_text_decode_on_device,
+                                                    prefix, tail_valid)
         tokens, lengths = tokens.cpu(), lengths.cpu()
         lists = [list(tokens[r, :int(lengths[r])]) for r in range(R)]
         if return_logprobs:

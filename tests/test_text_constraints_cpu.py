@@ -160,23 +160,46 @@ def _simulate(script, prompt, valid, cons, eos, pad, penalty):
     return toks, lps, lengths, procs
 
 
-def test_host_token_loop_with_every_wrapper_on_a_scripted_head():
+def _stack_by_hand(V, out, logp, lengths, prompt, valid, process, choose):
+    """the wrapper stack composed here, layer by layer -> (pick, emit, emit_until_stop's done)"""
     from models.sampling import history_of, seen_mask_of
-    from models.unigen import (checked_constraints, emit_until_stop, text_token_loop, with_constraints, with_logprobs,
-                               with_repetition_penalty)
-    script, prompt, valid = _script()
-    n, R, V = script.shape
+    from models.unigen import checked_constraints, emit_until_stop, with_constraints, with_logprobs, with_repetition_penalty
+    R = out.shape[0]
     cons, singles = checked_constraints("test", lambda: V, **CONS)
     assert singles == [] and cons["stop_seqs"] == SEQS and cons["bias"] == [(3, 2.0), (5, NINF), (7, -1.5)]
+    emit = emit_until_stop(out, torch.tensor([EOS]), PAD, lengths=lengths)
+    done = emit.done
+    pick, emit = with_logprobs(process, choose, emit, logp)
+    pick, emit = with_repetition_penalty(pick, emit, P, seen_mask_of(prompt, valid, R, V, CPU))
+    pick, emit = with_constraints(pick, emit, cons, done, history_of(prompt, valid, R, V), stop_ids=[EOS], lengths=lengths)
+    return pick, emit, done
+
+
+def _stack_of_the_call(V, out, logp, lengths, prompt, valid, process, choose):
+    """the stack the entry points run: text_pick_emit's, from the TextCall of the same arguments (done: read off the lengths)"""
+    from models.unigen import text_call, text_pick_emit
+    call = text_call("test", lambda: V, None, (process, choose), EOS, pad_finished=True, pad_token_id=PAD, repetition_penalty=P,
+                     return_logprobs=True, **CONS)
+    assert call.stop == [EOS] and call.constraints["stop_seqs"] == SEQS and call.constraints["bias"] == [(3, 2.0), (5, NINF), (7, -1.5)]
+    pick, emit = text_pick_emit(call, out, V, logp, lengths, prompt, valid)
+    return pick, emit, None
+
+
+def test_host_token_loop_with_every_wrapper_on_a_scripted_head():
+    for stack in (_stack_by_hand, _stack_of_the_call):           # the same expectations of both
+        _scripted_head_run(stack)
+
+
+def _scripted_head_run(stack):
+    from models.unigen import text_token_loop
+    script, prompt, valid = _script()
+    n, R, V = script.shape
     out = torch.full((R, n), PAD, dtype=torch.long)
     lengths = torch.full((R,), n, dtype=torch.long)
     logp = torch.zeros((R, n))
-    emit = emit_until_stop(out, torch.tensor([EOS]), PAD, lengths=lengths)
-    done = emit.done
     seen_scores = []
-    pick, emit = with_logprobs(lambda last: (seen_scores.append(last.clone()), last)[1], lambda s: s.argmax(-1, keepdim=True), emit, logp)
-    pick, emit = with_repetition_penalty(pick, emit, P, seen_mask_of(prompt, valid, R, V, CPU))
-    pick, emit = with_constraints(pick, emit, cons, done, history_of(prompt, valid, R, V), stop_ids=[EOS], lengths=lengths)
+    pick, emit, done = stack(V, out, logp, lengths, prompt, valid, lambda last: (seen_scores.append(last.clone()), last)[1],
+                             lambda s: s.argmax(-1, keepdim=True))
     counter = iter(range(n))
     steps = text_token_loop(n, None, pick, emit, head=lambda hn: script[next(counter)].clone(), embed=lambda ids: None, step=lambda x: None)
     toks, lps, want_len, procs = _simulate(script, prompt, valid, CONS, [EOS], PAD, P)
@@ -186,7 +209,7 @@ def test_host_token_loop_with_every_wrapper_on_a_scripted_head():
     # a sequence that is complete only through the prompt does not fire: row 0 emits 22 behind its prompt's 20 21 and goes on
     assert toks[0][0] == 22 and toks[1][0] != PAD and want_len[0] == 7 and toks[6][0] == EOS
     # both sequences complete at row 1's step 2: the row finishes once, there, and is pad from then on
-    assert [t[1] for t in toks[:4]] == [20, 21, 22, PAD] and bool(done.all())
+    assert [t[1] for t in toks[:4]] == [20, 21, 22, PAD] and bool((lengths < n).all() if done is None else done.all())
     # min_new_tokens holds row 2's EOS back at step 1; suppress_tokens takes row 0's target 5 at step 1; the bias lifts 3 at step 3
     assert toks[1][2] == 11 and toks[1][0] == 25 and toks[3][0] == 3
     # the log-probabilities are those of the constrained and penalised scores, 0.0 for a finished row
@@ -240,7 +263,7 @@ def test_generate_needs_an_eos_or_a_pad_for_stop_sequences():
 
 
 def test_on_device_limits_raise_when_explicit_and_fall_back_when_derived():
-    from models.unigen import UniGen, checked_constraints
+    from models.unigen import UniGen, text_call
     from unigen_hip import ops
     from unigen_hip.lib import UniGenHipError
     assert (ops.TEXT_MAX_BIAS, ops.TEXT_MAX_NGRAM, ops.TEXT_MAX_STOP_SEQS, ops.TEXT_MAX_STOP_SEQ_LEN) == (1024, 16, 8, 16)
@@ -251,14 +274,13 @@ def test_on_device_limits_raise_when_explicit_and_fall_back_when_derived():
              (dict(stop_sequences=[list(range(17))]), "17 ids"),
              (dict(stop_sequences=[[e] for e in range(5)]), "9 stop ids")]      # with the four ids below: singles count as stop ids
     for kw, word in cases:
-        cons, singles = checked_constraints("t", lambda: V, **kw)
-        stop = [4000, 4001, 4002, 4003] + singles
+        call = text_call("generate", lambda: V, None, (None, None), [4000, 4001, 4002, 4003], **kw)
         with pytest.raises(UniGenHipError, match=word):
-            UniGen._text_on_device(_fake_model(V), True, "generate", 3, True, stop, 8, constraints=cons)
-        assert UniGen._text_on_device(_fake_model(V, default=True), None, "generate", 3, True, stop, 8, constraints=cons) is False
-    ok, _ = checked_constraints("t", lambda: V, logit_bias={e: 0.5 for e in range(1024)}, no_repeat_ngram_size=16,
-                                stop_sequences=[list(range(e, e + 16)) for e in range(8)])
-    assert UniGen._text_on_device(_fake_model(V), True, "generate", 3, True, [1], 8, constraints=ok) is True
+            UniGen._text_on_device(_fake_model(V), True, call, 3, True, 8)
+        assert UniGen._text_on_device(_fake_model(V, default=True), None, call, 3, True, 8) is False
+    ok = text_call("generate", lambda: V, None, (None, None), [1], logit_bias={e: 0.5 for e in range(1024)}, no_repeat_ngram_size=16,
+                   stop_sequences=[list(range(e, e + 16)) for e in range(8)])
+    assert UniGen._text_on_device(_fake_model(V), True, ok, 3, True, 8) is True
 
 
 # ------------------------------------------------------------------ the C entries

@@ -9,7 +9,11 @@ def _fake(hidden=1536, default=False):
     from models.unigen import UniGen
     eng = types.SimpleNamespace(dims=types.SimpleNamespace(hidden_size=hidden))
     fake = types.SimpleNamespace(text_decode_on_device=default, llm=types.SimpleNamespace(engine=eng), _stop_list=UniGen._stop_list)
-    return lambda *a: UniGen._text_on_device(fake, *a)
+
+    def on_device(flag, who, rows, cached, stop, new):          # (the switch reads the stop ids off the call's record)
+        from models.unigen import text_call
+        return UniGen._text_on_device(fake, flag, text_call(who, lambda: 1000, None, (None, None), stop), rows, cached, new)
+    return on_device
 
 
 def test_stop_list_normalises_every_form_the_callers_pass():
