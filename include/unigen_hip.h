@@ -261,6 +261,8 @@ int ug_attn_decode_fused(const float* acc_qkv, int64_t ldacc, const float* ss_in
  * + eps))).  The norm-fed entry points also sit behind a split-K producer of the form above: with `pend` (raw fp32 accumulator
  * [R][ld_pend]) the residual stream is h + float(bf16(pend)), written to x_out (a buffer other than h, or NULL) by the launch's first
  * eight workgroups; the accumulator is left as it is (a later launch clears it).
+ * `h` carries no leading dimension: it is CONTIGUOUS -- [R][N] for ug_decode_sw_resid (its rows are N floats apart), [R][H] = [R][K] for
+ * ug_decode_sw_gate_up and ug_decode_sw_head (rows K = 1536 floats apart), and so is x_out.  The entry points cannot check this.
  * R <= 16; ug_decode_sw_supported() says whether a model's sizes fit this build (hidden 1536 = six 256-wide k-slabs, head_dim 128). */
 int ug_decode_sw_supported(int64_t hidden, int64_t inter, int64_t q_dim, int head_dim);
 /* The down projection's form (its 287 KB operand rules a whole-K workgroup out): split-K in k-blocks of seven 256-wide slabs -- a

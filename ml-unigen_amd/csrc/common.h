@@ -33,6 +33,19 @@ void ug_set_error(const char* fmt, ...);
     }                                                                             \
   } while (0)
 
+// For a dispatch function that names one kernel instantiation per case: `return ug_launch(name, kern<...>, grid, block, st, args...)`
+// launches (arguments converted to the kernel's parameter types) and checks; a plan that no case names ends in ug_no_kernel.
+template <class... P, class... A>
+int ug_launch(const char* name, void (*kern)(P...), dim3 grid, dim3 block, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(kern, grid, block, 0, st, static_cast<P>(args)...);
+  UG_CHECK_LAUNCH(name);
+  return UG_OK;
+}
+inline int ug_no_kernel(const char* name) {
+  ug_set_error("%s: the launch plan names no kernel", name);
+  return UG_ERR_STATE;
+}
+
 #define UG_HIP(call)                                                              \
   do {                                                                            \
     hipError_t e__ = (call);                                                      \

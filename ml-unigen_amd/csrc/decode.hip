@@ -3,6 +3,7 @@
 // generation, position / length read from DEVICE memory so one captured hipGraph replays all 256 steps.
 //   cache layout: K,V [rows][HKV][Tmax][128] bf16 (keys of one (row, kv-head) contiguous)
 #include "common.h"
+#include "decode_plan.h"
 #include "unigen_hip.h"
 #include "vmem_asm.h"
 #include <stdlib.h>
@@ -422,7 +423,10 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
                                                    const bf16_t* __restrict__ W, int64_t ldw, float* __restrict__ acc,
                                                    int64_t sr, int64_t sn, int N, int K) {
   __shared__ float red[3][64][4 * RB];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  // wave: through readfirstlane, so that `kbase + u * 32 < K` below is a scalar branch.  As a per-lane condition the compiler put the
+  // second MFMA of gemv_kernel<1, 2> into an EXEC-masked region without a skip; an MFMA does not honour EXEC, and the waves past K
+  // added a product of stale registers (K = 96: tests/test_gemv_exact_gpu.py, (2, 16369, 96)).
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), g = lane >> 4;
   const int n0 = blockIdx.x * 16;
   const int nrow = min(n0 + (lane & 15), N - 1);
   const int kbase = (blockIdx.y * 4 + wave) * (32 * U);
@@ -1055,81 +1059,122 @@ __global__ __launch_bounds__(64) void finish_resid_norm_ord_kernel(const float* 
   if (pos_inc && blockIdx.x == 0 && threadIdx.x == 0) { ++*pos_inc; ++*len_inc; }
 }
 
-template <int RB>
-void launch_gemv(int U, dim3 grid, hipStream_t st, const bf16_t* x, int64_t ldx, int R, const bf16_t* W, int64_t ldw,
-                 float* acc, int64_t sr, int64_t sn, int N, int K) {
-  const dim3 block(256);
-  switch (U) {
-    case 8: hipLaunchKernelGGL((gemv_kernel<RB, 8>), grid, block, 0, st, x, ldx, R, W, ldw, acc, sr, sn, N, K); break;
-    case 4: hipLaunchKernelGGL((gemv_kernel<RB, 4>), grid, block, 0, st, x, ldx, R, W, ldw, acc, sr, sn, N, K); break;
-    case 2: hipLaunchKernelGGL((gemv_kernel<RB, 2>), grid, block, 0, st, x, ldx, R, W, ldw, acc, sr, sn, N, K); break;
-    default: hipLaunchKernelGGL((gemv_kernel<RB, 1>), grid, block, 0, st, x, ldx, R, W, ldw, acc, sr, sn, N, K); break;
+// ---- host side: the entry points check their arguments, decode_plan.h says what to launch, and one dispatch function per kernel
+// family names each instantiation once (ug_launch, common.h).  A plan that no case names is an error, never another kernel.
+using ug_plan::RingPlan;
+static_assert(XIN_BF16 == ug_plan::DEC_XIN_BF16, "plan_ring4 tells the one-wave ring form by this value");
+dim3 to_dim3(const ug_plan::Grid3& g) { return dim3(g.x, g.y, g.z); }
+
+// gemv_kernel<RB, U>
+int launch_gemv(const char* name, const ug_plan::GemvPlan& pl, hipStream_t st, const bf16_t* x, int64_t ldx, int R, const bf16_t* W, int64_t ldw,
+                float* acc, int64_t sr, int64_t sn, int N, int K) {
+  auto go = [&](auto kern) { return ug_launch(name, kern, to_dim3(pl.grid), dim3(pl.block), st, x, ldx, R, W, ldw, acc, sr, sn, N, K); };
+  switch (pl.RB * 16 + pl.U) {
+    case 16 + 8: return go(gemv_kernel<1, 8>);
+    case 16 + 4: return go(gemv_kernel<1, 4>);
+    case 16 + 2: return go(gemv_kernel<1, 2>);
+    case 16 + 1: return go(gemv_kernel<1, 1>);
+    case 32 + 8: return go(gemv_kernel<2, 8>);
+    case 32 + 4: return go(gemv_kernel<2, 4>);
+    case 32 + 2: return go(gemv_kernel<2, 2>);
+    case 32 + 1: return go(gemv_kernel<2, 1>);
   }
+  return ug_no_kernel(name);
 }
 
-// every workgroup's share of the clears a launch carries (float4 units; the kernels only multiply)
-void set_clear_shares(DecodeIn& f, float* zero0, int64_t n0, float* zero1, int64_t n1, float* ss_zero, unsigned nblocks) {
-  f.zero0 = zero0; f.zero1 = zero1; f.ss_zero = ss_zero;
-  f.n0_4 = (int)(n0 >> 2); f.n1_4 = (int)(n1 >> 2);
-  f.per0 = (int)((f.n0_4 + nblocks - 1) / nblocks); f.per1 = (int)((f.n1_4 + nblocks - 1) / nblocks);
+// gemv_ring_kernel<RB, KW, ORD>: the one-wave ring over a finished bf16 operand; ORD = the ordered form (one slot per k-slab)
+int launch_ring1(const char* name, int RB, int KW, bool ord, dim3 grid, hipStream_t st, const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw,
+                 float* acc, int sr, int sn, int N, int K, const DecodeIn& f) {
+  auto go = [&](auto kern) { return ug_launch(name, kern, grid, dim3(64), st, x, ldx, R, W, ldw, acc, sr, sn, N, K, f); };
+  switch ((RB * 4 + KW) * 2 + (ord ? 1 : 0)) {
+    case (4 + 1) * 2: return go(gemv_ring_kernel<1, 1>);
+    case (4 + 2) * 2: return go(gemv_ring_kernel<1, 2>);
+    case (8 + 1) * 2: return go(gemv_ring_kernel<2, 1>);
+    case (8 + 2) * 2: return go(gemv_ring_kernel<2, 2>);
+    case (4 + 1) * 2 + 1: return go(gemv_ring_kernel<1, 1, true>);
+    case (8 + 1) * 2 + 1: return go(gemv_ring_kernel<2, 1, true>);
+  }
+  return ug_no_kernel(name);
 }
 
-// measured on MI355X (tools/gemv_bench.py): two row groups per wave once there are >= 3000 tiles, else one
+// gemv_ring4_kernel<RB, KW, XIN, NW, CLR, NPEND>.  npend < 0: the accumulator forms of the plan; 0 | 5: the ordered form of
+// ug_decode_gemv_resid_norm_ord.  (p0, p1, nw, ld1: the kernel's leading arguments, see there.)  <., 2, ., 4, .> is not here: no shape
+// selects it (decode_plan.h, DEC_RING_CANDS).
 template <int XIN>
-void launch_ring_auto(hipStream_t st, const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, float* acc, int sr, int sn, int N,
-                      int K, DecodeIn f, float* zero0 = nullptr, int64_t n0 = 0, float* zero1 = nullptr, int64_t n1 = 0,
-                      float* ss_zero = nullptr) {
-  const int64_t groups = (N + 15) / 16;
-  const int nslabs = (K + 255) / 256;
-  const int KW = groups * nslabs >= 3000 ? 2 : 1;
+int launch_ring4(const char* name, const RingPlan& pl, int npend, hipStream_t st, const float* p0, const float* p1, const float* nw,
+                 const bf16_t* W, int R, int K, int ld1, int ldw, int N, float* acc, int sr, int sn, const DecodeIn& f) {
+  auto go = [&](auto kern) {
+    return ug_launch(name, kern, to_dim3(pl.grid), dim3(pl.block), st, p0, p1, nw, W, R, K, ld1, ldw, N, (int)ug_plan::dec_slabs(K), acc, sr, sn, f);
+  };
+  auto go2 = [&](auto with_clears, auto without) { return go(pl.CLR ? with_clears : without); };
+  if constexpr (XIN == XIN_RESID_NORM) {
+    if (npend == 0) return go(gemv_ring4_kernel<1, 1, XIN_RESID_NORM, 4, false, 0>);
+    if (npend == ug_plan::DEC_ORD_DOWN_KBLOCKS) return go(gemv_ring4_kernel<1, 1, XIN_RESID_NORM, 4, false, 5>);
+  }
+  if (npend >= 0) return ug_no_kernel(name);
+  switch ((pl.RB * 4 + pl.KW) * 16 + pl.NW) {
+    case (4 + 3) * 16 + 9: return go2(gemv_ring4_kernel<1, 3, XIN, 9, true>, gemv_ring4_kernel<1, 3, XIN, 9, false>);
+    case (4 + 2) * 16 + 8: return go2(gemv_ring4_kernel<1, 2, XIN, 8, true>, gemv_ring4_kernel<1, 2, XIN, 8, false>);
+    case (4 + 2) * 16 + 7: return go2(gemv_ring4_kernel<1, 2, XIN, 7, true>, gemv_ring4_kernel<1, 2, XIN, 7, false>);
+    case (4 + 1) * 16 + 4: return go2(gemv_ring4_kernel<1, 1, XIN, 4, true>, gemv_ring4_kernel<1, 1, XIN, 4, false>);
+    case (8 + 1) * 16 + 4: return go2(gemv_ring4_kernel<2, 1, XIN, 4, true>, gemv_ring4_kernel<2, 1, XIN, 4, false>);
+  }
+  return ug_no_kernel(name);
+}
+
+// the three ug_decode_gemv* entries and the ring form of ug_gemv_bf16: plan, every workgroup's share of the clears, launch
+template <int XIN>
+int launch_ring_auto(const char* name, hipStream_t st, const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, float* acc, int sr, int sn,
+                     int N, int K, DecodeIn f, float* zero0 = nullptr, int64_t n0 = 0, float* zero1 = nullptr, int64_t n1 = 0,
+                     float* ss_zero = nullptr) {
+  const RingPlan pl = ug_plan::plan_ring4(XIN, R, N, K, zero0 || zero1 || ss_zero);
+  const ug_plan::ClearShares c = ug_plan::clear_shares(n0, n1, pl.nblocks());
+  f.zero0 = zero0; f.zero1 = zero1; f.ss_zero = ss_zero;
+  f.n0_4 = c.n0_4; f.per0 = c.per0; f.n1_4 = c.n1_4; f.per1 = c.per1;
   if constexpr (XIN == XIN_BF16) {
-    const dim3 grid((unsigned)nslabs, (unsigned)((groups + KW - 1) / KW));
-    set_clear_shares(f, zero0, n0, zero1, n1, ss_zero, grid.x * grid.y);
-#define UG_RING1(RBV, KWV) hipLaunchKernelGGL((gemv_ring_kernel<RBV, KWV>), grid, dim3(64), 0, st, x, ldx, R, W, ldw, acc, sr, sn, N, K, f)
-    if (R <= 16) { if (KW == 2) UG_RING1(1, 2); else UG_RING1(1, 1); }
-    else { if (KW == 2) UG_RING1(2, 2); else UG_RING1(2, 1); }
-#undef UG_RING1
+    return launch_ring1(name, pl.RB, pl.KW, false, to_dim3(pl.grid), st, x, ldx, R, W, ldw, acc, sr, sn, N, K, f);
   } else {
-    // workgroup shape (waves, tiles per wave) by the tile count the busiest CU ends up with: one 9-wave x 3-tile workgroup
-    // per CU for gate_up (27 tile slots for 26.25 tiles per CU), 7 x 2 for down (14 for 13.1), 4 x 1|2 otherwise
-    struct Cand { int nw, kw; };
-    const Cand cands[4] = {{4, 1}, {4, 2}, {7, 2}, {9, 3}};
-    int best = 0;
-    int64_t best_cost = INT64_MAX;
-    for (int c = 0; c < 4; ++c) {
-      if (R > 16 && cands[c].nw != 4) continue;                    // two row blocks: the operand image needs the LDS
-      const int64_t blocks = ((groups + cands[c].nw * cands[c].kw - 1) / (cands[c].nw * cands[c].kw)) * nslabs;
-      const int64_t cost = ((blocks + 255) / 256) * cands[c].nw * cands[c].kw;
-      if (cost < best_cost) { best_cost = cost; best = c; }
-    }
-    int NWc = cands[best].nw, KWc = cands[best].kw, xcd_chunks = 0;
-    // many k-slabs (down projection: 35): the workgroups of a slab on one XCD -- 8 waves x 2 tiles, chunks x ceil(slabs / 8)
-    // workgroups per XCD must fit its 32 CUs
-    if (R <= 16 && nslabs >= 16) {
-      const int64_t chunks8 = (groups + 15) / 16;
-      if (chunks8 * ((nslabs + 7) / 8) <= 32) { NWc = 8; KWc = 2; xcd_chunks = (int)chunks8; }
-    }
-    // (dealing the nslabs % 8 left-over slabs' workgroups over all XCDs for equal bytes per XCD measured no better: 10.50 vs 10.33 us)
-    const dim3 grid = xcd_chunks ? dim3(8, (unsigned)xcd_chunks, (unsigned)((nslabs + 7) / 8))
-                                 : dim3((unsigned)nslabs, (unsigned)((groups + NWc * KWc - 1) / (NWc * KWc)));
-    set_clear_shares(f, zero0, n0, zero1, n1, ss_zero, grid.x * grid.y * grid.z);
     // leading arguments: see the kernel
     const float* p0 = XIN == XIN_RESID_NORM ? f.x_in : f.gu;
     const float* p1 = XIN == XIN_RESID_NORM ? f.pend : f.ss_in;
     const int64_t ld1 = XIN == XIN_RESID_NORM ? f.ld_pend : f.ld_gu;          // (< 2^24: checked by the entry points)
-    const bool clr = zero0 || zero1 || ss_zero;
-#define UG_RING4(RBV, KWV, NWV)                                                                                                              \
-  do {                                                                                                                                       \
-    if (clr) hipLaunchKernelGGL((gemv_ring4_kernel<RBV, KWV, XIN, NWV, true>), grid, dim3(64 * NWV), 0, st, p0, p1, f.norm_w, W, R, K, (int)ld1, ldw, \
-                                N, nslabs, acc, sr, sn, f);                                                                                  \
-    else hipLaunchKernelGGL((gemv_ring4_kernel<RBV, KWV, XIN, NWV, false>), grid, dim3(64 * NWV), 0, st, p0, p1, f.norm_w, W, R, K, (int)ld1, ldw, \
-                            N, nslabs, acc, sr, sn, f);                                                                                      \
-  } while (0)
-    if (R <= 16) {
-      if (NWc == 9) UG_RING4(1, 3, 9); else if (NWc == 8) UG_RING4(1, 2, 8); else if (NWc == 7) UG_RING4(1, 2, 7); else if (KWc == 2) UG_RING4(1, 2, 4); else UG_RING4(1, 1, 4);
-    } else { if (KWc == 2) UG_RING4(2, 2, 4); else UG_RING4(2, 1, 4); }
-#undef UG_RING4
+    return launch_ring4<XIN>(name, pl, -1, st, p0, p1, f.norm_w, W, R, K, (int)ld1, ldw, N, acc, sr, sn, f);
   }
+}
+
+// attn_decode_fused_kernel<NQP>: nparts == 0 reads the raw accumulator, nparts == 6 that many k-slab slots in ascending order
+int launch_attn_decode_fused(const char* name, int64_t nparts, const float* qkv, int64_t ld, const float* ss, float eps, int64_t norm_cols,
+                             const void* bias, const float* cos_tab, const float* sin_tab, const int* pos_dev, void* cache_k, void* cache_v,
+                             const uint8_t* key_valid, void* o, int64_t ldo, int64_t rows, int H, int HKV, int64_t Tmax, int64_t max_pos,
+                             float scale, hipStream_t st) {
+  auto go = [&](auto kern) {
+    return ug_launch(name, kern, to_dim3(ug_plan::attn_decode_fused_grid(rows, H, HKV)), dim3(64 * ADF_WAVES), st, qkv, ss, pos_dev,
+                     (bf16_t*)cache_k, (bf16_t*)cache_v, (int)rows, HKV, H, (int)ld, (int)Tmax, (int)max_pos, (const bf16_t*)bias, cos_tab,
+                     sin_tab, key_valid, (bf16_t*)o, ldo, eps, (int)norm_cols, scale);
+  };
+  if (nparts == 0) return go(attn_decode_fused_kernel<0>);
+  if (nparts == ug_plan::DEC_ORD_QKV_SLABS) return go(attn_decode_fused_kernel<6>);
+  return ug_no_kernel(name);
+}
+
+// finish_resid_norm_kernel<MAXV> (nparts == 0: src is the accumulator, which the kernel also clears) or
+// finish_resid_norm_ord_kernel<MAXV> (src holds nparts slots of rows x ld floats)
+int launch_finish_resid_norm(const char* name, int64_t nparts, const float* src, int64_t ld, float* x, const float* w, void* xn, int64_t rows,
+                             int64_t cols, float eps, int* pos_inc, int* len_inc, hipStream_t st) {
+  const dim3 grid((unsigned)rows), block(64);
+  auto acc_form = [&](auto kern) {
+    return ug_launch(name, kern, grid, block, st, const_cast<float*>(src), ld, x, w, (bf16_t*)xn, (int)cols, eps, pos_inc, len_inc);
+  };
+  auto ord_form = [&](auto kern) {
+    return ug_launch(name, kern, grid, block, st, src, (int)ld, (int)nparts, x, w, (bf16_t*)xn, (int)cols, eps, pos_inc, len_inc);
+  };
+  switch (ug_plan::finish_vectors(cols) + (nparts ? 1 : 0)) {
+    case 8: return acc_form(finish_resid_norm_kernel<8>);
+    case 16: return acc_form(finish_resid_norm_kernel<16>);
+    case 8 + 1: return ord_form(finish_resid_norm_ord_kernel<8>);
+    case 16 + 1: return ord_form(finish_resid_norm_ord_kernel<16>);
+  }
+  return ug_no_kernel(name);
 }
 
 // 32-bit / 24-bit ranges of the ring kernels' addressing (weights up to 2^31 elements, strides below 2^24)
@@ -1148,25 +1193,16 @@ extern "C" int ug_gemv_bf16(const void* x, int64_t ldx, int64_t R, const void* W
                             int64_t acc_stride_n, int64_t N, int64_t K, hipStream_t st) {
   UG_REQUIRE(R > 0 && R <= 32 && N > 0 && K > 0 && K % 32 == 0, "ug_gemv_bf16: need 1 <= rows <= 32 and K %% 32 == 0 (rows=%ld K=%ld)", (long)R, (long)K);
   UG_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ug_aligned16(x) && ug_aligned16(W), "ug_gemv_bf16: 16-byte aligned rows required");
-  const int64_t groups = (N + 15) / 16;
   const bf16_t* xb = (const bf16_t*)x;
   const bf16_t* wb = (const bf16_t*)W;
-  if (K >= 256) {
+  const ug_plan::GemvPlan pl = ug_plan::plan_gemv((int)R, N, K);
+  if (pl.ring) {
     UG_RING_RANGES("ug_gemv_bf16", N, K, ldw, acc_stride_r, acc_stride_n);
     UG_REQUIRE(ldx < (1 << 24), "ug_gemv_bf16: ldx beyond 2^24");
-    launch_ring_auto<XIN_BF16>(st, xb, (int)ldx, (int)R, wb, (int)ldw, acc, (int)acc_stride_r, (int)acc_stride_n, (int)N, (int)K, DecodeIn{});
-    UG_CHECK_LAUNCH("ug_gemv_bf16");
-    return UG_OK;
+    return launch_ring_auto<XIN_BF16>("ug_gemv_bf16", st, xb, (int)ldx, (int)R, wb, (int)ldw, acc, (int)acc_stride_r, (int)acc_stride_n, (int)N,
+                                      (int)K, DecodeIn{});
   }
-  // short contractions: direct loads, deepest per-wave unroll that still leaves >= 2048 waves
-  int U = 8;
-  while (U > 1 && groups * ((K + 32 * U - 1) / (32 * U)) < 2048) U >>= 1;
-  const int64_t nslices = (K + 32 * U - 1) / (32 * U);
-  dim3 grid((unsigned)groups, (unsigned)((nslices + 3) / 4));
-  if (R <= 16) launch_gemv<1>(U, grid, st, xb, ldx, (int)R, wb, ldw, acc, acc_stride_r, acc_stride_n, (int)N, (int)K);
-  else launch_gemv<2>(U, grid, st, xb, ldx, (int)R, wb, ldw, acc, acc_stride_r, acc_stride_n, (int)N, (int)K);
-  UG_CHECK_LAUNCH("ug_gemv_bf16");
-  return UG_OK;
+  return launch_gemv("ug_gemv_bf16", pl, st, xb, ldx, (int)R, wb, ldw, acc, acc_stride_r, acc_stride_n, (int)N, (int)K);
 }
 
 #define UG_DECODE_COMMON(name)                                                                                              \
@@ -1182,10 +1218,8 @@ extern "C" int ug_decode_gemv(const void* x, int64_t ldx, int64_t R, const void*
   UG_DECODE_COMMON("ug_decode_gemv");
   UG_REQUIRE(x && ldx % 8 == 0 && ug_aligned16(x), "ug_decode_gemv: activations must be 16-byte aligned rows");
   UG_REQUIRE(ldx < (1 << 24), "ug_decode_gemv: ldx beyond 2^24");
-  launch_ring_auto<XIN_BF16>(st, (const bf16_t*)x, (int)ldx, (int)R, (const bf16_t*)W, (int)ldw, acc, (int)ldacc, 1, (int)N, (int)K, DecodeIn{},
-                             zero0, n0, zero1, n1, ss_zero);
-  UG_CHECK_LAUNCH("ug_decode_gemv");
-  return UG_OK;
+  return launch_ring_auto<XIN_BF16>("ug_decode_gemv", st, (const bf16_t*)x, (int)ldx, (int)R, (const bf16_t*)W, (int)ldw, acc, (int)ldacc, 1, (int)N,
+                                    (int)K, DecodeIn{}, zero0, n0, zero1, n1, ss_zero);
 }
 
 extern "C" int ug_decode_gemv_resid_norm(const float* x_in, const float* pending, int64_t ld_pending, const float* norm_w,
@@ -1199,9 +1233,8 @@ extern "C" int ug_decode_gemv_resid_norm(const float* x_in, const float* pending
   DecodeIn f{};
   f.x_in = x_in; f.pend = pending; f.ld_pend = ld_pending; f.norm_w = norm_w; f.x_out = x_out; f.ss_out = ss_out;
   UG_REQUIRE(ld_pending < (1 << 24), "ug_decode_gemv_resid_norm: ld_pending beyond 2^24");
-  launch_ring_auto<XIN_RESID_NORM>(st, nullptr, 0, (int)R, (const bf16_t*)W, (int)ldw, acc, (int)ldacc, 1, (int)N, (int)K, f, zero0, n0, zero1, n1, ss_zero);
-  UG_CHECK_LAUNCH("ug_decode_gemv_resid_norm");
-  return UG_OK;
+  return launch_ring_auto<XIN_RESID_NORM>("ug_decode_gemv_resid_norm", st, nullptr, 0, (int)R, (const bf16_t*)W, (int)ldw, acc, (int)ldacc, 1, (int)N,
+                                          (int)K, f, zero0, n0, zero1, n1, ss_zero);
 }
 
 extern "C" int ug_decode_gemv_swiglu(const float* gate_up_acc, int64_t ld_gu, const float* ss_in, float eps, int64_t norm_cols,
@@ -1213,9 +1246,8 @@ extern "C" int ug_decode_gemv_swiglu(const float* gate_up_acc, int64_t ld_gu, co
   DecodeIn f{};
   f.gu = gate_up_acc; f.ld_gu = ld_gu; f.ss_in = ss_in; f.eps = eps; f.norm_cols = (int)norm_cols;
   UG_REQUIRE(ld_gu < (1 << 24), "ug_decode_gemv_swiglu: ld_gu beyond 2^24");
-  launch_ring_auto<XIN_SWIGLU>(st, nullptr, 0, (int)R, (const bf16_t*)W, (int)ldw, acc, (int)ldacc, 1, (int)N, (int)K, f, zero0, n0, zero1, n1, ss_zero);
-  UG_CHECK_LAUNCH("ug_decode_gemv_swiglu");
-  return UG_OK;
+  return launch_ring_auto<XIN_SWIGLU>("ug_decode_gemv_swiglu", st, nullptr, 0, (int)R, (const bf16_t*)W, (int)ldw, acc, (int)ldacc, 1, (int)N, (int)K, f,
+                                      zero0, n0, zero1, n1, ss_zero);
 }
 
 extern "C" int ug_decode_finish_resid_norm(float* acc, int64_t ldacc, float* x, const float* w, void* xn, int64_t rows,
@@ -1225,14 +1257,7 @@ extern "C" int ug_decode_finish_resid_norm(float* acc, int64_t ldacc, float* x, 
              "ug_decode_finish_resid_norm: bad args (cols=%ld, multiple of 4 and <= 4096)", (long)cols);
   UG_REQUIRE(ug_aligned16(x) && ug_aligned16(w) && ug_aligned16(acc) && ((uintptr_t)xn & 7) == 0,
              "ug_decode_finish_resid_norm: alignment");
-  if (cols <= 2048)
-    hipLaunchKernelGGL(finish_resid_norm_kernel<8>, dim3((unsigned)rows), dim3(64), 0, st, acc, ldacc, x, w, (bf16_t*)xn,
-                       (int)cols, eps, pos_inc, len_inc);
-  else
-    hipLaunchKernelGGL(finish_resid_norm_kernel<16>, dim3((unsigned)rows), dim3(64), 0, st, acc, ldacc, x, w, (bf16_t*)xn,
-                       (int)cols, eps, pos_inc, len_inc);
-  UG_CHECK_LAUNCH("ug_decode_finish_resid_norm");
-  return UG_OK;
+  return launch_finish_resid_norm("ug_decode_finish_resid_norm", 0, acc, ldacc, x, w, xn, rows, cols, eps, pos_inc, len_inc, st);
 }
 
 extern "C" int ug_kv_store(const void* qkv, int64_t ldq, int64_t k_col, int64_t v_col, void* cache_k, void* cache_v,
@@ -1274,14 +1299,9 @@ extern "C" int ug_attn_decode_fused(const float* acc_qkv, int64_t ldacc, const f
                                     int H, int HKV, int head_dim, int64_t Tmax, int64_t max_pos, float scale, hipStream_t st) {
   UG_REQUIRE(rows > 0 && head_dim == DHD && H % HKV == 0 && acc_qkv && ss_in && norm_cols > 0 && pos_dev && cache_k && cache_v && o,
              "ug_attn_decode_fused: bad args");
-  // (XCD-aware placement: see the kernel)
-  const dim3 grid(8u, (unsigned)(H / HKV), (unsigned)((rows * HKV + 7) / 8));
   UG_REQUIRE(ldacc > 0 && ldacc < (1ll << 31), "ug_attn_decode_fused: ldacc out of range");
-  hipLaunchKernelGGL(attn_decode_fused_kernel<>, grid, dim3(64 * ADF_WAVES), 0, st, acc_qkv, ss_in, pos_dev, (bf16_t*)cache_k,
-                     (bf16_t*)cache_v, (int)rows, HKV, H, (int)ldacc, (int)Tmax, (int)max_pos, (const bf16_t*)bias, cos_tab, sin_tab,
-                     key_valid, (bf16_t*)o, ldo, eps, (int)norm_cols, scale);
-  UG_CHECK_LAUNCH("ug_attn_decode_fused");
-  return UG_OK;
+  return launch_attn_decode_fused("ug_attn_decode_fused", 0, acc_qkv, ldacc, ss_in, eps, norm_cols, bias, cos_tab, sin_tab, pos_dev, cache_k, cache_v,
+                                  key_valid, o, ldo, rows, H, HKV, Tmax, max_pos, scale, st);
 }
 
 extern "C" int ug_skinny_finish(const float* acc, const void* bias, void* out_bf16, float* resid, int64_t M, int64_t N,
@@ -1302,20 +1322,14 @@ extern "C" int ug_gemv_bf16_ord(const void* x, int64_t ldx, int64_t R, const voi
              (long)R, (long)K);
   UG_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ug_aligned16(x) && ug_aligned16(W) && ldpart >= N && part_stride >= R * ldpart,
              "ug_gemv_bf16_ord: 16-byte aligned rows, ldpart >= N and slots of rows x ldpart required");
-  const int64_t groups = (N + 15) / 16, nslabs = (K + 255) / 256;
-  UG_REQUIRE(part_stride * nslabs < (1ll << 31) && ldx < (1 << 24), "ug_gemv_bf16_ord: partial slots beyond 2^31 floats");
-  const bf16_t* xb = (const bf16_t*)x;
-  const bf16_t* wb = (const bf16_t*)W;
+  UG_REQUIRE(part_stride * ug_plan::dec_slabs(K) < (1ll << 31) && ldx < (1 << 24), "ug_gemv_bf16_ord: partial slots beyond 2^31 floats");
   // one wave per (k-slab, 16 weight rows): slot = k-slab (a contraction shorter than 256 is one slab; the tile loads clamp to K and the
   // steps past K are skipped)
   UG_RING_RANGES("ug_gemv_bf16_ord", N, K, ldw, ldpart, 1);
   DecodeIn f{};
   f.part_slot = (int)part_stride;
-  const dim3 grid((unsigned)nslabs, (unsigned)groups);
-  if (R <= 16) hipLaunchKernelGGL((gemv_ring_kernel<1, 1, true>), grid, dim3(64), 0, st, xb, (int)ldx, (int)R, wb, (int)ldw, part, (int)ldpart, 1, (int)N, (int)K, f);
-  else hipLaunchKernelGGL((gemv_ring_kernel<2, 1, true>), grid, dim3(64), 0, st, xb, (int)ldx, (int)R, wb, (int)ldw, part, (int)ldpart, 1, (int)N, (int)K, f);
-  UG_CHECK_LAUNCH("ug_gemv_bf16_ord");
-  return UG_OK;
+  return launch_ring1("ug_gemv_bf16_ord", R <= ug_plan::DEC_RING_MAX_ROWS1 ? 1 : 2, 1, true, to_dim3(ug_plan::gemv_ord_grid(N, K)), st, (const bf16_t*)x,
+                      (int)ldx, (int)R, (const bf16_t*)W, (int)ldw, part, (int)ldpart, 1, (int)N, (int)K, f);
 }
 
 extern "C" int ug_skinny_finish_ord(const float* parts, int64_t nparts, int64_t part_stride, const void* bias, void* out_bf16, float* out_f32,
@@ -1341,20 +1355,12 @@ extern "C" int ug_decode_gemv_resid_norm_ord(const float* x_in, const float* pen
                  ug_aligned16(pend_parts) && ug_aligned16(norm_w) && ug_aligned16(x_out),
              "ug_decode_gemv_resid_norm_ord: bad args (x_in and x_out must be distinct, 16-byte aligned fp32 buffers)");
   UG_RING_RANGES("ug_decode_gemv_resid_norm_ord", N, K, ldw, ldpart, 1);
-  const int64_t nslabs = (K + 255) / 256, groups = (N + 15) / 16;
-  UG_REQUIRE(npend * R * ld_pending < (1ll << 31) && nslabs * R * ldpart < (1ll << 31) && ld_pending < (1 << 24),
+  UG_REQUIRE(npend * R * ld_pending < (1ll << 31) && ug_plan::dec_slabs(K) * R * ldpart < (1ll << 31) && ld_pending < (1 << 24),
              "ug_decode_gemv_resid_norm_ord: partial slots beyond 2^31 floats");
   DecodeIn f{};
   f.x_out = x_out; f.ss_out = ss_part;
-  const dim3 grid((unsigned)nslabs, (unsigned)((groups + 3) / 4));          // four waves x one 16-row group per workgroup
-  if (npend == 0)
-    hipLaunchKernelGGL((gemv_ring4_kernel<1, 1, XIN_RESID_NORM, 4, false, 0>), grid, dim3(256), 0, st, x_in, pend_parts, norm_w, (const bf16_t*)W,
-                       (int)R, (int)K, (int)ld_pending, (int)ldw, (int)N, (int)nslabs, part, (int)ldpart, 1, f);
-  else
-    hipLaunchKernelGGL((gemv_ring4_kernel<1, 1, XIN_RESID_NORM, 4, false, 5>), grid, dim3(256), 0, st, x_in, pend_parts, norm_w, (const bf16_t*)W,
-                       (int)R, (int)K, (int)ld_pending, (int)ldw, (int)N, (int)nslabs, part, (int)ldpart, 1, f);
-  UG_CHECK_LAUNCH("ug_decode_gemv_resid_norm_ord");
-  return UG_OK;
+  return launch_ring4<XIN_RESID_NORM>("ug_decode_gemv_resid_norm_ord", ug_plan::plan_resid_norm_ord(N, K), (int)npend, st, x_in, pend_parts, norm_w,
+                                      (const bf16_t*)W, (int)R, (int)K, (int)ld_pending, (int)ldw, (int)N, part, (int)ldpart, 1, f);
 }
 
 extern "C" int ug_attn_decode_fused_ord(const float* qkv_part, int64_t ldpart, int64_t nparts, const float* ss_part, float eps, int64_t norm_cols,
@@ -1365,12 +1371,8 @@ extern "C" int ug_attn_decode_fused_ord(const float* qkv_part, int64_t ldpart, i
                  cache_v && o, "ug_attn_decode_fused_ord: bad args");
   UG_REQUIRE(nparts == 6, "ug_attn_decode_fused_ord: built for six k-slab slots (a 1536-wide hidden size; got %ld)", (long)nparts);
   UG_REQUIRE(ldpart > 0 && nparts * rows * ldpart < (1ll << 31), "ug_attn_decode_fused_ord: ldpart out of range");
-  const dim3 grid(8u, (unsigned)(H / HKV), (unsigned)((rows * HKV + 7) / 8));
-  hipLaunchKernelGGL(attn_decode_fused_kernel<6>, grid, dim3(64 * ADF_WAVES), 0, st, qkv_part, ss_part, pos_dev, (bf16_t*)cache_k,
-                     (bf16_t*)cache_v, (int)rows, HKV, H, (int)ldpart, (int)Tmax, (int)max_pos, (const bf16_t*)bias, cos_tab, sin_tab,
-                     key_valid, (bf16_t*)o, ldo, eps, (int)norm_cols, scale);
-  UG_CHECK_LAUNCH("ug_attn_decode_fused_ord");
-  return UG_OK;
+  return launch_attn_decode_fused("ug_attn_decode_fused_ord", nparts, qkv_part, ldpart, ss_part, eps, norm_cols, bias, cos_tab, sin_tab, pos_dev, cache_k,
+                                  cache_v, key_valid, o, ldo, rows, H, HKV, Tmax, max_pos, scale, st);
 }
 
 extern "C" int ug_decode_finish_resid_norm_ord(const float* parts, int64_t ldp, int64_t nparts, float* x, const float* w, void* xn, int64_t rows,
@@ -1380,12 +1382,5 @@ extern "C" int ug_decode_finish_resid_norm_ord(const float* parts, int64_t ldp, 
              "ug_decode_finish_resid_norm_ord: bad args (cols=%ld, multiple of 4 and <= 4096)", (long)cols);
   UG_REQUIRE(ug_aligned16(x) && ug_aligned16(w) && ug_aligned16(parts) && ((uintptr_t)xn & 7) == 0 && nparts * rows * ldp < (1ll << 31),
              "ug_decode_finish_resid_norm_ord: alignment / slot range");
-  if (cols <= 2048)
-    hipLaunchKernelGGL(finish_resid_norm_ord_kernel<8>, dim3((unsigned)rows), dim3(64), 0, st, parts, (int)ldp, (int)nparts, x, w, (bf16_t*)xn,
-                       (int)cols, eps, pos_inc, len_inc);
-  else
-    hipLaunchKernelGGL(finish_resid_norm_ord_kernel<16>, dim3((unsigned)rows), dim3(64), 0, st, parts, (int)ldp, (int)nparts, x, w, (bf16_t*)xn,
-                       (int)cols, eps, pos_inc, len_inc);
-  UG_CHECK_LAUNCH("ug_decode_finish_resid_norm_ord");
-  return UG_OK;
+  return launch_finish_resid_norm("ug_decode_finish_resid_norm_ord", nparts, parts, ldp, x, w, xn, rows, cols, eps, pos_inc, len_inc, st);
 }

@@ -17,6 +17,7 @@
 //   weights stream HBM -> LDS by LDS-DMA (nt), 16 rows x 256 k per tile, source-side XOR swizzle, per-wave ring, all vector memory
 //   hand-issued with counted waits (vmem_asm.h); 256 workgroups split the 1.5B model's projections exactly (6 / 70 / 32 weight rows).
 #include "common.h"
+#include "decode_plan.h"
 #include "unigen_hip.h"
 #include "vmem_asm.h"
 #include <stdlib.h>
@@ -305,14 +306,8 @@ int cu_count() {
   return n;
 }
 
-// units per workgroup: one workgroup per CU when the tile budget allows, else as many units as MAXT tiles hold
-int units_per_wg(int nunits, int max_upw) {
-  const int ncu = cu_count();
-  int upw = (nunits + ncu - 1) / ncu;
-  if (upw < 1) upw = 1;
-  return upw > max_upw ? max_upw : upw;
-}
-
+// ---- host side: the entry points check their arguments and fill SwArgs, plan_sw (decode_plan.h) gives units per workgroup and grid,
+// launch_sw names each instantiation once
 // the kernel's leading scalar arguments (kernarg preload: see gemv_sw_kernel) out of a filled SwArgs
 #define UG_SW_LEAD_NORM(a) (a).W, (const void*)(a).h, (const void*)(a).norm_w, (a).ldw, (a).K, (a).R, (a).nunits, (a).upw, 0, (a).I, (a).eps
 #define UG_SW_LEAD_BF16(a, aux) (a).W, (const void*)(a).xb, (const void*)(aux), (a).ldw, (a).K, (a).R, (a).nunits, (a).upw, (a).ldx, 0, 0.f
@@ -326,10 +321,46 @@ int units_per_wg(int nunits, int max_upw) {
   UG_REQUIRE(pend != nullptr || x_out == nullptr, name ": x_out is written only together with a pending accumulator");               \
   a.pend = pend; a.ld_pend = (int)ld_pend; a.x_out = x_out
 
+// gemv_sw_kernel<PRO, EPI, NW, MAXT, RING, MAXI, PEND, KBLK> of a filled SwArgs: the plan's units per workgroup and grid, for
+// SW_KBLOCK every workgroup's share of the clears (n0, n1 floats), then the one case that names the instantiation
+int launch_sw(const char* name, ug_plan::SwKind kind, SwArgs a, int ncu, hipStream_t st, int64_t n0 = 0, int64_t n1 = 0) {
+  const ug_plan::SwPlan pl = ug_plan::plan_sw(kind, a.nunits, a.K, ncu);
+  a.upw = pl.upw;
+  UG_REQUIRE(!a.x_out || pl.grid.x >= 8, "%s: fewer than eight workgroups cannot write x_out", name);
+  if (kind == ug_plan::SW_KBLOCK) {
+    const ug_plan::ClearShares c = ug_plan::clear_shares(n0, n1, pl.grid.x * pl.grid.y);
+    a.n0_4 = c.n0_4; a.per0 = c.per0; a.n1_4 = c.n1_4; a.per1 = c.per1;
+  }
+  const dim3 grid(pl.grid.x, pl.grid.y), block(64 * pl.waves);
+  auto norm = [&](auto kern) { return ug_launch(name, kern, grid, block, st, UG_SW_LEAD_NORM(a), a); };
+  auto bf16 = [&](auto kern, const void* aux) { return ug_launch(name, kern, grid, block, st, UG_SW_LEAD_BF16(a, aux), a); };
+  switch (kind * 2 + (a.pend ? 1 : 0)) {
+    case ug_plan::SW_GATE_UP * 2: return norm(gemv_sw_kernel<PRO_NORM, EPI_SWIGLU, 6, 5, 3, 8>);
+    case ug_plan::SW_GATE_UP * 2 + 1: return norm(gemv_sw_kernel<PRO_NORM, EPI_SWIGLU, 6, 5, 3, 8, true>);
+    case ug_plan::SW_RESID * 2: return bf16(gemv_sw_kernel<PRO_BF16, EPI_RESID, 6, 1, 1, 4>, a.h_io);
+    case ug_plan::SW_HEAD * 2: return norm(gemv_sw_kernel<PRO_NORM, EPI_STORE, 6, 2, 2, 8>);
+    case ug_plan::SW_HEAD * 2 + 1: return norm(gemv_sw_kernel<PRO_NORM, EPI_STORE, 6, 2, 2, 8, true>);
+    case ug_plan::SW_KBLOCK * 2: return bf16(gemv_sw_kernel<PRO_BF16, EPI_ATOMIC, 7, 2, 2, 8, false, true>, nullptr);
+    case ug_plan::SW_KBLOCK_ORD * 2: return bf16(gemv_sw_kernel<PRO_BF16, EPI_PART, 7, 2, 2, 8, false, true>, nullptr);
+  }
+  return ug_no_kernel(name);
+}
+
+// ug_decode_sw_kblock (nslots == 0: one atomic per element into `out`, carrying the clears) and ug_decode_sw_kblock_ord (nslots = the
+// k-blocks, each stores its own slot out[k-block][R][ld_out]: no atomics, no clears)
+int launch_sw_kblock(const char* name, int64_t nslots, const void* x, int64_t ldx, int64_t R, const void* W, int64_t ldw, float* out, int64_t ld_out,
+                     int64_t N, int64_t K, float* zero0, int64_t n0, float* zero1, int64_t n1, float* ss_zero, hipStream_t st) {
+  SwArgs a{};
+  a.W = (const bf16_t*)W; a.ldw = (int)ldw; a.K = (int)K; a.R = (int)R;
+  a.nunits = (int)N; a.xb = (const bf16_t*)x; a.ldx = (int)ldx; a.out = out; a.ld_out = (int)ld_out;
+  a.zero0 = zero0; a.zero1 = zero1; a.ss_zero = ss_zero;
+  return launch_sw(name, nslots ? ug_plan::SW_KBLOCK_ORD : ug_plan::SW_KBLOCK, a, 0, st, n0, n1);
+}
+
 }  // namespace
 
 extern "C" int ug_decode_sw_supported(int64_t hidden, int64_t inter, int64_t q_dim, int head_dim) {
-  return hidden == 1536 && q_dim == 1536 && inter > 0 && head_dim == 128 ? 1 : 0;
+  return ug_plan::decode_sw_supported(hidden, inter, q_dim, head_dim) ? 1 : 0;
 }
 
 extern "C" int ug_decode_sw_gate_up(const float* h, const float* pend, int64_t ld_pend, float* x_out, const float* norm_w, float eps,
@@ -341,16 +372,11 @@ extern "C" int ug_decode_sw_gate_up(const float* h, const float* pend, int64_t l
              "ug_decode_sw_gate_up: bad args (hidden must be 1536; hidden=%ld)", (long)H);
   SwArgs a{};
   a.W = (const bf16_t*)W; a.ldw = (int)ldw; a.K = (int)H; a.R = (int)R;
-  a.nunits = (int)I; a.upw = units_per_wg(a.nunits, 40);
+  a.nunits = (int)I;
   a.h = h; a.norm_w = norm_w; a.eps = eps;
   a.act = (bf16_t*)act; a.ld_act = (int)ld_act; a.I = (int)I;
   UG_SW_PEND_ARGS("ug_decode_sw_gate_up");
-  const unsigned grid = (unsigned)((a.nunits + a.upw - 1) / a.upw);
-  UG_REQUIRE(!x_out || grid >= 8, "ug_decode_sw_gate_up: fewer than eight workgroups cannot write x_out");
-  if (pend) hipLaunchKernelGGL((gemv_sw_kernel<PRO_NORM, EPI_SWIGLU, 6, 5, 3, 8, true>), dim3(grid), dim3(64 * 6), 0, st, UG_SW_LEAD_NORM(a), a);
-  else hipLaunchKernelGGL((gemv_sw_kernel<PRO_NORM, EPI_SWIGLU, 6, 5, 3, 8>), dim3(grid), dim3(64 * 6), 0, st, UG_SW_LEAD_NORM(a), a);
-  UG_CHECK_LAUNCH("ug_decode_sw_gate_up");
-  return UG_OK;
+  return launch_sw("ug_decode_sw_gate_up", ug_plan::SW_GATE_UP, a, cu_count(), st);
 }
 
 extern "C" int ug_decode_sw_resid(const void* x, int64_t ldx, int64_t R, const void* W, int64_t ldw, int64_t N, int64_t K, float* h,
@@ -361,11 +387,7 @@ extern "C" int ug_decode_sw_resid(const void* x, int64_t ldx, int64_t R, const v
   SwArgs a{};
   a.W = (const bf16_t*)W; a.ldw = (int)ldw; a.K = (int)K; a.R = (int)R;
   a.nunits = (int)N; a.xb = (const bf16_t*)x; a.ldx = (int)ldx; a.h_io = h;
-  a.upw = units_per_wg(a.nunits, 8);
-  const unsigned grid = (unsigned)((a.nunits + a.upw - 1) / a.upw);
-  hipLaunchKernelGGL((gemv_sw_kernel<PRO_BF16, EPI_RESID, 6, 1, 1, 4>), dim3(grid), dim3(64 * 6), 0, st, UG_SW_LEAD_BF16(a, a.h_io), a);
-  UG_CHECK_LAUNCH("ug_decode_sw_resid");
-  return UG_OK;
+  return launch_sw("ug_decode_sw_resid", ug_plan::SW_RESID, a, cu_count(), st);
 }
 
 extern "C" int ug_decode_sw_kblock(const void* x, int64_t ldx, int64_t R, const void* W, int64_t ldw, float* acc, int64_t ldacc, int64_t N,
@@ -375,18 +397,7 @@ extern "C" int ug_decode_sw_kblock(const void* x, int64_t ldx, int64_t R, const 
                  ldacc >= N && n0 % 4 == 0 && n1 % 4 == 0 && n0 < (1ll << 31) && n1 < (1ll << 31) && ug_aligned16(zero0) && ug_aligned16(zero1),
              "ug_decode_sw_kblock: bad args (the contraction must be a whole number of 1792-wide k-blocks: seven waves x one 256-wide "
              "k-slab; K=%ld)", (long)K);
-  SwArgs a{};
-  a.W = (const bf16_t*)W; a.ldw = (int)ldw; a.K = (int)K; a.R = (int)R;
-  a.nunits = (int)N; a.xb = (const bf16_t*)x; a.ldx = (int)ldx; a.out = acc; a.ld_out = (int)ldacc;
-  a.upw = 32;                                                  // two 16-row tiles per workgroup
-  const dim3 grid((unsigned)((a.nunits + a.upw - 1) / a.upw), (unsigned)(K / (256 * 7)));
-  const unsigned nblocks = grid.x * grid.y;
-  a.zero0 = zero0; a.zero1 = zero1; a.ss_zero = ss_zero;
-  a.n0_4 = (int)(n0 >> 2); a.n1_4 = (int)(n1 >> 2);
-  a.per0 = (int)((a.n0_4 + nblocks - 1) / nblocks); a.per1 = (int)((a.n1_4 + nblocks - 1) / nblocks);
-  hipLaunchKernelGGL((gemv_sw_kernel<PRO_BF16, EPI_ATOMIC, 7, 2, 2, 8, false, true>), grid, dim3(64 * 7), 0, st, UG_SW_LEAD_BF16(a, nullptr), a);
-  UG_CHECK_LAUNCH("ug_decode_sw_kblock");
-  return UG_OK;
+  return launch_sw_kblock("ug_decode_sw_kblock", 0, x, ldx, R, W, ldw, acc, ldacc, N, K, zero0, n0, zero1, n1, ss_zero, st);
 }
 
 extern "C" int ug_decode_sw_head(const float* h, const float* pend, int64_t ld_pend, float* x_out, const float* norm_w, float eps,
@@ -398,15 +409,10 @@ extern "C" int ug_decode_sw_head(const float* h, const float* pend, int64_t ld_p
              "ug_decode_sw_head: bad args (hidden must be 1536; hidden=%ld)", (long)H);
   SwArgs a{};
   a.W = (const bf16_t*)W; a.ldw = (int)ldw; a.K = (int)H; a.R = (int)R;
-  a.nunits = (int)N; a.upw = units_per_wg(a.nunits, 32);
+  a.nunits = (int)N;
   a.h = h; a.norm_w = norm_w; a.eps = eps; a.out = logits; a.ld_out = (int)ld_logits; a.pos_inc = pos_inc; a.len_inc = len_inc;
   UG_SW_PEND_ARGS("ug_decode_sw_head");
-  const unsigned grid = (unsigned)((a.nunits + a.upw - 1) / a.upw);
-  UG_REQUIRE(!x_out || grid >= 8, "ug_decode_sw_head: fewer than eight workgroups cannot write x_out");
-  if (pend) hipLaunchKernelGGL((gemv_sw_kernel<PRO_NORM, EPI_STORE, 6, 2, 2, 8, true>), dim3(grid), dim3(64 * 6), 0, st, UG_SW_LEAD_NORM(a), a);
-  else hipLaunchKernelGGL((gemv_sw_kernel<PRO_NORM, EPI_STORE, 6, 2, 2, 8>), dim3(grid), dim3(64 * 6), 0, st, UG_SW_LEAD_NORM(a), a);
-  UG_CHECK_LAUNCH("ug_decode_sw_head");
-  return UG_OK;
+  return launch_sw("ug_decode_sw_head", ug_plan::SW_HEAD, a, cu_count(), st);
 }
 
 extern "C" int ug_decode_sw_kblock_ord(const void* x, int64_t ldx, int64_t R, const void* W, int64_t ldw, float* part, int64_t ldpart, int64_t N,
@@ -415,12 +421,5 @@ extern "C" int ug_decode_sw_kblock_ord(const void* x, int64_t ldx, int64_t R, co
   UG_REQUIRE(x && part && K > 0 && K % (256 * 7) == 0 && ldx >= K && ldx % 8 == 0 && ldx < (1 << 20) && ldw >= K && ug_aligned16(x) &&
                  ldpart >= N && (K / (256 * 7)) * R * ldpart < (1ll << 31),
              "ug_decode_sw_kblock_ord: bad args (the contraction must be a whole number of 1792-wide k-blocks; K=%ld)", (long)K);
-  SwArgs a{};
-  a.W = (const bf16_t*)W; a.ldw = (int)ldw; a.K = (int)K; a.R = (int)R;
-  a.nunits = (int)N; a.xb = (const bf16_t*)x; a.ldx = (int)ldx; a.out = part; a.ld_out = (int)ldpart;
-  a.upw = 32;                                                  // two 16-row tiles per workgroup, as ug_decode_sw_kblock
-  const dim3 grid((unsigned)((a.nunits + a.upw - 1) / a.upw), (unsigned)(K / (256 * 7)));
-  hipLaunchKernelGGL((gemv_sw_kernel<PRO_BF16, EPI_PART, 7, 2, 2, 8, false, true>), grid, dim3(64 * 7), 0, st, UG_SW_LEAD_BF16(a, nullptr), a);
-  UG_CHECK_LAUNCH("ug_decode_sw_kblock_ord");
-  return UG_OK;
+  return launch_sw_kblock("ug_decode_sw_kblock_ord", K / (256 * 7), x, ldx, R, W, ldw, part, ldpart, N, K, nullptr, 0, nullptr, 0, nullptr, st);
 }

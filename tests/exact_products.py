@@ -405,9 +405,15 @@ def wgrad_group_k(n):
     return WGRAD_GROUP_K if n != 1 else max(40, WGRAD_GROUP_K // 3 // 8 * 8)      # the second problem has a K of its own
 
 
-GEMV_SHAPES = [(16, 2048, 1536), (5, 333, 256), (16, 1536, 8960), (1, 64, 32), (16, 17920, 1536)]       # (R, N, K)
-# more than 16 rows: gemv_kernel<2, .> (K = 32), gemv_ring_kernel<2, 1> and, from 3000 tiles on (501 groups x 6 slabs), <2, 2>
-GEMV_TALL_SHAPES = [(17, 64, 32), (24, 333, 256), (32, 2048, 1536), (24, 8016, 1536)]
+# (R, N, K).  The last three: the direct kernel's deeper unrolls (csrc/decode_plan.h, plan_gemv: the deepest U that leaves 2048 waves) at
+# the fewest weight rows that select them -- gemv_kernel<1, 8> (2048 groups x one 256-wide slice), <1, 4> (1024 groups x two 128-wide
+# slices), <1, 2> (1024 x two 64-wide); (1, 64, 32) runs <1, 1>
+GEMV_SHAPES = [(16, 2048, 1536), (5, 333, 256), (16, 1536, 8960), (1, 64, 32), (16, 17920, 1536), (3, 32753, 32), (5, 16369, 160),
+               (2, 16369, 96)]
+# more than 16 rows: gemv_kernel<2, .> (K = 32), gemv_ring_kernel<2, 1> and, from 3000 tiles on (501 groups x 6 slabs), <2, 2>; the last
+# three: gemv_kernel<2, 8>, <2, 4>, <2, 2> as above
+GEMV_TALL_SHAPES = [(17, 64, 32), (24, 333, 256), (32, 2048, 1536), (24, 8016, 1536), (17, 32753, 32), (18, 16369, 160), (20, 16369, 96)]
+GEMV_ORD_TALL_SHAPES = [(17, 64, 32)]          # ug_gemv_bf16_ord beyond 16 rows: gemv_ring_kernel<2, 1, true>
 # tests/test_decode_exact_gpu.py (R, N, K); what each reaches is asserted in tests/test_exact_products_cpu.py
 RESID_NORM_SHAPES = [(1, 16, 256), (5, 333, 1568), (16, 2048, 1536), (13, 272, 3584), (17, 333, 1568), (32, 2048, 1536),
                      (16, 8208, 1536), (16, 16400, 1536), (16, 48, 4864)]

@@ -43,7 +43,8 @@ def _assert_cleared(*ts):
 def test_gemv_acc_into_prefilled_accumulator(dev, R, N, K):
     """ug_gemv_bf16: the ring kernel (K >= 256) and the direct-load kernel (K = 32); twice into the same accumulator.  The shapes of
     more than 16 rows run the two-row-block instantiations: gemv_kernel<2, .> at K = 32, gemv_ring_kernel<2, 1> and -- from 3000 tiles
-    on, (24, 8016, 1536) has 501 groups x 6 slabs -- gemv_ring_kernel<2, 2>."""
+    on, (24, 8016, 1536) has 501 groups x 6 slabs -- gemv_ring_kernel<2, 2>.  The shapes of 16 369 and 32 753 weight rows at K < 256
+    run the direct kernel's unrolls 2, 4 and 8 (tests/test_decode_plan_cpu.py says which shape selects which instantiation)."""
     ops = _ops()
     x, w, _, ref = _operands(dev, R, N, K, "dense")
     pre = ep.int_prefill(R, N, seed=N + K)
@@ -109,9 +110,10 @@ def test_decode_sw_resid(dev, R, N, K):
         ep.assert_exact(h, N, pre + rep * ref, f"decode_sw_resid_ {(R, N, K)} call {rep}")
 
 
-@pytest.mark.parametrize("R,N,K", ep.GEMV_SHAPES)
+@pytest.mark.parametrize("R,N,K", ep.GEMV_SHAPES + ep.GEMV_ORD_TALL_SHAPES)
 def test_skinny_linear_ord(dev, R, N, K):
-    """ug_gemv_bf16_ord + ug_skinny_finish_ord: per-256-k-slice slots summed in slice order -- bf16 (+ bias), residual update, fp32"""
+    """ug_gemv_bf16_ord + ug_skinny_finish_ord: per-256-k-slice slots summed in slice order -- bf16 (+ bias), residual update, fp32;
+    17 rows run the two-row-block form gemv_ring_kernel<2, 1, true>"""
     ops = _ops()
     x, w, bias, ref = _operands(dev, R, N, K, "small")
     y = ops.skinny_linear_ord(x, w, bias=bias.to(dev))
