@@ -116,25 +116,24 @@ class FlatGradSync:
     def _comm_init(self):
         import ctypes
         from . import lib as _l
-        L = _l.load()
+        self._lib, self._ug = _l.load(), _l.api()            # raw status (the unchecked destroy) / checked calls
         ident = ctypes.create_string_buffer(128)
         if self.rank == 0:
-            _l.check(L.ug_comm_unique_id(ident), "ug_comm_unique_id")
+            self._ug.ug_comm_unique_id(ident)
         box = [bytes(ident.raw)]
         if self.world > 1:
             dist.broadcast_object_list(box, src=0, group=self.pg)           # the only use of torch.distributed on this transport
         cap = min(self.max_bucket, self._numel)
         handle = ctypes.c_void_p()
-        _l.check(L.ug_comm_init(ctypes.byref(handle), self.world, self.rank, ctypes.create_string_buffer(box[0], 128), int(cap)), "ug_comm_init")
-        self._comm, self._lib = handle, L
+        self._ug.ug_comm_init(ctypes.byref(handle), self.world, self.rank, ctypes.create_string_buffer(box[0], 128), int(cap))
+        self._comm = handle
         self.backend = "ug_comm(rccl)"
         self._mode = {"fp32": 0, "bf16_fp32acc": 1, "bf16": 2, "fp32_rsag": 3}[self.reduce]
 
     def _comm_bucket(self, buf, mode=None):
-        from . import lib as _l
-        _l.check(self._lib.ug_comm_allreduce_bucket(self._comm, buf.data_ptr(), buf.numel(), self._mode if mode is None else mode,
-                                                    torch.cuda.current_stream().cuda_stream), "ug_comm_allreduce_bucket")
-        self.bytes_on_wire = int(self._lib.ug_comm_bytes_on_wire(self._comm))
+        self._ug.ug_comm_allreduce_bucket(self._comm, buf.data_ptr(), buf.numel(), self._mode if mode is None else mode,
+                                          torch.cuda.current_stream().cuda_stream)
+        self.bytes_on_wire = int(self._ug.ug_comm_bytes_on_wire(self._comm))
 
     def __del__(self):
         if getattr(self, "_comm", None) is not None:
@@ -285,10 +284,9 @@ class FlatGradSync:
             with torch.cuda.stream(self.stream):
                 d_src.copy_(src, non_blocking=True)
                 if self._comm is not None:
-                    from . import lib as _l
                     side = torch.cuda.current_stream().cuda_stream
-                    _l.check(self._lib.ug_comm_allgather(self._comm, d_src.data_ptr(), d_all.data_ptr(), 16, side), "ug_comm_allgather")
-                    _l.check(self._lib.ug_comm_wait(self._comm, side), "ug_comm_wait")
+                    self._ug.ug_comm_allgather(self._comm, d_src.data_ptr(), d_all.data_ptr(), 16, side)
+                    self._ug.ug_comm_wait(self._comm, side)
                 else:
                     dist.all_gather_into_tensor(d_all, d_src, group=self.pg)
                 dst.copy_(d_all, non_blocking=True)
@@ -344,8 +342,7 @@ class FlatGradSync:
                                  "lookup rows than announced); the ranks' collectives would no longer pair")
         if self.cuda:
             if self._comm is not None:
-                from . import lib as _l
-                _l.check(self._lib.ug_comm_wait(self._comm, torch.cuda.current_stream().cuda_stream), "ug_comm_wait")
+                self._ug.ug_comm_wait(self._comm, torch.cuda.current_stream().cuda_stream)
             else:
                 torch.cuda.current_stream().wait_stream(self.stream)
         else:
@@ -361,11 +358,9 @@ class FlatGradSync:
     def _all_gather_flat(self, recv, send):
         """recv [W * n] <- every rank's send [n] (on the current stream / host)"""
         if self._comm is not None:
-            from . import lib as _l
             side = torch.cuda.current_stream().cuda_stream
-            _l.check(self._lib.ug_comm_allgather(self._comm, send.data_ptr(), recv.data_ptr(), send.numel() * send.element_size(), side),
-                     "ug_comm_allgather")
-            _l.check(self._lib.ug_comm_wait(self._comm, side), "ug_comm_wait")
+            self._ug.ug_comm_allgather(self._comm, send.data_ptr(), recv.data_ptr(), send.numel() * send.element_size(), side)
+            self._ug.ug_comm_wait(self._comm, side)
         else:
             self._coll(dist.all_gather_into_tensor, recv, send)
 
@@ -500,17 +495,15 @@ class FlatGradSync:
                 with torch.cuda.stream(self.stream):
                     self.stream.wait_event(ev)
                     if self._comm is not None:      # the dense buckets run on the communicator's own stream
-                        from . import lib as _l
-                        _l.check(self._lib.ug_comm_wait(self._comm, self.stream.cuda_stream), "ug_comm_wait")
+                        self._ug.ug_comm_wait(self._comm, self.stream.cuda_stream)
                     self._exchange_lookups()
         self._embed_done = False
         extra = [p for p in (self.extra_params() if self.extra_params is not None else []) if p.grad is not None]
         if self._comm is not None:
-            from . import lib as _l
             flat = torch.cat([p.grad.reshape(-1).float() for p in extra]) if extra else None
             if flat is not None:
                 self._comm_bucket(flat, mode=0)
-            _l.check(self._lib.ug_comm_wait(self._comm, torch.cuda.current_stream().cuda_stream), "ug_comm_wait")
+            self._ug.ug_comm_wait(self._comm, torch.cuda.current_stream().cuda_stream)
             torch.cuda.current_stream().wait_stream(self.stream)        # (the lookups' sort + scatter ran there)
             o = 0
             for p in extra:
@@ -580,9 +573,8 @@ class FlatGradSync:
         v = torch.zeros(max(64, self.world), dtype=torch.float32, device=dev)
         v[self.rank] = 1.0
         if self._comm is not None:
-            from . import lib as _l
             self._comm_bucket(v, mode=0)
-            _l.check(self._lib.ug_comm_wait(self._comm, torch.cuda.current_stream().cuda_stream), "ug_comm_wait")
+            self._ug.ug_comm_wait(self._comm, torch.cuda.current_stream().cuda_stream)
         elif dist.is_initialized():
             self._allreduce_mean_(v)
         return int((v > 0).sum().item())

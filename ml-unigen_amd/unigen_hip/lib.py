@@ -1,139 +1,89 @@
 """ctypes binding of libunigen_hip.so (the C ABI declared in include/unigen_hip.h).
 
+The header is the table: every prototype in it is parsed at import and the ctypes argument and return types are derived from
+it, so the binding cannot drift from the declarations the compiler checks every definition against.  tests/test_binding_cpu.py
+freezes the derived ABI v7 table against a recorded one and tests/test_host_cpu.py checks the library's exports against it.
+
 The product path has no CPU fallback: if the shared library is missing the import of any op fails
 loudly with the build command.  Nothing under oracle/ is ever imported from here.
 """
+import collections
 import ctypes
 import os
+import re
 import subprocess
+import types
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.normpath(os.path.join(_HERE, "..", "csrc"))
 LIB_PATH = os.environ.get("UNIGEN_HIP_LIB") or os.path.join(CSRC_DIR, "libunigen_hip.so")     # (probe builds: tools/probes/_build/*.so)
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "unigen_hip.h"))
 
-ABI_VERSION = 7
 P = ctypes.c_void_p
 I64 = ctypes.c_int64
 I32 = ctypes.c_int
 F32 = ctypes.c_float
 
-# name -> argtypes (must mirror include/unigen_hip.h exactly; tests/test_abi.py cross-checks the
-# exported symbol list against the header)
-SIGNATURES = {
-    "ug_abi_version": [],
-    "ug_create": [P],
-    "ug_destroy": [P],
-    "ug_gemm_bf16": [P, P, I64, I32, P, I64, I32, P, I64, I64, I64, I64, I32, P, P, I64, I32, P, I32, P],
-    "ug_gemm_bf16_qkv_rope": [P, P, I64, P, I64, P, P, I64, I64, I64, I64, P, P, I64, I64, I32, P],
-    "ug_gemm_bf16_swiglu_bwd": [P, P, I64, P, I64, P, I64, P, I64, I64, I64, I64, P],
-    "ug_gemm_bf16_swiglu": [P, P, I64, P, I64, P, I64, P, I64, I64, I64, I64, P],
-    "ug_cast_f32_bf16": [P, P, I64, P],
-    "ug_rmsnorm_fwd": [P, P, P, P, I64, I64, F32, I32, P],
-    "ug_rmsnorm_bwd": [P, P, P, P, P, P, P, I64, I64, P],
-    "ug_rope": [P, P, P, I64, I64, I64, I32, I32, I32, P],
-    "ug_swiglu_fwd": [P, P, I64, I64, P],
-    "ug_swiglu_bwd": [P, P, P, I64, I64, P],
-    "ug_gelu": [P, P, P, I64, P],
-    "ug_embed_fwd": [P, P, P, I64, I64, I64, P, P],
-    "ug_embed_bwd": [P, P, P, I64, I64, I64, P],
-    "ug_embed_bwd_sorted": [P, P, P, P, I64, I64, I64, F32, P],
-    "ug_gather_rows_bf16": [P, I64, P, P, I64, I64, I64, I32, P],
-    "ug_colsum_bf16": [P, I64, P, I64, I64, P],
-    "ug_attn_mask_compress": [P, I32, I64, I64, P, P, I64, I64, P, P],
-    "ug_attn_mask_causal": [P, P, P, I64, I64, P],
-    "ug_attn_fwd": [P, P, P, I64, P, I64, P, P, P, I64, I64, I64, I32, I32, I32, F32, P],
-    "ug_attn_bwd": [P, P, P, I64, P, P, I64, P, P, P, P, P, I64, P, P, I64, I64, I64, I32, I32, I32, F32, P, P, P, P, P],
-    "ug_kv_store": [P, I64, I64, I64, P, P, I64, I64, I32, I32, I64, P, I32, P],
-    "ug_rope_at": [P, P, P, I64, I64, I32, I32, P, I64, P],
-    "ug_attn_decode": [P, I64, P, P, P, P, I64, I64, I32, I32, I32, I64, P, F32, P],
-    "ug_attn_prefill_cached": [P, I64, P, P, P, P, I64, I64, I64, I64, I32, I32, I32, I64, F32, P],
-    "ug_gemv_bf16": [P, I64, I64, P, I64, P, I64, I64, I64, I64, P],
-    "ug_decode_gemv": [P, I64, I64, P, I64, P, I64, I64, I64, P, I64, P, I64, P, P],
-    "ug_decode_gemv_resid_norm": [P, P, I64, P, P, P, I64, P, I64, P, I64, I64, I64, P, I64, P, I64, P, P],
-    "ug_decode_gemv_swiglu": [P, I64, P, F32, I64, I64, P, I64, P, I64, I64, I64, P, I64, P, I64, P, P],
-    "ug_gemm_set_fused_tile_height": [I32],
-    "ug_attn_decode_fused": [P, I64, P, F32, I64, P, P, P, P, P, P, P, P, I64, I64, I32, I32, I32, I64, I64, F32, P],
-    "ug_decode_finish_resid_norm": [P, I64, P, P, P, I64, I64, F32, P, P, P],
-    "ug_decode_sw_supported": [I64, I64, I64, I32],
-    "ug_decode_sw_kblock": [P, I64, I64, P, I64, P, I64, I64, I64, P, I64, P, I64, P, P],
-    "ug_decode_sw_resid": [P, I64, I64, P, I64, I64, I64, P, P],
-    "ug_decode_sw_gate_up": [P, P, I64, P, P, F32, I64, I64, P, I64, I64, P, I64, P],
-    "ug_decode_sw_head": [P, P, I64, P, P, F32, I64, I64, P, I64, I64, P, I64, P, P, P],
-    "ug_t2i_assemble": [P, P, P, I64, P, I64, P, P, I64, I64, I64, I64, I64, I64, I64, P, P, P, P],
-    "ug_attn_mask_from_ids": [P, I64, I64, I64, I64, I64, I32, P, P, P, P, P],
-    "ug_maskgit_train_mask": [P, P, P, I64, I64, I64, I64, P, P, P],
-    "ug_ar_sample": [P, I64, I64, I64, F32, F32, I32, P, P, I64, I64, P, I64, I64, I64, P, P, P, P],
-    "ug_ar_sample_filtered": [P, I64, I64, I64, F32, F32, I32, P, P, I64, I64, P, I64, I64, I64, P, P, P, I64, F32, F32, P, P],
-    "ug_text_pick": [P, I64, I64, I64, I32, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P],
-    "ug_text_sample_workspace_ints": [I64],
-    "ug_text_sample": [P, I64, I64, I64, I32, F32, I64, F32, P, P, P, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P],
-    "ug_ar_sample_logp": [P, I64, I64, I64, F32, F32, I32, P, P, I64, I64, P, I64, I64, I64, P, P, P, P, P],
-    "ug_ar_sample_filtered_logp": [P, I64, I64, I64, F32, F32, I32, P, P, I64, I64, P, I64, I64, I64, P, P, P, I64, F32, F32, P, P, P],
-    "ug_text_pick_logp": [P, I64, I64, I64, I32, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P, P],
-    "ug_text_sample_logp": [P, I64, I64, I64, I32, F32, I64, F32, P, P, P, P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P, P],
-    "ug_text_seen_mark": [P, I64, P, I64, I64, I64, P, I64, P],
-    "ug_text_penalize": [P, I64, I64, I64, F32, P, I64, P, P],
-    "ug_text_constrain": [P, I64, I64, I64, P, I64, I64, P, I64, I64, P, I64, P, P, I64, P, P],
-    "ug_text_stop_seq": [P, P, I64, I64, P, I64, I64, P, P, P],
-    "ug_maskgit_step": [P, I64, I64, I64, I64, I32, F32, P, P, P, I64, I64, I64, F32, P, P, P, P, P, P],
-    "ug_maskgit_step_ex": [P, I64, I64, I64, I64, I32, F32, P, P, P, I64, I64, I64, F32, F32, I64, F32, F32, P, P, P, P, P, P, P, P],
-    "ug_skinny_finish": [P, P, P, P, I64, I64, I32, P],
-    "ug_gemv_bf16_ord": [P, I64, I64, P, I64, P, I64, I64, I64, I64, P],
-    "ug_skinny_finish_ord": [P, I64, I64, P, P, P, P, I64, I64, P],
-    "ug_decode_gemv_resid_norm_ord": [P, P, I64, I64, P, P, P, I64, P, I64, P, I64, I64, I64, P],
-    "ug_attn_decode_fused_ord": [P, I64, I64, P, F32, I64, P, P, P, P, P, P, P, P, I64, I64, I32, I32, I32, I64, I64, F32, P],
-    "ug_decode_sw_kblock_ord": [P, I64, I64, P, I64, P, I64, I64, I64, P],
-    "ug_decode_finish_resid_norm_ord": [P, I64, I64, P, P, P, I64, I64, F32, P, P, P],
-    "ug_ce_fwd": [P, I64, I64, I64, P, I64, P, P, P, P, P],
-    "ug_ce_bwd": [P, I64, I64, I64, P, I64, P, P, P, P, P],
-    "ug_head_score_ws_bytes": [I64, I64],
-    "ug_head_score": [P, I64, I64, P, I64, I64, I64, P, I64, P, P, P, P, P, P],
-    "ug_adamw_flat": [P, P, P, P, P, I64, F32, F32, F32, F32, F32, I64, F32, I32, P],
-    "ug_adamw_flat_dev": [P, P, P, P, P, I64, F32, F32, F32, F32, F32, I64, F32, P, I32, P],
-    "ug_sumsq_spans_f32": [P, I64, P, I32, I32, P],
-    "ug_clip_finish": [P, I64, F32, F32, P, P],
-    "ug_scale_spans_f32": [P, I64, P, I32, P],
-    "ug_gemm_bf16_wgrad_group": [I32, P, P, P, P, P, P, P, P, P, P, P],
-    "ug_grad_pack_bf16": [P, P, I64, F32, P],
-    "ug_comm_unique_id": [P],
-    "ug_comm_init": [P, I32, I32, P, I64],
-    "ug_comm_allreduce_bucket": [P, P, I64, I32, P],
-    "ug_comm_allgather": [P, P, P, I64, P],
-    "ug_comm_wait": [P, P],
-    "ug_comm_destroy": [P],
-    "ug_comm_bytes_on_wire": [P],
-    "ug_zero_ranges_f32": [P, P, I64, I64, P],
-    "ug_grad_unpack_bf16": [P, P, I64, P],
-    "ug_grad_sum_shards_bf16": [P, I32, I64, P, I64, F32, P],
-    "ug_conv2d_f32": [P, P, P, P, P, I64, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P],
-    "ug_conv_split_weights": [P, P, I32, I32, I32, P],
-    "ug_amax_f32": [P, I64, I64, I64, P, P],
-    "ug_amax_f32_into_zeroed": [P, I64, I64, I64, P, P],
-    "ug_conv2d_split": [P, P, P, P, P, P, I64, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, I32, P],
-    "ug_conv3x3_split": [P, P, P, P, P, P, I64, I32, I32, I32, I32, I32, P, P, P, I32, I32, P, I32, P],
-    "ug_groupnorm_finalize": [P, P, I64, I64, I32, I32, F32, P],
-    "ug_groupnorm_stats": [P, P, P, I64, I64, I32, I32, F32, P],
-    "ug_siglip_attn_f32": [P, I64, P, P, I64, I64, I64, I32, I32, F32, P],
-    "ug_linear_split": [P, I64, P, P, P, P, I64, P, I64, I64, I64, I64, I32, I32, P],
-    "ug_gemm_f32_nested": [P, I64, I64, I64, P, I64, I64, I64, I32, P, I64, I64, I64, I64, I64, I64, I64, I64, F32, P],
-    "ug_gemm_f32": [P, I64, I64, P, I64, I64, I32, P, I64, I64, I64, I64, I64, I64, F32, P],
-    "ug_groupnorm_swish": [P, P, P, P, P, I64, I64, I32, I32, F32, I32, P],
-    "ug_softmax_rows_f32": [P, I64, I64, I64, F32, P],
-    "ug_linear_f32": [P, I64, P, I64, P, P, I64, P, I64, I64, I64, I64, I32, P],
-    "ug_layernorm_f32": [P, P, P, P, I64, I64, F32, P],
-    "ug_layernorm_bwd_f32": [P, P, P, P, P, P, P, I64, I64, F32, P],
-    "ug_gelu_tanh_f32": [P, P, P, I64, P],
-    "ug_softmax_bwd_rows_f32": [P, P, I64, I64, I64, F32, P],
-    "ug_colsum_f32": [P, I64, P, I64, I64, P],
-    "ug_transpose_f32": [P, I64, I64, P, I64, I64, I64, I64, I64, P],
-    "ug_nchw_to_nhwc": [P, P, I64, I32, I64, I32, P],
-    "ug_nhwc_to_nchw": [P, P, I64, I32, I64, I32, P],
-    "ug_lfq_pack": [P, I64, P, I64, I32, P],
-    "ug_lfq_unpack": [P, P, I64, I32, P, P],
-    "ug_probe_layouts": [P, I64, P],
-}
+
+class UniGenHipError(RuntimeError):
+    pass
+
+
+# ---- the header's prototypes -> ctypes.  Nothing is guessed: a type outside these two maps fails the import, naming the prototype.
+_SCALARS = {"int64_t": I64, "int": I32, "float": F32, "hipStream_t": P}
+_RETURNS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
+# restype / argtypes: ctypes types; names / c_types: the header's parameter names and their C spellings
+Proto = collections.namedtuple("Proto", "restype argtypes names c_types")
+
+
+def _c_type(text):
+    return re.sub(r"\*(?=\w)", "* ", re.sub(r"\s*\*\s*", "*", text.strip()))      # one spelling: `const void* const*`
+
+
+def parse_header(text):
+    """C header text -> ({name: Proto} for every `RET ug_name(params);` in the header's order, UG_ABI_VERSION or None)"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+UG_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, re.M)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    protos = {}
+    for stmt in re.split(r"[;{}]", text):
+        if "(" not in stmt:
+            continue                                   # typedefs, `extern "C"`
+        stmt = " ".join(stmt.split())
+        m = re.fullmatch(r"([\w \*]+?) ?\b(ug_\w+) ?\(([^()]*)\)", stmt)
+        if m is None:
+            raise UniGenHipError(f"unigen_hip.h: cannot bind `{stmt}`: not of the form RET ug_name(TYPE name, ...)")
+        ret, name, params = _c_type(m.group(1)), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise UniGenHipError(f"unigen_hip.h: {name}: no ctypes mapping for the return type `{ret}`")
+        argtypes, names, c_types = [], [], []
+        for param in ([] if params == "void" else params.split(",")):
+            pm = re.fullmatch(r"(.*[\w\*]) ?\b(\w+)", param.strip())
+            c = _c_type(pm.group(1)) if pm else ""
+            if "*" in c:
+                kind = P
+            elif c in _SCALARS:
+                kind = _SCALARS[c]
+            else:
+                raise UniGenHipError(f"unigen_hip.h: {name}: no ctypes mapping for the parameter `{param.strip()}`")
+            argtypes.append(kind)
+            names.append(pm.group(2))
+            c_types.append(c)
+        protos[name] = Proto(_RETURNS[ret], argtypes, names, c_types)
+    return protos, (int(version.group(1)) if version else None)
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES, ABI_VERSION = parse_header(_f.read())
+if ABI_VERSION is None:
+    raise UniGenHipError(f"{HEADER_PATH} defines no UG_ABI_VERSION")
+SIGNATURES = {name: proto.argtypes for name, proto in PROTOTYPES.items() if name != "ug_last_error"}    # name -> argtypes
+# entry points whose return value is a value, not a status: api() hands it back unchecked
+VALUE_RETURNS = frozenset(("ug_abi_version", "ug_decode_sw_supported", "ug_text_sample_workspace_ints", "ug_head_score_ws_bytes",
+                           "ug_comm_bytes_on_wire"))
 
 _lib = None
+_api = None
 
 # Launch-time breakdown by kernel family (bench.py's `roofline_by_family`): when PROFILE is a dict, every entry point that
 # launches on the caller's stream is bracketed by a pair of HIP events recorded on torch's current stream -- the stream every
@@ -154,36 +104,75 @@ def family_of(name):
     return "elementwise"
 
 
-def _profiled(name, fn):
-    fam = family_of(name)
+# bench tags that carry the launch's shape: entry point -> (the header's parameter names, format of their values)
+_TAGS = {
+    "ug_gemm_bf16": (("M", "N", "K", "a_kmajor", "b_kmajor", "epilogue"),
+                     lambda *v: "ug_gemm_bf16[M=%d N=%d K=%d ak=%d bk=%d epi=%d]" % v),
+    "ug_conv3x3_split": (("B", "H", "W", "Cin", "Cout", "gn_mu_rstd"),
+                         lambda *v: "ug_conv3x3_split[B=%d %dx%d %d->%d gn=%d]" % (v[:5] + (1 if v[5] else 0,))),
+    "ug_gemm_bf16_wgrad_group": (("n", "rows", "cols", "K"),
+                                 lambda n, rows, cols, K: "ug_gemm_bf16_wgrad_group[%s]" % " ".join("%dx%dx%d" % (rows[i], cols[i], K[i]) for i in range(n))),
+}
 
-    def call(*args):
-        prof = PROFILE
-        if prof is None:
-            return fn(*args)
-        import torch
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        sp = args[-1]                                  # every launching entry point takes its stream last
-        sp = getattr(sp, "value", sp) or 0
-        st = torch.cuda.current_stream() if sp == torch.cuda.current_stream().cuda_stream else torch.cuda.ExternalStream(sp)
+
+def _tagger(name, names):
+    """args -> the bench tag of one call; the tag's fields are resolved to argument positions here, once"""
+    if name not in _TAGS:
+        return lambda args: name
+    fields, fmt = _TAGS[name]
+    missing = [f for f in fields if f not in names]
+    if missing:
+        raise UniGenHipError(f"{name}: its profile tag reads the parameters {missing}, which include/unigen_hip.h does not declare")
+    idx = [names.index(f) for f in fields]
+    return lambda args: fmt(*[args[i] for i in idx])
+
+
+def _event_pair(sp):
+    """two timing events and the torch stream that the raw hipStream_t `sp` is"""
+    import torch
+    sp = getattr(sp, "value", sp) or 0
+    cur = torch.cuda.current_stream()
+    st = cur if sp == cur.cuda_stream else torch.cuda.ExternalStream(sp)
+    return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), st
+
+
+def _failure(name, rc, last_error):
+    return UniGenHipError(f"{name} failed (rc={rc}): {last_error().decode('utf-8', 'replace')}")
+
+
+def _profiled(name, fn, names, last_error):
+    """(raw, checked) forms of a launching entry point: both time the launch when PROFILE is set; `raw` returns the status,
+    `checked` raises UniGenHipError on a non-zero one"""
+    fam, tag_of = family_of(name), _tagger(name, names)
+
+    def timed(prof, args):
+        e0, e1, st = _event_pair(args[-1])             # every launching entry point takes its stream last
         e0.record(st)
         rc = fn(*args)
         e1.record(st)
-        tag = name
-        if name == "ug_gemm_bf16":                     # (handle, A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N, K, epilogue, ...)
-            tag = "ug_gemm_bf16[M=%d N=%d K=%d ak=%d bk=%d epi=%d]" % (args[9], args[10], args[11], args[3], args[6], args[12])
-        elif name == "ug_conv3x3_split":               # (x, x_amax, w_split, bias, residual, y, B, H, W, Cin, Cout, ...)
-            tag = "ug_conv3x3_split[B=%d %dx%d %d->%d gn=%d]" % (args[6], args[7], args[8], args[9], args[10], 1 if args[12] else 0)
-        elif name == "ug_gemm_bf16_wgrad_group":       # (n, dy, ld_dy, x, ld_x, dw, ld_dw, rows, cols, beta, K, stream)
-            tag = "ug_gemm_bf16_wgrad_group[%s]" % " ".join("%dx%dx%d" % (args[7][i], args[8][i], args[10][i]) for i in range(args[0]))
-        prof.setdefault(fam, []).append((e0, e1, tag))
+        prof.setdefault(fam, []).append((e0, e1, tag_of(args)))
         return rc
-    call.__name__ = name
-    return call
+
+    def raw(*args):
+        prof = PROFILE
+        return fn(*args) if prof is None else timed(prof, args)
+
+    def checked(*args):
+        prof = PROFILE
+        rc = fn(*args) if prof is None else timed(prof, args)
+        if rc != 0:
+            raise _failure(name, rc, last_error)
+    raw.__name__ = checked.__name__ = name
+    return raw, checked
 
 
-class UniGenHipError(RuntimeError):
-    pass
+def _checked(name, fn, last_error):
+    def checked(*args):
+        rc = fn(*args)
+        if rc != 0:
+            raise _failure(name, rc, last_error)
+    checked.__name__ = name
+    return checked
 
 
 def build(verbose=False):
@@ -199,7 +188,8 @@ def build(verbose=False):
 
 
 def load():
-    global _lib
+    """The library with every entry point bound to the header's prototype; its functions return the raw status."""
+    global _lib, _api
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
@@ -211,22 +201,33 @@ def load():
     # device -- so torch's runtime always goes first (the host side of this library is PyTorch anyway).
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    lib.ug_last_error.restype = ctypes.c_char_p
-    lib.ug_last_error.argtypes = []
-    for name, argtypes in SIGNATURES.items():
+    checked = types.SimpleNamespace()
+    last_error = lib.ug_last_error
+    for name, proto in PROTOTYPES.items():
         fn = getattr(lib, name)   # AttributeError here = header/library mismatch: fail loudly
-        fn.argtypes = argtypes
-        fn.restype = ctypes.c_int64 if name == "ug_comm_bytes_on_wire" else ctypes.c_int
-        if name.startswith("ug_comm_") or name in ("ug_abi_version", "ug_create", "ug_destroy"):
-            continue
-        setattr(lib, name, _profiled(name, fn))
+        fn.argtypes, fn.restype = proto.argtypes, proto.restype
+        if name in VALUE_RETURNS or name == "ug_last_error":
+            setattr(checked, name, fn)
+        elif proto.c_types[-1:] != ["hipStream_t"] or name.startswith("ug_comm_"):      # launches nothing / runs on its own streams
+            setattr(checked, name, _checked(name, fn, last_error))
+        else:
+            raw, chk = _profiled(name, fn, proto.names, last_error)
+            setattr(lib, name, raw)
+            setattr(checked, name, chk)
     if lib.ug_abi_version() != ABI_VERSION:
         raise UniGenHipError(f"ABI version mismatch: library reports {lib.ug_abi_version()}, binding expects {ABI_VERSION}")
-    _lib = lib
+    _lib, _api = lib, checked
     return lib
+
+
+def api():
+    """The checked call surface: api().ug_x(*args) launches and raises UniGenHipError itself on a non-zero status (the
+    VALUE_RETURNS entries hand their value back as it is)."""
+    if _api is None:
+        load()
+    return _api
 
 
 def check(rc, name="ug call"):
     if rc != 0:
-        msg = load().ug_last_error().decode("utf-8", "replace")
-        raise UniGenHipError(f"{name} failed (rc={rc}): {msg}")
+        raise _failure(name, rc, load().ug_last_error)

@@ -69,7 +69,7 @@ def _handle():
         if torch.cuda.is_current_stream_capturing():
             return 0
         out = ctypes.c_void_p()
-        _l.check(_l.load().ug_create(ctypes.byref(out)), "ug_create")
+        _l.api().ug_create(ctypes.byref(out))
         h = _HANDLES[key] = out.value
     return h
 
@@ -107,12 +107,11 @@ def gemm(a, b, out=None, *, M=None, N=None, K=None, a_kmajor=False, b_kmajor=Fal
     if out is None:
         dt = out_dtype or (torch.bfloat16 if epilogue == UG_EPI_BF16 else torch.float32)
         out = torch.empty((M, N), dtype=dt, device=a.device)
-    lib = _l.load()
+    lib = _l.api()
     with _gemm_timed(2.0 * M * N * K):
-        rc = lib.ug_gemm_bf16(_handle(), _p(a), a.stride(0), int(a_kmajor), _p(b), b.stride(0), int(b_kmajor), _p(out), out.stride(0),
-                              M, N, K, epilogue, _p(bias), _p(resid), resid.stride(0) if resid is not None else 0, beta,
-                              _p(alpha_dev), GEMM_POLICY, _stream())
-        _l.check(rc, "ug_gemm_bf16")
+        lib.ug_gemm_bf16(_handle(), _p(a), a.stride(0), int(a_kmajor), _p(b), b.stride(0), int(b_kmajor), _p(out), out.stride(0),
+                         M, N, K, epilogue, _p(bias), _p(resid), resid.stride(0) if resid is not None else 0, beta,
+                         _p(alpha_dev), GEMM_POLICY, _stream())
     return out
 
 
@@ -135,8 +134,8 @@ def gemm_swiglu(x, w_gate_up):
     gu = torch.empty((M, 2 * I), dtype=torch.bfloat16, device=x.device)
     act = torch.empty((M, I), dtype=torch.bfloat16, device=x.device)
     with _gemm_timed(2.0 * M * 2 * I * K, fused=True):
-        _l.check(_l.load().ug_gemm_bf16_swiglu(_handle(), _p(x), x.stride(0), _p(w_gate_up), w_gate_up.stride(0), _p(gu), gu.stride(0),
-                                               _p(act), act.stride(0), M, I, K, _stream()), "ug_gemm_bf16_swiglu")
+        _l.api().ug_gemm_bf16_swiglu(_handle(), _p(x), x.stride(0), _p(w_gate_up), w_gate_up.stride(0), _p(gu), gu.stride(0),
+                                     _p(act), act.stride(0), M, I, K, _stream())
     return gu, act
 
 
@@ -158,13 +157,12 @@ def gemm_wgrad_group(problems):
         _need_cuda(dy, x, dw)
         assert dy.shape[0] == x.shape[0] and dw.shape == (dy.shape[1], x.shape[1])
     with _gemm_timed(sum(2.0 * dy.shape[1] * x.shape[1] * dy.shape[0] for dy, x, _, _ in problems)):
-        rc = _l.load().ug_gemm_bf16_wgrad_group(
+        _l.api().ug_gemm_bf16_wgrad_group(
             n, PA(*[_p(dy) for dy, _, _, _ in problems]), LA(*[dy.stride(0) for dy, _, _, _ in problems]),
             PA(*[_p(x) for _, x, _, _ in problems]), LA(*[x.stride(0) for _, x, _, _ in problems]),
             PA(*[_p(dw) for _, _, dw, _ in problems]), LA(*[dw.stride(0) for _, _, dw, _ in problems]),
             LA(*[dy.shape[1] for dy, _, _, _ in problems]), LA(*[x.shape[1] for _, x, _, _ in problems]),
             IA(*[int(b) for _, _, _, b in problems]), LA(*[dy.shape[0] for dy, _, _, _ in problems]), _stream())
-        _l.check(rc, "ug_gemm_bf16_wgrad_group")
 
 
 def set_gemm_tile_policy(policy):
@@ -189,7 +187,7 @@ def set_gemm_tile_policy(policy):
 def set_fused_tile_height(rows):
     """Tile height of the fused-epilogue GEMM launches (gemm_swiglu / gemm_qkv_rope / gemm_swiglu_bwd): 0 = automatic; tests force
     every instantiated height (include/unigen_hip.h: ug_gemm_set_fused_tile_height)."""
-    _l.check(_l.load().ug_gemm_set_fused_tile_height(int(rows)), "ug_gemm_set_fused_tile_height")
+    _l.api().ug_gemm_set_fused_tile_height(int(rows))
 
 
 def gemm_nt(a, b, out=None, **kw):
@@ -201,32 +199,31 @@ def cast_bf16(x, out=None):
     _need_cuda(x)
     if out is None:
         out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-    _l.check(_l.load().ug_cast_f32_bf16(_p(x), _p(out), x.numel(), _stream()), "ug_cast_f32_bf16")
+    _l.api().ug_cast_f32_bf16(_p(x), _p(out), x.numel(), _stream())
     return out
 
 
 def zero_ranges_(buf, ranges, max_len):
     """Clear the spans {first, count} (int64 device table [n, 2]) of the fp32 buffer `buf` with one launch."""
-    _l.check(_l.load().ug_zero_ranges_f32(_p(buf), _p(ranges), ranges.shape[0], int(max_len), _stream()), "ug_zero_ranges_f32")
+    _l.api().ug_zero_ranges_f32(_p(buf), _p(ranges), ranges.shape[0], int(max_len), _stream())
     return buf
 
 
 def grad_pack_bf16(g, out, scale):
     """out (bf16) = g (fp32) * scale: staging for the data-parallel bf16 all-reduce (unigen_hip/ddp.py)."""
     _need_cuda(g, out)
-    _l.check(_l.load().ug_grad_pack_bf16(_p(g), _p(out), g.numel(), float(scale), _stream()), "ug_grad_pack_bf16")
+    _l.api().ug_grad_pack_bf16(_p(g), _p(out), g.numel(), float(scale), _stream())
 
 
 def grad_unpack_bf16(src, g):
     _need_cuda(src, g)
-    _l.check(_l.load().ug_grad_unpack_bf16(_p(src), _p(g), g.numel(), _stream()), "ug_grad_unpack_bf16")
+    _l.api().ug_grad_unpack_bf16(_p(src), _p(g), g.numel(), _stream())
 
 
 def grad_sum_shards_bf16(shards, world, stride, out, scale):
     """out (bf16 [n]) = bf16(scale * sum over the `world` bf16 shards of n elements, `stride` apart), fp32 sum in rank order."""
     _need_cuda(shards, out)
-    _l.check(_l.load().ug_grad_sum_shards_bf16(_p(shards), int(world), int(stride), _p(out), out.numel(), float(scale), _stream()),
-             "ug_grad_sum_shards_bf16")
+    _l.api().ug_grad_sum_shards_bf16(_p(shards), int(world), int(stride), _p(out), out.numel(), float(scale), _stream())
 
 
 # ------------------------------------------------------------------------------------ row ops
@@ -235,8 +232,7 @@ def rmsnorm_fwd(x, w, eps, out_f32=False, want_rstd=True, out=None):
     rows, cols = x.shape
     y = out if out is not None else torch.empty((rows, cols), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
     rstd = torch.empty((rows,), dtype=torch.float32, device=x.device) if want_rstd else None
-    _l.check(_l.load().ug_rmsnorm_fwd(_p(x), _p(w), _p(y), _p(rstd), rows, cols, eps, int(out_f32), _stream()),
-             "ug_rmsnorm_fwd")
+    _l.api().ug_rmsnorm_fwd(_p(x), _p(w), _p(y), _p(rstd), rows, cols, eps, int(out_f32), _stream())
     return y, rstd
 
 
@@ -245,8 +241,7 @@ def rmsnorm_bwd(dy, x, rstd, w, dres, dw, want_bf16=False):
     the GEMMs that consume the updated gradient), written by the same kernel."""
     rows, cols = x.shape
     out = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device) if want_bf16 else None
-    _l.check(_l.load().ug_rmsnorm_bwd(_p(dy), _p(x), _p(rstd), _p(w), _p(dres), _p(dw), _p(out), rows, cols, _stream()),
-             "ug_rmsnorm_bwd")
+    _l.api().ug_rmsnorm_bwd(_p(dy), _p(x), _p(rstd), _p(w), _p(dres), _p(dw), _p(out), rows, cols, _stream())
     return out
 
 
@@ -281,8 +276,8 @@ def rope_tables(L, head_dim, theta, device, scaling=None):
 
 def rope_(qkv, cos, sin, L, nheads, head_dim, backward=False):
     tokens = qkv.shape[0]
-    _l.check(_l.load().ug_rope(_p(qkv), _p(cos), _p(sin), tokens, L, qkv.stride(0), nheads, head_dim,
-                               int(backward), _stream()), "ug_rope")
+    _l.api().ug_rope(_p(qkv), _p(cos), _p(sin), tokens, L, qkv.stride(0), nheads, head_dim,
+                     int(backward), _stream())
     return qkv
 
 
@@ -299,15 +294,15 @@ def gemm_qkv_rope(x, w, bias, cos, sin, L, nheads, head_dim):
         return rope_(qkv, cos, sin, L, nheads, head_dim)
     qkv = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     with _gemm_timed(2.0 * M * N * K, fused=True):
-        _l.check(_l.load().ug_gemm_bf16_qkv_rope(_handle(), _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(qkv), qkv.stride(0), M, N, K,
-                                                  _p(cos), _p(sin), L, nheads * head_dim, head_dim, _stream()), "ug_gemm_bf16_qkv_rope")
+        _l.api().ug_gemm_bf16_qkv_rope(_handle(), _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(qkv), qkv.stride(0), M, N, K,
+                                        _p(cos), _p(sin), L, nheads * head_dim, head_dim, _stream())
     return qkv
 
 
 def swiglu_fwd(gu):
     tokens, two_i = gu.shape
     act = torch.empty((tokens, two_i // 2), dtype=torch.bfloat16, device=gu.device)
-    _l.check(_l.load().ug_swiglu_fwd(_p(gu), _p(act), tokens, two_i // 2, _stream()), "ug_swiglu_fwd")
+    _l.api().ug_swiglu_fwd(_p(gu), _p(act), tokens, two_i // 2, _stream())
     return act
 
 
@@ -328,15 +323,14 @@ def gemm_swiglu_bwd(dy, w_down, gu):
         return swiglu_bwd(gu, gemm(dy, w_down, b_kmajor=True))
     dgu = torch.empty_like(gu)
     with _gemm_timed(2.0 * M * I * K, fused=True):
-        _l.check(_l.load().ug_gemm_bf16_swiglu_bwd(_handle(), _p(dy), dy.stride(0), _p(w_down), w_down.stride(0), _p(gu), gu.stride(0),
-                                                    _p(dgu), dgu.stride(0), M, I, K, _stream()), "ug_gemm_bf16_swiglu_bwd")
+        _l.api().ug_gemm_bf16_swiglu_bwd(_handle(), _p(dy), dy.stride(0), _p(w_down), w_down.stride(0), _p(gu), gu.stride(0),
+                                          _p(dgu), dgu.stride(0), M, I, K, _stream())
     return dgu
 
 
 def swiglu_bwd(gu, dact):
     dgu = torch.empty_like(gu)
-    _l.check(_l.load().ug_swiglu_bwd(_p(gu), _p(dact), _p(dgu), gu.shape[0], gu.shape[1] // 2, _stream()),
-             "ug_swiglu_bwd")
+    _l.api().ug_swiglu_bwd(_p(gu), _p(dact), _p(dgu), gu.shape[0], gu.shape[1] // 2, _stream())
     return dgu
 
 
@@ -344,40 +338,38 @@ def embed_fwd(ids, W, err_flag=None):
     tokens = ids.numel()
     V, H = W.shape
     out = torch.empty((tokens, H), dtype=torch.float32, device=W.device)
-    _l.check(_l.load().ug_embed_fwd(_p(ids), _p(W), _p(out), tokens, H, V, _p(err_flag), _stream()), "ug_embed_fwd")
+    _l.api().ug_embed_fwd(_p(ids), _p(W), _p(out), tokens, H, V, _p(err_flag), _stream())
     return out
 
 
 def embed_bwd(ids, dout, dW):
     V, H = dW.shape
-    _l.check(_l.load().ug_embed_bwd(_p(ids), _p(dout), _p(dW), ids.numel(), H, V, _stream()), "ug_embed_bwd")
+    _l.api().ug_embed_bwd(_p(ids), _p(dout), _p(dW), ids.numel(), H, V, _stream())
 
 
 def embed_bwd_sorted(ids_sorted, order, rows, dW, scale):
     """dW[id] += scale * sum of the rows of each run of equal ids, in sorted order (deterministic; ddp.py's lookup exchange)"""
     V, H = dW.shape
-    _l.check(_l.load().ug_embed_bwd_sorted(_p(ids_sorted), _p(order), _p(rows), _p(dW), ids_sorted.numel(), H, V, float(scale), _stream()),
-             "ug_embed_bwd_sorted")
+    _l.api().ug_embed_bwd_sorted(_p(ids_sorted), _p(order), _p(rows), _p(dW), ids_sorted.numel(), H, V, float(scale), _stream())
 
 
 def gather_rows(x, idx):
     n, C = idx.numel(), x.shape[1]
     out = torch.empty((n, C), dtype=torch.bfloat16, device=x.device)
-    _l.check(_l.load().ug_gather_rows_bf16(_p(x), x.stride(0), _p(idx), _p(out), C, n, C, 0, _stream()), "ug_gather_rows_bf16")
+    _l.api().ug_gather_rows_bf16(_p(x), x.stride(0), _p(idx), _p(out), C, n, C, 0, _stream())
     return out
 
 
 def scatter_rows_(src, idx, out):
     n, C = idx.numel(), src.shape[1]
-    _l.check(_l.load().ug_gather_rows_bf16(_p(src), src.stride(0), _p(idx), _p(out), out.stride(0), n, C, 1, _stream()),
-             "ug_gather_rows_bf16")
+    _l.api().ug_gather_rows_bf16(_p(src), src.stride(0), _p(idx), _p(out), out.stride(0), n, C, 1, _stream())
     return out
 
 
 def colsum_(x, out, R=None, C=None):
     R = x.shape[0] if R is None else R
     C = x.shape[1] if C is None else C
-    _l.check(_l.load().ug_colsum_bf16(_p(x), x.stride(0), _p(out), R, C, _stream()), "ug_colsum_bf16")
+    _l.api().ug_colsum_bf16(_p(x), x.stride(0), _p(out), R, C, _stream())
 
 
 # ------------------------------------------------------------------------------------ attention
@@ -412,15 +404,15 @@ def mask_compress(mask4d, err_flag=None):
     if m.dtype not in _MASK_DTYPES:
         raise _l.UniGenHipError(f"unsupported attention-mask dtype {m.dtype}")
     bits, tileany = _alloc_mask(B, L, m.device)
-    _l.check(_l.load().ug_attn_mask_compress(_p(m), _MASK_DTYPES[m.dtype], m.stride(0), m.stride(1), _p(bits),
-                                             _p(tileany), B, L, _p(err_flag), _stream()), "ug_attn_mask_compress")
+    _l.api().ug_attn_mask_compress(_p(m), _MASK_DTYPES[m.dtype], m.stride(0), m.stride(1), _p(bits),
+                                   _p(tileany), B, L, _p(err_flag), _stream())
     return MaskBits(bits, tileany, B, L)
 
 
 def mask_causal(B, L, device, key_valid=None):
     bits, tileany = _alloc_mask(B, L, device)
     kv = None if key_valid is None else key_valid.to(torch.uint8).contiguous()
-    _l.check(_l.load().ug_attn_mask_causal(_p(kv), _p(bits), _p(tileany), B, L, _stream()), "ug_attn_mask_causal")
+    _l.api().ug_attn_mask_causal(_p(kv), _p(bits), _p(tileany), B, L, _stream())
     return MaskBits(bits, tileany, B, L)
 
 
@@ -436,8 +428,8 @@ def mask_from_ids(ids, pad_id, soi_id, eoi_id, mode=MASK_T2I):
     bits, tileany = _alloc_mask(B, L, ids.device)
     meta = torch.empty((B, 4), dtype=torch.int32, device=ids.device)
     flags = torch.empty((B, L), dtype=torch.uint8, device=ids.device)
-    _l.check(_l.load().ug_attn_mask_from_ids(_p(ids), B, L, int(pad_id), int(soi_id), int(eoi_id), int(mode), _p(meta), _p(flags),
-                                             _p(bits), _p(tileany), _stream()), "ug_attn_mask_from_ids")
+    _l.api().ug_attn_mask_from_ids(_p(ids), B, L, int(pad_id), int(soi_id), int(eoi_id), int(mode), _p(meta), _p(flags),
+                                   _p(bits), _p(tileany), _stream())
     return MaskBits(bits, tileany, B, L)
 
 
@@ -460,9 +452,9 @@ def t2i_assemble(text_ids, image_in, image_labels, max_seq_len, pad_id, soi_id, 
     ids = torch.empty((B, max_seq_len), dtype=torch.int64, device=dev)
     labels = torch.empty_like(ids)
     attn = torch.empty((B, max_seq_len), dtype=torch.uint8, device=dev)
-    _l.check(_l.load().ug_t2i_assemble(_p(flat), _p(offs), _p(cs), cs.numel(), _p(ce), ce.numel(), _p(image_in.to(torch.int64).contiguous()),
-                                       _p(image_labels.to(torch.int64).contiguous()), B, n, max_seq_len, int(pad_id), int(soi_id),
-                                       int(eoi_id), int(ignore_id), _p(ids), _p(labels), _p(attn), _stream()), "ug_t2i_assemble")
+    _l.api().ug_t2i_assemble(_p(flat), _p(offs), _p(cs), cs.numel(), _p(ce), ce.numel(), _p(image_in.to(torch.int64).contiguous()),
+                             _p(image_labels.to(torch.int64).contiguous()), B, n, max_seq_len, int(pad_id), int(soi_id),
+                             int(eoi_id), int(ignore_id), _p(ids), _p(labels), _p(attn), _stream())
     return ids, attn, labels
 
 
@@ -479,8 +471,8 @@ def attn_fwd(qkv, mb, H, HKV, hd, scale=None, out=None):
     else:
         o = torch.empty((B * L, H * hd), dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
-    _l.check(_l.load().ug_attn_fwd(_p(q), _p(k), _p(v), qkv.stride(0), _p(o), o.stride(0), _p(lse), _p(mb.bits),
-                                   _p(mb.tileany), B, L, Lp, H, HKV, hd, scale, _stream()), "ug_attn_fwd")
+    _l.api().ug_attn_fwd(_p(q), _p(k), _p(v), qkv.stride(0), _p(o), o.stride(0), _p(lse), _p(mb.bits),
+                         _p(mb.tileany), B, L, Lp, H, HKV, hd, scale, _stream())
     return o, lse
 
 
@@ -511,22 +503,22 @@ def attn_bwd(qkv, o, lse, dout, mb, H, HKV, hd, scale=None, split_heads=True, ro
     dv = dqkv[:, (H + HKV) * hd:]
     delta = torch.empty((B, H, L), dtype=torch.float32, device=qkv.device)
     ws = _dkv_workspace(B * L, 2 * HKV * hd, qkv.device) if split_heads and H > HKV else None
-    _l.check(_l.load().ug_attn_bwd(_p(q), _p(k), _p(v), qkv.stride(0), _p(o), _p(dout), o.stride(0),
-                                   _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), dqkv.stride(0), _p(mb.bits),
-                                   _p(mb.tileany), B, L, Lp, H, HKV, hd, scale, _p(ws), _p(rope[0] if rope else None),
-                                   _p(rope[1] if rope else None), _p(dbias), _stream()), "ug_attn_bwd")
+    _l.api().ug_attn_bwd(_p(q), _p(k), _p(v), qkv.stride(0), _p(o), _p(dout), o.stride(0),
+                         _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), dqkv.stride(0), _p(mb.bits),
+                         _p(mb.tileany), B, L, Lp, H, HKV, hd, scale, _p(ws), _p(rope[0] if rope else None),
+                         _p(rope[1] if rope else None), _p(dbias), _stream())
     return dqkv
 
 
 # ------------------------------------------------------------------------------------ decode
 def kv_store(qkv, cache_k, cache_v, rows, L, H, HKV, hd, Tmax, pos_dev=None, pos_host=0):
-    _l.check(_l.load().ug_kv_store(_p(qkv), qkv.stride(0), H * hd, (H + HKV) * hd, _p(cache_k), _p(cache_v), rows, L, HKV, hd,
-                                   Tmax, _p(pos_dev), pos_host, _stream()), "ug_kv_store")
+    _l.api().ug_kv_store(_p(qkv), qkv.stride(0), H * hd, (H + HKV) * hd, _p(cache_k), _p(cache_v), rows, L, HKV, hd,
+                         Tmax, _p(pos_dev), pos_host, _stream())
 
 
 def rope_at_(qkv, cos, sin, nheads, hd, pos_dev):
-    _l.check(_l.load().ug_rope_at(_p(qkv), _p(cos), _p(sin), qkv.shape[0], qkv.stride(0), nheads, hd, _p(pos_dev),
-                                  cos.shape[0], _stream()), "ug_rope_at")
+    _l.api().ug_rope_at(_p(qkv), _p(cos), _p(sin), qkv.shape[0], qkv.stride(0), nheads, hd, _p(pos_dev),
+                        cos.shape[0], _stream())
     return qkv
 
 
@@ -534,8 +526,8 @@ def attn_decode(qkv, cache_k, cache_v, key_valid, H, HKV, hd, Tmax, len_dev, sca
     rows = qkv.shape[0]
     scale = 1.0 / math.sqrt(hd) if scale is None else scale
     o = out if out is not None else torch.empty((rows, H * hd), dtype=torch.bfloat16, device=qkv.device)
-    _l.check(_l.load().ug_attn_decode(_p(qkv), qkv.stride(0), _p(cache_k), _p(cache_v), _p(key_valid), _p(o), o.stride(0),
-                                      rows, H, HKV, hd, Tmax, _p(len_dev), scale, _stream()), "ug_attn_decode")
+    _l.api().ug_attn_decode(_p(qkv), qkv.stride(0), _p(cache_k), _p(cache_v), _p(key_valid), _p(o), o.stride(0),
+                            rows, H, HKV, hd, Tmax, _p(len_dev), scale, _stream())
     return o
 
 
@@ -553,8 +545,8 @@ def attn_prefill_cached(qkv, cache_k, cache_v, key_valid, S, P, H, HKV, hd, Tmax
         raise _l.UniGenHipError(f"attn_prefill_cached: caches must be contiguous [{rows}, {HKV}, {Tmax}, {hd}]")
     scale = 1.0 / math.sqrt(hd) if scale is None else scale
     o = out if out is not None else torch.empty((rows * S, H * hd), dtype=torch.bfloat16, device=qkv.device)
-    _l.check(_l.load().ug_attn_prefill_cached(_p(qkv), qkv.stride(0), _p(cache_k), _p(cache_v), _p(key_valid), _p(o), o.stride(0),
-                                              rows, S, P, H, HKV, hd, Tmax, scale, _stream()), "ug_attn_prefill_cached")
+    _l.api().ug_attn_prefill_cached(_p(qkv), qkv.stride(0), _p(cache_k), _p(cache_v), _p(key_valid), _p(o), o.stride(0),
+                                    rows, S, P, H, HKV, hd, Tmax, scale, _stream())
     return o
 
 
@@ -565,28 +557,26 @@ def skinny_linear(x, w, bias=None, resid=None):
     acc = torch.zeros((M, N), dtype=torch.float32, device=x.device)
     K = w.shape[1]
     if M <= 32 and K % 32 == 0:
-        _l.check(_l.load().ug_gemv_bf16(_p(x), x.stride(0), M, _p(w), w.stride(0), _p(acc), N, 1, N, K, _stream()), "ug_gemv_bf16")
+        _l.api().ug_gemv_bf16(_p(x), x.stride(0), M, _p(w), w.stride(0), _p(acc), N, 1, N, K, _stream())
     else:
         gemm(x, w, out=acc, epilogue=UG_EPI_F32, beta=1)
     out = None if resid is not None else torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    _l.check(_l.load().ug_skinny_finish(_p(acc), _p(bias), _p(out), _p(resid), M, N, 0 if resid is None else 1, _stream()),
-             "ug_skinny_finish")
+    _l.api().ug_skinny_finish(_p(acc), _p(bias), _p(out), _p(resid), M, N, 0 if resid is None else 1, _stream())
     return resid if resid is not None else out
 
 
 def gemv_acc_(x, w, acc):
     """acc[r, n] += sum_k x[r, k] w[n, k]; acc fp32 [rows, N] row-major (the decode accumulators)."""
     M, N, K = x.shape[0], w.shape[0], w.shape[1]
-    _l.check(_l.load().ug_gemv_bf16(_p(x), x.stride(0), M, _p(w), w.stride(0), _p(acc), acc.stride(0), 1, N, K, _stream()),
-             "ug_gemv_bf16")
+    _l.api().ug_gemv_bf16(_p(x), x.stride(0), M, _p(w), w.stride(0), _p(acc), acc.stride(0), 1, N, K, _stream())
     return acc
 
 
 def decode_finish_resid_norm_(acc, x, w, xn, eps, advance=None):
     """advance = (pos, len) device int32 scalars of the decode state: incremented by this launch (the step's last reader is done)"""
     pos, ln = advance if advance is not None else (None, None)
-    _l.check(_l.load().ug_decode_finish_resid_norm(_p(acc), acc.stride(0), _p(x), _p(w), _p(xn), x.shape[0], x.shape[1], eps,
-                                                   _p(pos), _p(ln), _stream()), "ug_decode_finish_resid_norm")
+    _l.api().ug_decode_finish_resid_norm(_p(acc), acc.stride(0), _p(x), _p(w), _p(xn), x.shape[0], x.shape[1], eps,
+                                         _p(pos), _p(ln), _stream())
     return xn
 
 
@@ -596,72 +586,68 @@ def _clr(t):
 
 def decode_gemv_(x, w, acc, zero0=None, zero1=None, ss_zero=None):
     """acc[r, n] += sum_k x[r, k] w[n, k] (bf16 operand) + the clears this launch carries."""
-    _l.check(_l.load().ug_decode_gemv(_p(x), x.stride(0), x.shape[0], _p(w), w.stride(0), _p(acc), acc.stride(0), w.shape[0],
-                                      w.shape[1], *_clr(zero0), *_clr(zero1), _p(ss_zero), _stream()), "ug_decode_gemv")
+    _l.api().ug_decode_gemv(_p(x), x.stride(0), x.shape[0], _p(w), w.stride(0), _p(acc), acc.stride(0), w.shape[0],
+                            w.shape[1], *_clr(zero0), *_clr(zero1), _p(ss_zero), _stream())
     return acc
 
 
 def decode_gemv_resid_norm_(x_in, pending, norm_w, x_out, ss_out, w, acc, zero0=None, zero1=None, ss_zero=None):
     """Projection whose operand is bf16(norm_w * (x_in + bf16round(pending))); x_out / ss_out receive the updated
     residual stream and its row sums of squares."""
-    _l.check(_l.load().ug_decode_gemv_resid_norm(_p(x_in), _p(pending), pending.stride(0), _p(norm_w), _p(x_out), _p(ss_out),
-                                                 x_in.shape[0], _p(w), w.stride(0), _p(acc), acc.stride(0), w.shape[0],
-                                                 w.shape[1], *_clr(zero0), *_clr(zero1), _p(ss_zero), _stream()),
-             "ug_decode_gemv_resid_norm")
+    _l.api().ug_decode_gemv_resid_norm(_p(x_in), _p(pending), pending.stride(0), _p(norm_w), _p(x_out), _p(ss_out),
+                                       x_in.shape[0], _p(w), w.stride(0), _p(acc), acc.stride(0), w.shape[0],
+                                       w.shape[1], *_clr(zero0), *_clr(zero1), _p(ss_zero), _stream())
     return acc
 
 
 def decode_gemv_swiglu_(gu_acc, ss_in, eps, norm_cols, w, acc, zero0=None, zero1=None, ss_zero=None):
     """Projection whose operand is SwiGLU of the raw gate/up accumulator scaled by the row's RMSNorm factor."""
-    _l.check(_l.load().ug_decode_gemv_swiglu(_p(gu_acc), gu_acc.stride(0), _p(ss_in), eps, norm_cols, gu_acc.shape[0], _p(w),
-                                             w.stride(0), _p(acc), acc.stride(0), w.shape[0], w.shape[1], *_clr(zero0),
-                                             *_clr(zero1), _p(ss_zero), _stream()), "ug_decode_gemv_swiglu")
+    _l.api().ug_decode_gemv_swiglu(_p(gu_acc), gu_acc.stride(0), _p(ss_in), eps, norm_cols, gu_acc.shape[0], _p(w),
+                                   w.stride(0), _p(acc), acc.stride(0), w.shape[0], w.shape[1], *_clr(zero0),
+                                   *_clr(zero1), _p(ss_zero), _stream())
     return acc
 
 
 def decode_sw_supported(hidden, inter, q_dim, head_dim):
     """whether the single-writer decode projections (include/unigen_hip.h: ug_decode_sw_*) are built for these sizes"""
-    return bool(_l.load().ug_decode_sw_supported(int(hidden), int(inter), int(q_dim), int(head_dim)))
+    return bool(_l.api().ug_decode_sw_supported(int(hidden), int(inter), int(q_dim), int(head_dim)))
 
 
 def decode_sw_resid_(x, w, h):
     """h[r, n] += float(bf16(sum_k x[r, k] w[n, k])) in place, one writer per element (o projection of a decode step)"""
-    _l.check(_l.load().ug_decode_sw_resid(_p(x), x.stride(0), x.shape[0], _p(w), w.stride(0), w.shape[0], w.shape[1], _p(h), _stream()),
-             "ug_decode_sw_resid")
+    _l.api().ug_decode_sw_resid(_p(x), x.stride(0), x.shape[0], _p(w), w.stride(0), w.shape[0], w.shape[1], _p(h), _stream())
     return h
 
 
 def decode_sw_kblock_(x, w, acc, zero0=None, zero1=None, ss_zero=None):
     """acc[r, n] += sum_k x[r, k] w[n, k] in k-blocks of 1 792 (one atomic per element and k-block) + the clears this launch carries"""
-    _l.check(_l.load().ug_decode_sw_kblock(_p(x), x.stride(0), x.shape[0], _p(w), w.stride(0), _p(acc), acc.stride(0), w.shape[0],
-                                           w.shape[1], *_clr(zero0), *_clr(zero1), _p(ss_zero), _stream()), "ug_decode_sw_kblock")
+    _l.api().ug_decode_sw_kblock(_p(x), x.stride(0), x.shape[0], _p(w), w.stride(0), _p(acc), acc.stride(0), w.shape[0],
+                                 w.shape[1], *_clr(zero0), *_clr(zero1), _p(ss_zero), _stream())
     return acc
 
 
 def decode_sw_gate_up_(h, norm_w, eps, w, act, pend=None, x_out=None):
     """act = bf16(bf16(silu(gate)) * up) with gate | up = Linear(RMSNorm(h [+ bf16round(pend)])); w = [2 I, H], gate rows first"""
-    _l.check(_l.load().ug_decode_sw_gate_up(_p(h), _p(pend), pend.stride(0) if pend is not None else 0, _p(x_out), _p(norm_w), eps,
-                                            h.shape[0], h.shape[1], _p(w), w.stride(0), w.shape[0] // 2, _p(act), act.stride(0), _stream()),
-             "ug_decode_sw_gate_up")
+    _l.api().ug_decode_sw_gate_up(_p(h), _p(pend), pend.stride(0) if pend is not None else 0, _p(x_out), _p(norm_w), eps,
+                                  h.shape[0], h.shape[1], _p(w), w.stride(0), w.shape[0] // 2, _p(act), act.stride(0), _stream())
     return act
 
 
 def decode_sw_head_(h, norm_w, eps, w, logits, pend=None, x_out=None, advance=None):
     """logits fp32 [R, N] = Linear(RMSNorm(h [+ bf16round(pend)])) for the N rows `w` of the tied embedding; advance = (pos, len)"""
     pos, ln = advance if advance is not None else (None, None)
-    _l.check(_l.load().ug_decode_sw_head(_p(h), _p(pend), pend.stride(0) if pend is not None else 0, _p(x_out), _p(norm_w), eps,
-                                         h.shape[0], h.shape[1], _p(w), w.stride(0), w.shape[0], _p(logits), logits.stride(0),
-                                         _p(pos), _p(ln), _stream()), "ug_decode_sw_head")
+    _l.api().ug_decode_sw_head(_p(h), _p(pend), pend.stride(0) if pend is not None else 0, _p(x_out), _p(norm_w), eps,
+                               h.shape[0], h.shape[1], _p(w), w.stride(0), w.shape[0], _p(logits), logits.stride(0),
+                               _p(pos), _p(ln), _stream())
     return logits
 
 
 def attn_decode_fused(acc_qkv, ss_in, eps, norm_cols, bias, cos, sin, pos_dev, cache_k, cache_v, key_valid, out, H, HKV, hd, Tmax,
                       scale=None):
     scale = 1.0 / math.sqrt(hd) if scale is None else scale
-    _l.check(_l.load().ug_attn_decode_fused(_p(acc_qkv), acc_qkv.stride(0), _p(ss_in), eps, norm_cols, _p(bias), _p(cos), _p(sin),
-                                            _p(pos_dev), _p(cache_k), _p(cache_v), _p(key_valid), _p(out), out.stride(0),
-                                            acc_qkv.shape[0], H, HKV, hd, Tmax, cos.shape[0], scale, _stream()),
-             "ug_attn_decode_fused")
+    _l.api().ug_attn_decode_fused(_p(acc_qkv), acc_qkv.stride(0), _p(ss_in), eps, norm_cols, _p(bias), _p(cos), _p(sin),
+                                  _p(pos_dev), _p(cache_k), _p(cache_v), _p(key_valid), _p(out), out.stride(0),
+                                  acc_qkv.shape[0], H, HKV, hd, Tmax, cos.shape[0], scale, _stream())
     return out
 
 
@@ -686,15 +672,14 @@ def skinny_linear_ord(x, w, bias=None, resid=None, out_f32=None):
         raise _l.UniGenHipError(f"skinny_linear_ord: K={K} must be a multiple of 32")
     S = ord_slices(K)
     parts = torch.empty((S, M, N), dtype=torch.float32, device=x.device)
-    L = _l.load()
+    L = _l.api()
     for r0 in range(0, M, ORD_ROW_BLOCK):
         r1 = min(M, r0 + ORD_ROW_BLOCK)
-        _l.check(L.ug_gemv_bf16_ord(_p(x[r0:r1]), x.stride(0), r1 - r0, _p(w), w.stride(0), _p(parts[:, r0:r1]), N, M * N, N, K, _stream()),
-                 "ug_gemv_bf16_ord")
+        L.ug_gemv_bf16_ord(_p(x[r0:r1]), x.stride(0), r1 - r0, _p(w), w.stride(0), _p(parts[:, r0:r1]), N, M * N, N, K, _stream())
     out = None
     if resid is None and out_f32 is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    _l.check(L.ug_skinny_finish_ord(_p(parts), S, M * N, _p(bias), _p(out), _p(out_f32), _p(resid), M, N, _stream()), "ug_skinny_finish_ord")
+    L.ug_skinny_finish_ord(_p(parts), S, M * N, _p(bias), _p(out), _p(out_f32), _p(resid), M, N, _stream())
     return out if out is not None else (resid if resid is not None else out_f32)
 
 
@@ -702,9 +687,9 @@ def decode_gemv_resid_norm_ord_(x_in, pend_parts, norm_w, x_out, ss_part, w, par
     """ordered q/k/v launch: operand = bf16(norm_w * (x_in + bf16round(sum of the pending slots))) (pend_parts [P, R, ld] or None),
     partials into part [slabs, R, N], row sums of squares into ss_part [slabs, 32]"""
     npend = 0 if pend_parts is None else pend_parts.shape[0]
-    _l.check(_l.load().ug_decode_gemv_resid_norm_ord(_p(x_in), _p(pend_parts), pend_parts.stride(1) if npend else 0, npend, _p(norm_w), _p(x_out),
-                                                     _p(ss_part), x_in.shape[0], _p(w), w.stride(0), _p(part), part.stride(1), w.shape[0],
-                                                     w.shape[1], _stream()), "ug_decode_gemv_resid_norm_ord")
+    _l.api().ug_decode_gemv_resid_norm_ord(_p(x_in), _p(pend_parts), pend_parts.stride(1) if npend else 0, npend, _p(norm_w), _p(x_out),
+                                           _p(ss_part), x_in.shape[0], _p(w), w.stride(0), _p(part), part.stride(1), w.shape[0],
+                                           w.shape[1], _stream())
     return part
 
 
@@ -712,25 +697,24 @@ def attn_decode_fused_ord(qkv_part, ss_part, eps, norm_cols, bias, cos, sin, pos
                           scale=None):
     """attn_decode_fused fed by the ordered q/k/v slots qkv_part [6, R, N] / ss_part [6, 32]"""
     scale = 1.0 / math.sqrt(hd) if scale is None else scale
-    _l.check(_l.load().ug_attn_decode_fused_ord(_p(qkv_part), qkv_part.stride(1), qkv_part.shape[0], _p(ss_part), eps, norm_cols, _p(bias),
-                                                _p(cos), _p(sin), _p(pos_dev), _p(cache_k), _p(cache_v), _p(key_valid), _p(out),
-                                                out.stride(0), qkv_part.shape[1], H, HKV, hd, Tmax, cos.shape[0], scale, _stream()),
-             "ug_attn_decode_fused_ord")
+    _l.api().ug_attn_decode_fused_ord(_p(qkv_part), qkv_part.stride(1), qkv_part.shape[0], _p(ss_part), eps, norm_cols, _p(bias),
+                                      _p(cos), _p(sin), _p(pos_dev), _p(cache_k), _p(cache_v), _p(key_valid), _p(out),
+                                      out.stride(0), qkv_part.shape[1], H, HKV, hd, Tmax, cos.shape[0], scale, _stream())
     return out
 
 
 def decode_sw_kblock_ord_(x, w, part):
     """part[b, r, n] = sum over k-block b (1 792 wide) of x[r, k] w[n, k]: one slot per k-block, plain stores"""
-    _l.check(_l.load().ug_decode_sw_kblock_ord(_p(x), x.stride(0), x.shape[0], _p(w), w.stride(0), _p(part), part.stride(1), w.shape[0],
-                                               w.shape[1], _stream()), "ug_decode_sw_kblock_ord")
+    _l.api().ug_decode_sw_kblock_ord(_p(x), x.stride(0), x.shape[0], _p(w), w.stride(0), _p(part), part.stride(1), w.shape[0],
+                                     w.shape[1], _stream())
     return part
 
 
 def decode_finish_resid_norm_ord_(parts, x, w, xn, eps, advance=None):
     """x += bf16round(sum of the slots parts [P, R, ld]) in place; xn = bf16(rmsnorm(x) * w) if xn is given; advance = (pos, len)"""
     pos, ln = advance if advance is not None else (None, None)
-    _l.check(_l.load().ug_decode_finish_resid_norm_ord(_p(parts), parts.stride(1), parts.shape[0], _p(x), _p(w), _p(xn), x.shape[0], x.shape[1],
-                                                       eps, _p(pos), _p(ln), _stream()), "ug_decode_finish_resid_norm_ord")
+    _l.api().ug_decode_finish_resid_norm_ord(_p(parts), parts.stride(1), parts.shape[0], _p(x), _p(w), _p(xn), x.shape[0], x.shape[1],
+                                             eps, _p(pos), _p(ln), _stream())
     return xn
 
 
@@ -763,16 +747,16 @@ def maskgit_step(logits, N, n, cfg, guidance_scale, u_sample, u_conf, cur_ids, m
     masking = torch.empty((N, n), dtype=torch.uint8, device=dev) if want_masking else None
     cur_ids = cur_ids.to(torch.int64).contiguous()
     if plain:
-        _l.check(_l.load().ug_maskgit_step(_p(logits), logits.stride(0), V, N, n, int(bool(cfg)), float(guidance_scale),
-                                           _p(u_sample.contiguous()), _p(u_conf.contiguous()), _p(cur_ids), int(mask_id),
-                                           int(id_offset), int(mask_len_sched), float(temperature), _p(sampled), _p(sel), _p(next_cur),
-                                           _p(next_ids), _p(masking), _stream()), "ug_maskgit_step")
+        _l.api().ug_maskgit_step(_p(logits), logits.stride(0), V, N, n, int(bool(cfg)), float(guidance_scale),
+                                 _p(u_sample.contiguous()), _p(u_conf.contiguous()), _p(cur_ids), int(mask_id),
+                                 int(id_offset), int(mask_len_sched), float(temperature), _p(sampled), _p(sel), _p(next_cur),
+                                 _p(next_ids), _p(masking), _stream())
     else:
-        _l.check(_l.load().ug_maskgit_step_ex(_p(logits), logits.stride(0), V, N, n, int(bool(cfg)), float(guidance_scale),
-                                              _p(u_sample.contiguous()), _p(u_conf.contiguous()), _p(cur_ids), int(mask_id),
-                                              int(id_offset), int(mask_len_sched), float(temperature), float(sample_temperature),
-                                              int(top_k), float(top_p), float(min_p), _p(sampled), _p(sel), _p(next_cur), _p(next_ids),
-                                              _p(masking), _p(logp), _p(stats), _stream()), "ug_maskgit_step_ex")
+        _l.api().ug_maskgit_step_ex(_p(logits), logits.stride(0), V, N, n, int(bool(cfg)), float(guidance_scale),
+                                    _p(u_sample.contiguous()), _p(u_conf.contiguous()), _p(cur_ids), int(mask_id),
+                                    int(id_offset), int(mask_len_sched), float(temperature), float(sample_temperature),
+                                    int(top_k), float(top_p), float(min_p), _p(sampled), _p(sel), _p(next_cur), _p(next_ids),
+                                    _p(masking), _p(logp), _p(stats), _stream())
     return (sampled, next_cur, next_ids, masking.bool()) if want_masking else (sampled, next_cur, next_ids)
 
 
@@ -783,8 +767,8 @@ def maskgit_train_mask(tokens, scores, num_masked, mask_id, ignore_id=-100):
     B, n = tokens.shape
     tokens = tokens.to(torch.int64).contiguous()
     ids, labels = torch.empty_like(tokens), torch.empty_like(tokens)
-    _l.check(_l.load().ug_maskgit_train_mask(_p(tokens), _p(scores.float().contiguous()), _p(num_masked.float().contiguous()), B, n,
-                                             int(mask_id), int(ignore_id), _p(ids), _p(labels), _stream()), "ug_maskgit_train_mask")
+    _l.api().ug_maskgit_train_mask(_p(tokens), _p(scores.float().contiguous()), _p(num_masked.float().contiguous()), B, n,
+                                   int(mask_id), int(ignore_id), _p(ids), _p(labels), _stream())
     return ids, labels
 
 
@@ -797,9 +781,9 @@ def ar_sample_(acc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_d
             int(pos0), int(nsteps), _p(embed_master), embed_master.stride(0), embed_master.shape[1], int(id_offset), _p(tok),
             _p(out_tokens), _p(x))
     if logp is None:
-        _l.check(_l.load().ug_ar_sample(*args, _stream()), "ug_ar_sample")
+        _l.api().ug_ar_sample(*args, _stream())
     else:
-        _l.check(_l.load().ug_ar_sample_logp(*args, _p(_logp_buffer(logp, (bsz, int(nsteps), 2))), _stream()), "ug_ar_sample_logp")
+        _l.api().ug_ar_sample_logp(*args, _p(_logp_buffer(logp, (bsz, int(nsteps), 2))), _stream())
 
 
 def ar_sample_filtered_(acc, bsz, V, guidance_scale, temperature, greedy, uniforms, pos_dev, pos0, nsteps, embed_master, id_offset, tok,
@@ -811,10 +795,9 @@ def ar_sample_filtered_(acc, bsz, V, guidance_scale, temperature, greedy, unifor
             int(pos0), int(nsteps), _p(embed_master), embed_master.stride(0), embed_master.shape[1], int(id_offset), _p(tok),
             _p(out_tokens), _p(x), int(top_k), float(top_p), float(min_p), _p(stats))
     if logp is None:
-        _l.check(_l.load().ug_ar_sample_filtered(*args, _stream()), "ug_ar_sample_filtered")
+        _l.api().ug_ar_sample_filtered(*args, _stream())
     else:
-        _l.check(_l.load().ug_ar_sample_filtered_logp(*args, _p(_logp_buffer(logp, (bsz, int(nsteps), 2))), _stream()),
-                 "ug_ar_sample_filtered_logp")
+        _l.api().ug_ar_sample_filtered_logp(*args, _p(_logp_buffer(logp, (bsz, int(nsteps), 2))), _stream())
 
 
 def _logp_buffer(logp, shape, what="logp"):
@@ -844,9 +827,10 @@ def text_state_reset_(state, rows):
 
 def text_sample_workspace(rows, device):
     """the zeroed int32 workspace of ug_text_sample for `rows` rows (every call leaves it zeroed)"""
-    n = _l.load().ug_text_sample_workspace_ints(int(rows))
+    ints = _l.api().ug_text_sample_workspace_ints
+    n = ints(int(rows))
     if n <= 0:
-        _l.check(n, "ug_text_sample_workspace_ints")
+        _l.check(n, ints.__name__)
     return torch.zeros(n, dtype=torch.int32, device=device)
 
 
@@ -864,9 +848,9 @@ def text_pick_(logits, V, state, nsteps, embed_master, tok, out_tokens, x, clear
     args = (_p(logits), logits.stride(0), logits.shape[0], int(V), int(bool(clear)), *_text_out(stop_ids, pad_id, embed_master), _p(state),
             int(nsteps), _p(tok), _p(out_tokens), _p(lengths), _p(x))
     if logp is None:
-        _l.check(_l.load().ug_text_pick(*args, _stream()), "ug_text_pick")
+        _l.api().ug_text_pick(*args, _stream())
     else:
-        _l.check(_l.load().ug_text_pick_logp(*args, _p(_logp_buffer(logp, (logits.shape[0], int(nsteps)))), _stream()), "ug_text_pick_logp")
+        _l.api().ug_text_pick_logp(*args, _p(_logp_buffer(logp, (logits.shape[0], int(nsteps)))), _stream())
 
 
 def text_sample_(logits, V, state, nsteps, embed_master, tok, out_tokens, x, uniforms, workspace, temperature=1.0, top_k=0, top_p=1.0,
@@ -880,9 +864,9 @@ def text_sample_(logits, V, state, nsteps, embed_master, tok, out_tokens, x, uni
             _p(uniforms), _p(workspace), _p(stats), *_text_out(stop_ids, pad_id, embed_master), _p(state), int(nsteps), _p(tok),
             _p(out_tokens), _p(lengths), _p(x))
     if logp is None:
-        _l.check(_l.load().ug_text_sample(*args, _stream()), "ug_text_sample")
+        _l.api().ug_text_sample(*args, _stream())
     else:
-        _l.check(_l.load().ug_text_sample_logp(*args, _p(_logp_buffer(logp, (logits.shape[0], int(nsteps)))), _stream()), "ug_text_sample_logp")
+        _l.api().ug_text_sample_logp(*args, _p(_logp_buffer(logp, (logits.shape[0], int(nsteps)))), _stream())
 
 
 def text_seen(rows, V, device):
@@ -904,8 +888,8 @@ def text_seen_mark_(seen, ids, V, valid=None):
     _need_cuda(seen, ids)
     if seen.shape[0] != ids.shape[0] or seen.stride(1) != 1:
         raise _l.UniGenHipError(f"text_seen_mark_: seen {tuple(seen.shape)} against ids {tuple(ids.shape)}")
-    _l.check(_l.load().ug_text_seen_mark(_p(seen), seen.stride(0), _p(ids), ids.stride(0), ids.shape[0], ids.shape[1], _p(valid), int(V),
-                                         _stream()), "ug_text_seen_mark")
+    _l.api().ug_text_seen_mark(_p(seen), seen.stride(0), _p(ids), ids.stride(0), ids.shape[0], ids.shape[1], _p(valid), int(V),
+                               _stream())
     return seen
 
 
@@ -916,8 +900,8 @@ def text_penalize_(logits, V, penalty, seen, tok=None):
     _need_cuda(logits, seen)
     if seen.shape[0] != logits.shape[0] or seen.stride(1) != 1 or logits.stride(1) != 1:
         raise _l.UniGenHipError(f"text_penalize_: seen {tuple(seen.shape)} against logits {tuple(logits.shape)}")
-    _l.check(_l.load().ug_text_penalize(_p(logits), logits.stride(0), logits.shape[0], int(V), float(penalty), _p(seen), seen.stride(0),
-                                        _p(tok), _stream()), "ug_text_penalize")
+    _l.api().ug_text_penalize(_p(logits), logits.stride(0), logits.shape[0], int(V), float(penalty), _p(seen), seen.stride(0),
+                              _p(tok), _stream())
 
 
 # the on-device loop's limits for the constraints (include/unigen_hip.h: ug_text_constrain, ug_text_stop_seq); the host loop has none
@@ -959,10 +943,10 @@ def text_constrain_(logits, V, state, out_tokens, bias=None, min_new=0, stop_ids
             hist.dtype == torch.int32 and hist_len.dtype == torch.int32 and hist.dim() == 2 and hist.shape[0] == R and hist.stride(1) == 1 and
             hist_len.is_contiguous() and hist_len.numel() == R)):
         raise _l.UniGenHipError("text_constrain_: hist int32 [R, ld_hist] and hist_len int32 [R] come together")
-    _l.check(_l.load().ug_text_constrain(_p(logits), logits.stride(0), R, int(V), _p(bias), 0 if bias is None else bias.shape[0], int(min_new),
-                                         _p(stop_ids), 0 if stop_ids is None else stop_ids.numel(), int(ngram), _p(hist),
-                                         0 if hist is None else hist.stride(0), _p(hist_len), _p(out_tokens), out_tokens.shape[1], _p(state),
-                                         _stream()), "ug_text_constrain")
+    _l.api().ug_text_constrain(_p(logits), logits.stride(0), R, int(V), _p(bias), 0 if bias is None else bias.shape[0], int(min_new),
+                               _p(stop_ids), 0 if stop_ids is None else stop_ids.numel(), int(ngram), _p(hist),
+                               0 if hist is None else hist.stride(0), _p(hist_len), _p(out_tokens), out_tokens.shape[1], _p(state),
+                               _stream())
 
 
 def text_stop_seq_(seq_ids, seq_off, out_tokens, state, lengths=None):
@@ -974,8 +958,8 @@ def text_stop_seq_(seq_ids, seq_off, out_tokens, state, lengths=None):
         raise _l.UniGenHipError("text_stop_seq_: int32 contiguous seq_ids, seq_off [ns + 1] and out_tokens [R, nsteps]")
     if lengths is not None and not (lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == out_tokens.shape[0]):
         raise _l.UniGenHipError("text_stop_seq_: lengths must be int32 [R]")
-    _l.check(_l.load().ug_text_stop_seq(_p(seq_ids), _p(seq_off), seq_off.numel() - 1, seq_ids.numel(), _p(out_tokens), out_tokens.shape[1],
-                                        out_tokens.shape[0], _p(state), _p(lengths), _stream()), "ug_text_stop_seq")
+    _l.api().ug_text_stop_seq(_p(seq_ids), _p(seq_off), seq_off.numel() - 1, seq_ids.numel(), _p(out_tokens), out_tokens.shape[1],
+                              out_tokens.shape[0], _p(state), _p(lengths), _stream())
 
 
 # ------------------------------------------------------------------------------------ loss
@@ -987,15 +971,15 @@ def ce_fwd(logits, V, labels, ignore_index=-100, want_logp=False):
     loss_row = torch.empty((R,), dtype=torch.float32, device=dev)
     logp = torch.empty((R,), dtype=torch.float32, device=dev) if want_logp else None
     lc = torch.empty((2,), dtype=torch.float32, device=dev)
-    _l.check(_l.load().ug_ce_fwd(_p(logits), ld, R, V, _p(labels), ignore_index, _p(lse), _p(loss_row), _p(logp),
-                                 _p(lc), _stream()), "ug_ce_fwd")
+    _l.api().ug_ce_fwd(_p(logits), ld, R, V, _p(labels), ignore_index, _p(lse), _p(loss_row), _p(logp),
+                       _p(lc), _stream())
     return lc, lse, loss_row, logp
 
 
 def ce_bwd_(logits, V, labels, lse, lc, gscale=None, ignore_index=-100, row_scale=None):
     R, ld = logits.shape[0], logits.stride(0)
-    _l.check(_l.load().ug_ce_bwd(_p(logits), ld, R, V, _p(labels), ignore_index, _p(lse), _p(lc), _p(gscale),
-                                 _p(row_scale), _stream()), "ug_ce_bwd")
+    _l.api().ug_ce_bwd(_p(logits), ld, R, V, _p(labels), ignore_index, _p(lse), _p(lc), _p(gscale),
+                       _p(row_scale), _stream())
     return logits
 
 
@@ -1005,9 +989,10 @@ HEAD_SCORE_WANT = ("lse", "best", "best_logit")
 
 def head_score_ws_bytes(R, V):
     """bytes of ug_head_score's workspace (csrc/head_score_plan.h): 16 per (row, 256-entry column tile) + 4 per row"""
-    n = _l.load().ug_head_score_ws_bytes(R, V)
+    ws_bytes = _l.api().ug_head_score_ws_bytes
+    n = ws_bytes(R, V)
     if n <= 0:
-        _l.check(n, "ug_head_score_ws_bytes")
+        _l.check(n, ws_bytes.__name__)
     return n
 
 
@@ -1038,8 +1023,8 @@ def head_score(x, W, V, labels, ignore_index=-100, want=("lse", "best")):
     out = {"lse": None, "best": None, "best_logit": None}
     for n in want:
         out[n] = torch.empty((R,), dtype=torch.int64 if n == "best" else torch.float32, device=dev)
-    _l.check(_l.load().ug_head_score(_p(x), x.stride(0), R, _p(W), W.stride(0), V, K, _p(labels), ignore_index, _p(ws), _p(logp),
-                                     _p(out["lse"]), _p(out["best"]), _p(out["best_logit"]), _stream()), "ug_head_score")
+    _l.api().ug_head_score(_p(x), x.stride(0), R, _p(W), W.stride(0), V, K, _p(labels), ignore_index, _p(ws), _p(logp),
+                           _p(out["lse"]), _p(out["best"]), _p(out["best_logit"]), _stream())
     return (logp,) + tuple(out[n] for n in want)
 
 
@@ -1070,14 +1055,14 @@ def find_bf16_mirror(ptr, numel):
 # ------------------------------------------------------------------------------------ optimizer
 def adamw_flat_(p, g, m, v, p_bf16, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, max_blocks=0):
     """max_blocks > 0: the small-grid, register-lean form used beside MFMA-bound kernels (include/unigen_hip.h: ug_adamw_flat)."""
-    _l.check(_l.load().ug_adamw_flat(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), lr, beta1, beta2, eps, wd,
-                                     step, grad_scale, max_blocks, _stream()), "ug_adamw_flat")
+    _l.api().ug_adamw_flat(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), lr, beta1, beta2, eps, wd,
+                           step, grad_scale, max_blocks, _stream())
 
 
 def adamw_flat_dev_(p, g, m, v, p_bf16, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, grad_factor=None, max_blocks=0):
     """adamw_flat_ with the gradients multiplied by grad_scale * grad_factor[0] (a device fp32 scalar, e.g. clip_finish's factor)."""
-    _l.check(_l.load().ug_adamw_flat_dev(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), lr, beta1, beta2, eps, wd,
-                                         step, grad_scale, _p(grad_factor), max_blocks, _stream()), "ug_adamw_flat_dev")
+    _l.api().ug_adamw_flat_dev(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), lr, beta1, beta2, eps, wd,
+                               step, grad_scale, _p(grad_factor), max_blocks, _stream())
 
 
 # ------------------------------------------------------------------------------------ gradient-norm clipping
@@ -1091,19 +1076,19 @@ def sumsq_spans(spans, partials, blocks=None, accum=0):
     blocks = SUMSQ_BLOCKS if blocks is None else int(blocks)
     if partials.dtype != torch.float64 or partials.numel() < blocks:
         raise _l.UniGenHipError("sumsq_spans: the partial buffer needs `blocks` fp64 values")
-    _l.check(_l.load().ug_sumsq_spans_f32(_p(spans), spans.shape[0], _p(partials), blocks, accum, _stream()), "ug_sumsq_spans_f32")
+    _l.api().ug_sumsq_spans_f32(_p(spans), spans.shape[0], _p(partials), blocks, accum, _stream())
     return partials
 
 
 def clip_finish(partials, n_partials, max_norm, result, grad_scale=1.0):
     """result (fp32 [8]): norm, clip coefficient, grad_scale * coefficient, non-finite flag, the fp64 sum (include/unigen_hip.h)."""
-    _l.check(_l.load().ug_clip_finish(_p(partials), int(n_partials), float(max_norm), float(grad_scale), _p(result), _stream()), "ug_clip_finish")
+    _l.api().ug_clip_finish(_p(partials), int(n_partials), float(max_norm), float(grad_scale), _p(result), _stream())
     return result
 
 
 def scale_spans_(spans, coef, blocks=0):
     """g *= coef[0] over the span table; a device-side 1.0 returns without touching memory."""
-    _l.check(_l.load().ug_scale_spans_f32(_p(spans), spans.shape[0], _p(coef), int(blocks), _stream()), "ug_scale_spans_f32")
+    _l.api().ug_scale_spans_f32(_p(spans), spans.shape[0], _p(coef), int(blocks), _stream())
 
 
 # ------------------------------------------------------------------------------------ tokenizer (fp32 NHWC)
@@ -1126,7 +1111,7 @@ def split_conv_weight(wp):
     tensor's max|w| in the 8 trailing elements)."""
     taps, cin, cout_pad = wp.shape
     ws = torch.empty(2 * taps * round_up(cin, 32) * cout_pad + 8, dtype=torch.float16, device=wp.device)
-    _l.check(_l.load().ug_conv_split_weights(_p(wp), _p(ws), taps, cin, cout_pad, _stream()), "ug_conv_split_weights")
+    _l.api().ug_conv_split_weights(_p(wp), _p(ws), taps, cin, cout_pad, _stream())
     return ws
 
 
@@ -1155,10 +1140,10 @@ def amax(x2d):
         # slot nobody clears (the bound would only ever grow).  Under capture the bound gets its own scalar and the launch that
         # carries a memset node (ug_amax_f32), so every replay starts from zero.
         out = torch.empty(1, dtype=torch.float32, device=x2d.device)
-        _l.check(_l.load().ug_amax_f32(_p(x2d), rows, cols, ld, _p(out), _stream()), "ug_amax_f32")
+        _l.api().ug_amax_f32(_p(x2d), rows, cols, ld, _p(out), _stream())
         return out
     out = _amax_slot(x2d.device)
-    _l.check(_l.load().ug_amax_f32_into_zeroed(_p(x2d), rows, cols, ld, _p(out), _stream()), "ug_amax_f32")
+    _l.api().ug_amax_f32_into_zeroed(_p(x2d), rows, cols, ld, _p(out), _stream())
     return out
 
 
@@ -1199,14 +1184,14 @@ def conv2d_nhwc(x, wp, cout_pad, bias, cout, ksize, *, stride=1, pad=None, resid
             x_amax = amax(x.view(-1, Cin))
         if out_stats is not None and (out_stats.dtype != torch.float64 or out_stats.numel() != B * out_groups * 2 + 1):
             raise _l.UniGenHipError("conv2d_nhwc: out_stats must be a zeroed fp64 buffer of B * groups * 2 + 1 elements (gn_stats_slots)")
-        _l.check(_l.load().ug_conv2d_split(_p(x), _p(x_amax), _p(w_split), _p(bias), _p(residual), _p(y), B, H, W, Cin, cout,
-                                           cout_pad, ksize, stride, pt, pl, Ho, Wo, int(upsample), _p(out_stats),
-                                           int(out_groups) if out_stats is not None else 0, _stream()), "ug_conv2d_split")
+        _l.api().ug_conv2d_split(_p(x), _p(x_amax), _p(w_split), _p(bias), _p(residual), _p(y), B, H, W, Cin, cout,
+                                 cout_pad, ksize, stride, pt, pl, Ho, Wo, int(upsample), _p(out_stats),
+                                 int(out_groups) if out_stats is not None else 0, _stream())
         return y
     if out_stats is not None:
         raise _l.UniGenHipError("conv2d_nhwc: out_stats needs the split path (w_split)")
-    _l.check(_l.load().ug_conv2d_f32(_p(x), _p(wp), _p(bias), _p(residual), _p(y), B, H, W, Cin, cout, cout_pad, ksize,
-                                     stride, pt, pl, Ho, Wo, int(upsample), _stream()), "ug_conv2d_f32")
+    _l.api().ug_conv2d_f32(_p(x), _p(wp), _p(bias), _p(residual), _p(y), B, H, W, Cin, cout, cout_pad, ksize,
+                           stride, pt, pl, Ho, Wo, int(upsample), _stream())
     return y
 
 
@@ -1218,15 +1203,15 @@ def gemm_f32(a, b, *, b_is_nk, M, N, K, batch=1, lda=None, ldb=None, stride_a=0,
         out = torch.empty((batch, M, N), dtype=torch.float32, device=a.device)
     ldc = N if ldc is None else ldc
     stride_c = M * N if stride_c is None else stride_c
-    _l.check(_l.load().ug_gemm_f32(_p(a), lda, stride_a, _p(b), ldb, stride_b, int(b_is_nk), _p(out), ldc, stride_c, M, N,
-                                   K, batch, alpha, _stream()), "ug_gemm_f32")
+    _l.api().ug_gemm_f32(_p(a), lda, stride_a, _p(b), ldb, stride_b, int(b_is_nk), _p(out), ldc, stride_c, M, N,
+                         K, batch, alpha, _stream())
     return out
 
 
 def gemm_f32_nested(a, b, out, *, b_is_nk, M, N, K, batch_in, batch_out, lda, ldb, ldc, sa, sb, sc, alpha=1.0):
     """`gemm_f32` over a two-level batch (inner, outer); sa / sb / sc = (inner stride, outer stride) in elements."""
-    _l.check(_l.load().ug_gemm_f32_nested(_p(a), lda, sa[0], sa[1], _p(b), ldb, sb[0], sb[1], int(b_is_nk), _p(out), ldc,
-                                          sc[0], sc[1], M, N, K, batch_in, batch_out, alpha, _stream()), "ug_gemm_f32_nested")
+    _l.api().ug_gemm_f32_nested(_p(a), lda, sa[0], sa[1], _p(b), ldb, sb[0], sb[1], int(b_is_nk), _p(out), ldc,
+                                sc[0], sc[1], M, N, K, batch_in, batch_out, alpha, _stream())
     return out
 
 
@@ -1235,8 +1220,8 @@ def groupnorm_swish(x, gamma, beta, *, groups=32, eps=1e-6, swish=True):
     B, H, W, C = x.shape
     y = torch.empty_like(x)
     ws = torch.empty((B, groups, 2), dtype=torch.float64, device=x.device)
-    _l.check(_l.load().ug_groupnorm_swish(_p(x), _p(gamma), _p(beta), _p(y), _p(ws), B, H * W, C, groups, eps,
-                                          int(swish), _stream()), "ug_groupnorm_swish")
+    _l.api().ug_groupnorm_swish(_p(x), _p(gamma), _p(beta), _p(y), _p(ws), B, H * W, C, groups, eps,
+                                int(swish), _stream())
     return y
 
 
@@ -1246,8 +1231,7 @@ def groupnorm_stats(x, *, groups=32, eps=1e-6):
     B, H, W, C = x.shape
     ws = torch.empty((B, groups, 2), dtype=torch.float64, device=x.device)
     mr = torch.empty((B, groups, 2), dtype=torch.float32, device=x.device)
-    _l.check(_l.load().ug_groupnorm_stats(_p(x), _p(ws), _p(mr), B, H * W, C, groups, eps, _stream()),
-             "ug_groupnorm_stats")
+    _l.api().ug_groupnorm_stats(_p(x), _p(ws), _p(mr), B, H * W, C, groups, eps, _stream())
     return mr
 
 
@@ -1279,7 +1263,7 @@ def groupnorm_finalize(stats, B, HW, C, *, groups=32, eps=1e-6):
     if stats.numel() != B * groups * 2 + 1:
         raise _l.UniGenHipError("groupnorm_finalize: stats buffer does not match B x groups")
     mr = torch.empty((B, groups, 2), dtype=torch.float32, device=stats.device)
-    _l.check(_l.load().ug_groupnorm_finalize(_p(stats), _p(mr), B, HW, C, groups, eps, _stream()), "ug_groupnorm_finalize")
+    _l.api().ug_groupnorm_finalize(_p(stats), _p(mr), B, HW, C, groups, eps, _stream())
     return mr
 
 
@@ -1302,17 +1286,16 @@ def conv3x3_nhwc(x, w_split, cout_pad, bias, cout, *, residual=None, gn=None, x_
         x_amax = amax_const(gn_bound, x.device) if gn is not None else amax(x.view(-1, Cin))
     if out_stats is not None and (out_stats.dtype != torch.float64 or out_stats.numel() != B * out_groups * 2 + 1):
         raise _l.UniGenHipError("conv3x3_nhwc: out_stats must be a zeroed fp64 buffer of B * groups * 2 + 1 elements (gn_stats_slots)")
-    _l.check(_l.load().ug_conv3x3_split(_p(x), _p(x_amax), _p(w_split), _p(bias), _p(residual), _p(y), B, H, W, Cin, cout,
-                                        cout_pad, _p(mr), _p(ga), _p(be), groups, int(swish), _p(out_stats),
-                                        int(out_groups) if out_stats is not None else 0, _stream()), "ug_conv3x3_split")
+    _l.api().ug_conv3x3_split(_p(x), _p(x_amax), _p(w_split), _p(bias), _p(residual), _p(y), B, H, W, Cin, cout,
+                              cout_pad, _p(mr), _p(ga), _p(be), groups, int(swish), _p(out_stats),
+                              int(out_groups) if out_stats is not None else 0, _stream())
     return y
 
 
 def softmax_rows_(x2d, scale, cols=None):
     """in-place row softmax of scale*x over the first `cols` columns of a 2-D fp32 tensor (row stride = .stride(0))."""
     cols = x2d.shape[1] if cols is None else cols
-    _l.check(_l.load().ug_softmax_rows_f32(_p(x2d), x2d.shape[0], cols, x2d.stride(0), scale, _stream()),
-             "ug_softmax_rows_f32")
+    _l.api().ug_softmax_rows_f32(_p(x2d), x2d.shape[0], cols, x2d.stride(0), scale, _stream())
     return x2d
 
 
@@ -1322,9 +1305,9 @@ def linear_f32(x, W, bias=None, residual=None, act=0, out=None, M=None):
     N, K = W.shape
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    _l.check(_l.load().ug_linear_f32(_p(x), x.stride(0), _p(W), W.stride(0), _p(bias), _p(residual),
-                                     residual.stride(0) if residual is not None else 0, _p(out), out.stride(0), M, N, K, act,
-                                     _stream()), "ug_linear_f32")
+    _l.api().ug_linear_f32(_p(x), x.stride(0), _p(W), W.stride(0), _p(bias), _p(residual),
+                           residual.stride(0) if residual is not None else 0, _p(out), out.stride(0), M, N, K, act,
+                           _stream())
     return out
 
 
@@ -1346,9 +1329,9 @@ def linear_split(x, w_split, n_pad, N, bias=None, residual=None, act=0, out=None
         out = torch.empty((M, N), dtype=torch.float32, device=x.device)
     if x_amax is None:
         x_amax = amax(x[:M])
-    _l.check(_l.load().ug_linear_split(_p(x), x.stride(0), _p(x_amax), _p(w_split), _p(bias), _p(residual),
-                                       residual.stride(0) if residual is not None else 0, _p(out), out.stride(0), M, N, K,
-                                       n_pad, act, _stream()), "ug_linear_split")
+    _l.api().ug_linear_split(_p(x), x.stride(0), _p(x_amax), _p(w_split), _p(bias), _p(residual),
+                             residual.stride(0) if residual is not None else 0, _p(out), out.stride(0), M, N, K,
+                             n_pad, act, _stream())
     return out
 
 
@@ -1358,43 +1341,41 @@ def siglip_attn(qkv, out, B, T, H, hd, scale, qkv_amax=None):
     _need_cuda(qkv, out)
     if qkv_amax is None:
         qkv_amax = amax(qkv[:B * T])
-    _l.check(_l.load().ug_siglip_attn_f32(_p(qkv), qkv.stride(0), _p(qkv_amax), _p(out), out.stride(0), B, T, H, hd, float(scale),
-                                          _stream()), "ug_siglip_attn_f32")
+    _l.api().ug_siglip_attn_f32(_p(qkv), qkv.stride(0), _p(qkv_amax), _p(out), out.stride(0), B, T, H, hd, float(scale),
+                                _stream())
     return out
 
 
 def layernorm_f32(x2d, gamma, beta, eps):
     y = torch.empty_like(x2d)
-    _l.check(_l.load().ug_layernorm_f32(_p(x2d), _p(gamma), _p(beta), _p(y), x2d.shape[0], x2d.shape[1], eps, _stream()),
-             "ug_layernorm_f32")
+    _l.api().ug_layernorm_f32(_p(x2d), _p(gamma), _p(beta), _p(y), x2d.shape[0], x2d.shape[1], eps, _stream())
     return y
 
 
 def layernorm_bwd_f32(dy, x, gamma, eps, dgamma, dbeta, dres_in=None):
     """dx = [dres_in +] LayerNorm'(dy); dgamma / dbeta (fp32 [cols]) accumulate."""
     dx = torch.empty_like(x)
-    _l.check(_l.load().ug_layernorm_bwd_f32(_p(dy), _p(x), _p(gamma), _p(dres_in), _p(dx), _p(dgamma), _p(dbeta), x.shape[0], x.shape[1],
-                                            eps, _stream()), "ug_layernorm_bwd_f32")
+    _l.api().ug_layernorm_bwd_f32(_p(dy), _p(x), _p(gamma), _p(dres_in), _p(dx), _p(dgamma), _p(dbeta), x.shape[0], x.shape[1],
+                                  eps, _stream())
     return dx
 
 
 def gelu_tanh_f32(pre, dy=None):
     """gelu_pytorch_tanh(pre), or dy * gelu'(pre) when dy is given; fp32."""
     out = torch.empty_like(pre)
-    _l.check(_l.load().ug_gelu_tanh_f32(_p(pre), _p(dy), _p(out), pre.numel(), _stream()), "ug_gelu_tanh_f32")
+    _l.api().ug_gelu_tanh_f32(_p(pre), _p(dy), _p(out), pre.numel(), _stream())
     return out
 
 
 def softmax_bwd_rows_(P2d, dP2d, scale, cols):
     """in place on dP2d: dS = scale * P * (dP - rowsum(dP * P)) over the first `cols` columns, padding columns zeroed"""
-    _l.check(_l.load().ug_softmax_bwd_rows_f32(_p(P2d), _p(dP2d), P2d.shape[0], cols, P2d.stride(0), scale, _stream()),
-             "ug_softmax_bwd_rows_f32")
+    _l.api().ug_softmax_bwd_rows_f32(_p(P2d), _p(dP2d), P2d.shape[0], cols, P2d.stride(0), scale, _stream())
     return dP2d
 
 
 def colsum_f32_(x2d, out):
     """out[c] += sum_r x2d[r, c] (fp32)"""
-    _l.check(_l.load().ug_colsum_f32(_p(x2d), x2d.stride(0), _p(out), x2d.shape[0], x2d.shape[1], _stream()), "ug_colsum_f32")
+    _l.api().ug_colsum_f32(_p(x2d), x2d.stride(0), _p(out), x2d.shape[0], x2d.shape[1], _stream())
     return out
 
 
@@ -1407,47 +1388,46 @@ def transpose_f32(x, rows=None, cols=None, *, batch=1, ld_in=None, stride_in=0, 
     ld_out = round_up(rows, pad_to)
     if out is None:
         out = torch.empty((batch, cols, ld_out), dtype=torch.float32, device=x.device)
-    _l.check(_l.load().ug_transpose_f32(_p(x), ld_in, stride_in, _p(out), ld_out, cols * ld_out, rows, cols, batch, _stream()),
-             "ug_transpose_f32")
+    _l.api().ug_transpose_f32(_p(x), ld_in, stride_in, _p(out), ld_out, cols * ld_out, rows, cols, batch, _stream())
     return out
 
 
 def nchw_to_nhwc(x, c_pad):
     B, C, H, W = x.shape
     out = torch.empty((B, H, W, c_pad), dtype=torch.float32, device=x.device)
-    _l.check(_l.load().ug_nchw_to_nhwc(_p(x), _p(out), B, C, H * W, c_pad, _stream()), "ug_nchw_to_nhwc")
+    _l.api().ug_nchw_to_nhwc(_p(x), _p(out), B, C, H * W, c_pad, _stream())
     return out
 
 
 def nhwc_to_nchw(x, C):
     B, H, W, Cp = x.shape
     out = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
-    _l.check(_l.load().ug_nhwc_to_nchw(_p(x), _p(out), B, C, H * W, Cp, _stream()), "ug_nhwc_to_nchw")
+    _l.api().ug_nhwc_to_nchw(_p(x), _p(out), B, C, H * W, Cp, _stream())
     return out
 
 
 def lfq_pack(z2d, nbits):
     n = z2d.shape[0]
     idx = torch.empty((n,), dtype=torch.int64, device=z2d.device)
-    _l.check(_l.load().ug_lfq_pack(_p(z2d), z2d.stride(0), _p(idx), n, nbits, _stream()), "ug_lfq_pack")
+    _l.api().ug_lfq_pack(_p(z2d), z2d.stride(0), _p(idx), n, nbits, _stream())
     return idx
 
 
 def lfq_unpack(idx, nbits, err_flag=None):
     n = idx.numel()
     z = torch.empty((n, nbits), dtype=torch.float32, device=idx.device)
-    _l.check(_l.load().ug_lfq_unpack(_p(idx), _p(z), n, nbits, _p(err_flag), _stream()), "ug_lfq_unpack")
+    _l.api().ug_lfq_unpack(_p(idx), _p(z), n, nbits, _p(err_flag), _stream())
     return z
 
 
 def probe_layouts(device):
     out = torch.zeros((512,), dtype=torch.float32, device=device)
-    _l.check(_l.load().ug_probe_layouts(_p(out), 512, _stream()), "ug_probe_layouts")
+    _l.api().ug_probe_layouts(_p(out), 512, _stream())
     return out
 
 
 def gelu(x, dy=None):
     """bf16 GELU(erf): forward if dy is None, else the gradient dgelu(x) * dy."""
     out = torch.empty_like(x)
-    _l.check(_l.load().ug_gelu(_p(x), _p(dy), _p(out), x.numel(), _stream()), "ug_gelu")
+    _l.api().ug_gelu(_p(x), _p(dy), _p(out), x.numel(), _stream())
     return out

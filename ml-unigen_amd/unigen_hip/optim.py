@@ -278,7 +278,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._runs is None:
             self._build_runs()
         self._step += 1
-        lib = ops._l.load()
+        lib = ops._l.api()
         factor, host_scale = None, float(grad_scale)
         if self._deferred_factor is not None:      # clip_grad_norm_(..., defer_to=self) took the norm already
             factor, self._deferred_factor = self._deferred_factor, None
@@ -322,13 +322,12 @@ class FusedAdamW(torch.optim.Optimizer):
                 stream = self._side
             max_blocks = self.overlap_blocks if stream is not main else 0
             if factor is None:
-                rc = lib.ug_adamw_flat(r.p_ptr, g_ptr, r.m.data_ptr(), r.v.data_ptr(), mirror, r.numel, float(g["lr"]), b1, b2,
-                                       g["eps"], g["weight_decay"], self._step, host_scale, max_blocks, stream.cuda_stream)
+                lib.ug_adamw_flat(r.p_ptr, g_ptr, r.m.data_ptr(), r.v.data_ptr(), mirror, r.numel, float(g["lr"]), b1, b2,
+                                  g["eps"], g["weight_decay"], self._step, host_scale, max_blocks, stream.cuda_stream)
             else:
-                rc = lib.ug_adamw_flat_dev(r.p_ptr, g_ptr, r.m.data_ptr(), r.v.data_ptr(), mirror, r.numel, float(g["lr"]), b1, b2,
-                                           g["eps"], g["weight_decay"], self._step, host_scale, factor.data_ptr(), max_blocks,
-                                           stream.cuda_stream)
-            ops._l.check(rc, "ug_adamw_flat")
+                lib.ug_adamw_flat_dev(r.p_ptr, g_ptr, r.m.data_ptr(), r.v.data_ptr(), mirror, r.numel, float(g["lr"]), b1, b2,
+                                      g["eps"], g["weight_decay"], self._step, host_scale, factor.data_ptr(), max_blocks,
+                                      stream.cuda_stream)
             # the kernel wrote through a raw pointer: bump the (shared) version counter so the engine
             # knows its bf16 compute copies are stale
             torch.autograd.graph.increment_version(first)
