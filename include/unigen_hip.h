@@ -592,6 +592,50 @@ int ug_head_score(const void* x, int64_t ldx, int64_t R, const void* W, int64_t 
                   const int64_t* labels, int64_t ignore_index, void* ws, float* logp, float* lse, int64_t* best, float* best_logit,
                   hipStream_t stream);
 
+/* ---- Beam search of the text loop --------------------------------------------------------------
+ * The rule (UniGen.beam_search, models/beam.py: BeamSearch) is transformers' GenerationMixin._beam_search with do_sample=False:
+ *   - per prompt (a "group") B = num_beams running beams; initial running scores [0, -1e9, ..., -1e9];
+ *   - every step takes K = max(2, 1 + number of eos ids) * B candidates per group from the B * V values
+ *     log_softmax(logits[b])[e] + running_score[b], in descending order;
+ *   - a candidate whose token is an eos id never joins the running set; it enters the group's finished pool only when it ranks among
+ *     the first B of the K; the next running beams are the first B non-eos candidates;
+ *   - a finished hypothesis scores sum_logprobs / (generated_length ** length_penalty), the eos token counted; the pool keeps the
+ *     best B of old and new;
+ *   - after every step a group asks whether a running beam can still beat its pool: best running score / (length ** length_penalty)
+ *     > the pool's worst score (an incomplete pool counts as -1e9: always), with length = the generated length so far, or
+ *     max_new_tokens for early_stopping "never" with length_penalty > 0; once the answer is no it stays no and nothing enters that
+ *     pool any more; with early_stopping True a full pool is closed at once, whatever the bound says;
+ *   - the call ends when no group can improve, or (early_stopping True) every pool is full, or at max_new_tokens, where every
+ *     candidate ends and the first B of each group meet the pool like any finished hypothesis;
+ *   - num_beams = 1 is greedy search: a prompt's first hypothesis ends it (early_stopping True, whatever was passed);
+ *   - a prompt's output rows are its num_return_sequences <= B best hypotheses, best first, padded behind their eos with pad_token_id
+ *     (default: the first eos id).
+ * ug_beam_candidates: logits fp32 [G*B][ld], V <= ld (entries V..ld-1 are never read); beam_scores fp32 [G*B];
+ *   outputs cand_score fp32 [G][K], cand_beam int32 [G][K] (0..B-1 inside the group), cand_token int32 [G][K]; lse fp32 [G*B] or null.
+ *   Per row b: s[e] = bf16round(logit[e]) (the head rounding of the precision contract, what ug_text_pick picks from), m = max s,
+ *   lse = m + log(sum exp(s[e] - m)); a NaN entry contributes nothing and is no candidate, a -inf entry contributes 0 and is no
+ *   candidate (a +inf entry makes lse +inf and the row supplies no candidates; a row without a finite entry has lse -inf).
+ *   Per candidate: total = (s[e] - lse[b]) + beam_scores[b] in fp32, in exactly this order.  A row with beam_scores[b] <= -1e8 is a
+ *   dead beam and supplies no candidates.  Output order: total descending, equal totals by flat index b*V + e ascending; slots the
+ *   live beams cannot fill hold (-inf, -1, -1).
+ *   lse is summed per bf16 pattern (count * exp(value - m), fp64 accumulation, patterns in descending order): bit-reproducible, and a
+ *   row's lse bits depend on that row's logits alone -- two rows with equal logits and equal scores tie exactly, the lower beam first.
+ *   Limits, refused with a status before anything is touched: 1 <= B <= 8, 1 <= G*B <= 32, 1 <= K <= 64, 1 <= V <= 262144, ld >= V,
+ *   null pointers (lse excepted).  ws: ug_beam_candidates_ws_bytes(G, B, V, K) bytes, 16-byte aligned, need not be initialised
+ *   (csrc/beam_plan.h: 256 KiB of histogram per row + the rows' lists); > 0, or a negative status outside the limits.
+ * ug_beam_kv_reorder: k_ptrs / v_ptrs device arrays of n_layers pointers to bf16 caches [R][HKV][Tmax][hd] (DecodeState's layout,
+ *   16-byte aligned); parent int32 [R] in device memory, absolute row indices; len the state's device int; spare bf16
+ *   [2*n_layers][R][HKV][span][hd].  For every layer, both caches, every row r, head h and position t in
+ *   [first, min(*len, first + span)): cache[r][h][t] = the old cache[parent[r]][h][t]; every other byte of every cache is unchanged.
+ *   Two launches: gather into spare for rows with parent[r] != r, then write back; 16 bytes per lane; nothing is read on the host.  A
+ *   parent outside [0, R) moves nothing.  Limits: hd == 128, 1 <= R <= 32, first >= 0, span >= 1, first + span <= Tmax,
+ *   1 <= n_layers <= 1024, non-null pointers. */
+int ug_beam_candidates_ws_bytes(int64_t G, int64_t B, int64_t V, int64_t K);
+int ug_beam_candidates(const float* logits, int64_t ld, int64_t G, int64_t B, int64_t V, const float* beam_scores, int64_t K, void* ws,
+                       float* cand_score, int* cand_beam, int* cand_token, float* lse, hipStream_t stream);
+int ug_beam_kv_reorder(const void* const* k_ptrs, const void* const* v_ptrs, int64_t n_layers, int64_t R, int64_t HKV, int64_t Tmax,
+                       int64_t hd, const int* parent, const int* len, int64_t first, void* spare, int64_t span, hipStream_t stream);
+
 /* ---- optimizer ------------------------------------------------------------------------------- */
 /* replaces: torch.optim.AdamW.step (training/train.py:324-330,780) over one flat fp32 segment; also
  * refreshes the bf16 compute copy (p_bf16 may be null).  grads are multiplied by grad_scale first. */

@@ -316,7 +316,7 @@ def generate_call(vocab, do_sample, temperature, top_k, top_p, eos_token_id, pad
     """`generate`'s arguments -> (TextCall, num_return_sequences)"""
     unsupported = [k for k in ("num_beams", "penalty_alpha") if kwargs.get(k) not in (None, 1, 1.0)]
     if unsupported:
-        raise UniGenHipError(f"generate: {unsupported} are not implemented (greedy / sampling only)")
+        raise UniGenHipError(f"generate: {unsupported} are not implemented in generate (greedy / sampling only): call UniGen.beam_search")
     sampling = None
     if do_sample:
         sampling = (float(1.0 if temperature is None else temperature), int(top_k or 0), float(1.0 if top_p is None else top_p))
@@ -332,6 +332,42 @@ def generate_call(vocab, do_sample, temperature, top_k, top_p, eos_token_id, pad
     if n_ret > 1 and not do_sample:
         raise UniGenHipError(f"generate: num_return_sequences={n_ret} needs do_sample=True (greedy rows would all be equal)")
     return call, n_ret
+
+
+BEAM_REFUSED = ("do_sample", "repetition_penalty", "logit_bias", "suppress_tokens", "min_new_tokens", "no_repeat_ngram_size",
+                "stop_sequences", "return_logprobs", "num_beam_groups", "on_device")
+
+
+def beam_call(rows, max_new_tokens, num_beams, num_return_sequences, length_penalty, early_stopping, eos_token_id, pad_token_id, kwargs):
+    """`beam_search`'s arguments, checked before any launch -> (num_beams, num_return_sequences, eos ids, pad id).  rows: the number of
+    prompts.  What the method does not serve is refused by name: the options that need per-beam histories reordered with the beams
+    (the penalty, the constraints, log-probabilities), sampling, beam groups and the on-device loop."""
+    off = {"repetition_penalty": (None, 1, 1.0), "num_beam_groups": (None, 1), "min_new_tokens": (None, 0), "no_repeat_ngram_size": (None, 0)}
+    refused = [k for k in BEAM_REFUSED if k in kwargs and kwargs[k] not in off.get(k, (None, False)) and kwargs[k] != [] and kwargs[k] != {}]
+    if refused:
+        raise UniGenHipError(f"beam_search: {refused} are not implemented with beam search (greedy beams on the host loop only)")
+    unknown = [k for k in kwargs if k not in BEAM_REFUSED]
+    if unknown:
+        raise UniGenHipError(f"beam_search: unknown arguments {unknown}")
+    B, n = int(num_beams), int(num_return_sequences)
+    if not 1 <= B <= ops.BEAM_MAX_BEAMS:
+        raise UniGenHipError(f"beam_search: num_beams={B} must be between 1 and {ops.BEAM_MAX_BEAMS}")
+    if rows < 1 or rows * B > ops.BEAM_MAX_ROWS:
+        raise UniGenHipError(f"beam_search: {rows} prompts x num_beams={B} = {rows * B} rows (at least 1, at most {ops.BEAM_MAX_ROWS})")
+    if not 1 <= n <= B:
+        raise UniGenHipError(f"beam_search: num_return_sequences={n} must be between 1 and num_beams={B}")
+    if int(max_new_tokens) < 1:
+        raise UniGenHipError(f"beam_search: max_new_tokens={max_new_tokens} must be at least 1")
+    if early_stopping not in (False, True, "never"):
+        raise UniGenHipError(f"beam_search: early_stopping={early_stopping!r} must be False, True or 'never'")
+    if not math.isfinite(float(length_penalty)):
+        raise UniGenHipError(f"beam_search: length_penalty={length_penalty} must be finite")
+    eos = list(dict.fromkeys(stop_list(eos_token_id)))
+    if len(eos) > 7:
+        raise UniGenHipError(f"beam_search: {len(eos)} eos ids (at most 7: a step keeps (1 + eos ids) x num_beams candidates, at most "
+                             f"{ops.BEAM_MAX_K})")
+    pad = int(pad_token_id) if pad_token_id is not None else (eos[0] if eos else 0)
+    return B, n, eos, pad
 
 
 def mmu_call(who, vocab, temperature, top_k, eot_token, **how):
@@ -1291,6 +1327,62 @@ class UniGen(ModelMixin, ConfigMixin):
         out = out[:, :steps]
         seqs = torch.cat([prompt.prompt_ids, out], dim=1) if input_embeddings is None else out
         return (seqs, logp[:, :steps]) if return_logprobs else seqs
+
+    @torch.no_grad()
+    def beam_search(self, input_ids=None, input_embeddings=None, attention_mask=None, max_new_tokens=20, num_beams=4,
+                    num_return_sequences=1, length_penalty=1.0, early_stopping=False, eos_token_id=None, pad_token_id=None,
+                    deterministic=None, return_scores=False, **kwargs):
+        """Beam search with the rule of transformers' `generate(num_beams=B, do_sample=False)` (stated once, in include/unigen_hip.h:
+        "Beam search of the text loop"; the bookkeeping is models/beam.py: BeamSearch).  Prompts as `generate` takes them: ids [G, L]
+        or `input_embeddings` [G, L, H] with an optional 2-D [G, L] key-validity mask (left padding).  Every prompt row, with its mask
+        row, is repeated num_beams times consecutively before the one prefill; a step is the head over the whole vocabulary,
+        ops.beam_candidates (log-softmax of the bf16-rounded logits + running score, the K best per prompt), BeamSearch.step on the
+        [G, K] candidates (the step's one host read), ops.beam_kv_reorder on the generated positions [L, len) of the cache -- the
+        prompt part is the same in all beams of a prompt and never moves -- and the decode step on the chosen tokens.
+        Returns each prompt's num_return_sequences <= num_beams best hypotheses, best first, padded behind their eos with
+        pad_token_id (default: the first eos id): prompt + continuation [G * n, L + new] for ids, the continuation alone [G * n, new]
+        for embeddings; with return_scores also sequence_scores fp32 [G * n] (sum of log-probabilities / length ** length_penalty).
+        num_beams=1 is greedy search.  Refused before any launch: more than 32 rows (G * num_beams), num_beams > 8,
+        num_return_sequences > num_beams, more than 7 eos ids, max_new_tokens < 1, and do_sample, repetition_penalty, logit_bias,
+        suppress_tokens, min_new_tokens, no_repeat_ngram_size, stop_sequences, return_logprobs, num_beam_groups, on_device=True."""
+        from unigen_hip.qwen2 import DecodeState, resolve_deterministic
+        from .beam import BeamSearch
+        src = input_ids if input_embeddings is None else input_embeddings
+        if src is None:
+            raise UniGenHipError("beam_search: give input_ids or input_embeddings")
+        G, n_new = int(src.shape[0]), int(max_new_tokens)
+        B, n_ret, eos, pad = beam_call(G, max_new_tokens, num_beams, num_return_sequences, length_penalty, early_stopping, eos_token_id,
+                                       pad_token_id, kwargs)
+        det = resolve_deterministic(deterministic)
+        rep = lambda t: None if t is None else t.repeat_interleave(B, dim=0)
+        eng, embed, V = self.llm.engine, self.llm.model.embed_tokens, self.config.vocab_size
+        prompt = self._generate_prompt(rep(input_ids), rep(input_embeddings), rep(attention_mask))
+        dev, R, L = prompt.embeds.device, prompt.rows, prompt.L
+        eng.last_decode_deterministic, eng.last_text_decode_on_device = det, False
+        st = DecodeState(eng.dims, R, L + n_new, dev, key_valid=prompt.key_valid, deterministic=det)
+        hn = prompt.prefill(eng, st)
+        eng.check_errors()
+        search = BeamSearch(G, B, eos, pad, n_new, length_penalty, early_stopping, n_ret)
+        spare = ops.beam_kv_spare(st, n_new) if B > 1 else None
+        x = torch.empty((R, eng.dims.hidden_size), dtype=torch.float32, device=dev)
+        scores = search.running_scores().to(dev)
+
+        def pick(logits):
+            return ops.beam_candidates(logits, scores, G, B, V, search.k)
+
+        def emit(i, cand):
+            parent, token, finished = search.step(*cand)
+            if not finished and i + 1 < n_new:
+                if i > 0 and B > 1:                                     # (step 0: nothing generated is in the cache yet)
+                    ops.beam_kv_reorder(st, parent, L, spare)
+                scores.copy_(search.running_scores())
+            return token, finished
+
+        text_token_loop(n_new, hn, pick, emit, head=lambda hn: eng.head_slice(hn, 0, V).float(),
+                        embed=lambda ids: x.copy_(embed(ids)[:, 0]), step=lambda x: eng.decode_step(st, x))
+        out, seq_scores = search.finalize()
+        seqs = torch.cat([input_ids.to(dev).repeat_interleave(n_ret, dim=0), out], dim=1) if input_embeddings is None else out
+        return (seqs, seq_scores) if return_scores else seqs
 
     # ------------------------------------------------------------------ text decoding for understanding
     @torch.no_grad()

@@ -80,7 +80,7 @@ if ABI_VERSION is None:
 SIGNATURES = {name: proto.argtypes for name, proto in PROTOTYPES.items() if name != "ug_last_error"}    # name -> argtypes
 # entry points whose return value is a value, not a status: api() hands it back unchecked
 VALUE_RETURNS = frozenset(("ug_abi_version", "ug_decode_sw_supported", "ug_text_sample_workspace_ints", "ug_head_score_ws_bytes",
-                           "ug_comm_bytes_on_wire"))
+                           "ug_comm_bytes_on_wire", "ug_beam_candidates_ws_bytes"))
 
 _lib = None
 _api = None

@@ -1028,6 +1028,76 @@ def head_score(x, W, V, labels, ignore_index=-100, want=("lse", "best")):
     return (logp,) + tuple(out[n] for n in want)
 
 
+BEAM_MAX_BEAMS, BEAM_MAX_ROWS, BEAM_MAX_K = 8, 32, 64        # csrc/beam_plan.h
+_BEAM_WS = {}
+
+
+def beam_candidates_ws_bytes(G, B, V, K):
+    """bytes of ug_beam_candidates' workspace (csrc/beam_plan.h): a 256 KiB histogram per row + the rows' candidate lists"""
+    ws_bytes = _l.api().ug_beam_candidates_ws_bytes
+    n = ws_bytes(G, B, V, K)
+    if n <= 0:
+        _l.check(n, ws_bytes.__name__)
+    return n
+
+
+def beam_candidates(logits, beam_scores, G, B, V, K, want_lse=False):
+    """The K best continuations of each of G groups of B beams (include/unigen_hip.h: ug_beam_candidates).  logits fp32 [G * B, >= V]
+    (unit inner stride), beam_scores fp32 [G * B] -> (cand_score fp32 [G, K], cand_beam int32 [G, K], cand_token int32 [G, K]), then
+    lse fp32 [G * B] with want_lse."""
+    _need_cuda(logits, beam_scores)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or logits.shape[0] != G * B or logits.shape[1] < V \
+            or beam_scores.dtype != torch.float32 or beam_scores.shape != (G * B,) or not beam_scores.is_contiguous() \
+            or beam_scores.device != logits.device:
+        raise _l.UniGenHipError(f"beam_candidates: need fp32 logits [G * B, >= V] with unit inner stride and contiguous fp32 beam_scores "
+                                f"[G * B] on one device (logits {tuple(logits.shape)} {logits.dtype}, beam_scores "
+                                f"{tuple(beam_scores.shape)} {beam_scores.dtype}, G {G}, B {B}, V {V})")
+    dev = logits.device
+    nbytes = beam_candidates_ws_bytes(G, B, V, K)
+    ws = _BEAM_WS.get(dev)
+    if ws is None or ws.numel() < nbytes:
+        ws = _BEAM_WS[dev] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)       # (the entry point clears what it reads)
+    cand_score = torch.empty((G, K), dtype=torch.float32, device=dev)
+    cand_beam = torch.empty((G, K), dtype=torch.int32, device=dev)
+    cand_token = torch.empty((G, K), dtype=torch.int32, device=dev)
+    lse = torch.empty((G * B,), dtype=torch.float32, device=dev) if want_lse else None
+    _l.api().ug_beam_candidates(_p(logits), logits.stride(0), G, B, V, _p(beam_scores), K, _p(ws), _p(cand_score), _p(cand_beam),
+                                _p(cand_token), _p(lse), _stream())
+    return (cand_score, cand_beam, cand_token) + ((lse,) if want_lse else ())
+
+
+def beam_kv_spare(st, span):
+    """the staging buffer of beam_kv_reorder for `span` generated positions of the decode state `st`"""
+    rows, hk, _, hd = st.k[0].shape
+    return torch.empty((2 * len(st.k), rows, hk, span, hd), dtype=torch.bfloat16, device=st.k[0].device)
+
+
+def beam_kv_reorder(st, parent, first, spare):
+    """Reorder the generated part of a DecodeState's KV cache by parent beam (include/unigen_hip.h: ug_beam_kv_reorder): positions
+    [first, min(st.len, first + span)) of every row r, in every layer's keys and values, become row parent[r]'s.  parent int32 [rows]
+    on the device (absolute rows), spare bf16 [2 * layers, rows, HKV, span, hd] (beam_kv_spare).  The two pointer tables are built
+    once per state and kept on it."""
+    _need_cuda(parent, spare)
+    rows, hk, Tmax, hd = st.k[0].shape
+    dev = st.k[0].device
+    n = len(st.k)
+    bad = [t for t in list(st.k) + list(st.v) if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.shape != (rows, hk, Tmax, hd)
+           or t.device != dev]
+    if bad or len(st.v) != n or parent.dtype != torch.int32 or parent.shape != (rows,) or not parent.is_contiguous() or parent.device != dev \
+            or spare.dtype != torch.bfloat16 or spare.dim() != 5 or not spare.is_contiguous() or spare.device != dev \
+            or spare.shape[:3] != (2 * n, rows, hk) or spare.shape[4] != hd or st.len.dtype != torch.int32 or st.len.device != dev:
+        raise _l.UniGenHipError(f"beam_kv_reorder: need contiguous bf16 caches [rows, HKV, Tmax, hd] on one device, int32 parent [rows] and "
+                                f"bf16 spare [2 * layers, rows, HKV, span, hd] there (cache {tuple(st.k[0].shape)}, parent "
+                                f"{tuple(parent.shape)} {parent.dtype}, spare {tuple(spare.shape)} {spare.dtype})")
+    tables = getattr(st, "_beam_kv_tables", None)
+    addrs = tuple(t.data_ptr() for t in list(st.k) + list(st.v))
+    if tables is None or tables[0] != addrs:
+        table = torch.tensor(addrs, dtype=torch.int64).to(dev)
+        tables = st._beam_kv_tables = (addrs, table[:n], table[n:])
+    _l.api().ug_beam_kv_reorder(_p(tables[1]), _p(tables[2]), n, rows, hk, Tmax, hd, _p(parent), _p(st.len), int(first), _p(spare),
+                                int(spare.shape[3]), _stream())
+
+
 # flat fp32 master buffers that keep a bf16 compute mirror (FlatParams registers itself); FusedAdamW writes the
 # mirror in the same pass so no separate cast pass follows an optimizer step
 BF16_MIRRORS = []

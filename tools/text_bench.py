@@ -21,7 +21,14 @@ one one-token call of the same session for the prefill + first token.  Five visi
 the same pairing for the constraints (one ug_text_constrain launch per step ahead of the penalty, one ug_text_stop_seq launch behind the
 pick): all off against logit_bias (64 ids), suppress_tokens (64 ids), min_new_tokens (with a stop id no row produces, which the "off"
 of that pair carries too), no_repeat_ngram_size=3 (the 768 prompt ids are the history), stop_sequences (8 of 16 ids no row produces), and
-all five at once."""
+all five at once.
+
+    python tools/text_bench.py --beam
+
+beam_search(num_beams=4) on 8 prompts (32 rows) against the host loop of generate(do_sample=True, num_return_sequences=4) on the same
+32 rows, alternating in one process: causal prompts of 768 ids, 64 new tokens, no eos.  Two warm-up calls of each, five timed; a
+call's decode time is its wall time minus the median of three one-token calls of the same entry point.  The line carries the power and
+clock sample of bench.py's PowerSampler over the timed calls (null where the hwmon files are missing or the card stayed under 300 W)."""
 import json
 import os
 import statistics
@@ -104,6 +111,48 @@ def paired(modes, label, rounds=5):
     print(json.dumps(result))
 
 
+def beam_pair(prompts=8, beams=4, rounds=5):
+    from bench import PowerSampler
+    dev = torch.device("cuda:0")
+    model = UniGen(w_und_encoder=False, vocab_size=VOCAB, llm_vocab_size=TEXT_VOCAB, llm_model_path="Qwen2.5-1.5B-Instruct",
+                   codebook_size=CODEBOOK, num_vq_tokens=NVQ, device=dev, init_seed=-1)
+    model.llm.init_weights_device(1)
+    model.eval()
+    g = torch.Generator(device=dev).manual_seed(2)
+    ids = torch.randint(0, 151643, (prompts, L), device=dev, generator=g)
+    R = prompts * beams
+
+    def call(beam, new=NEW):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if beam:
+            out = model.beam_search(input_ids=ids, max_new_tokens=new, num_beams=beams, num_return_sequences=beams)
+        else:
+            out = model.generate(input_ids=ids, max_new_tokens=new, do_sample=True, top_k=50, num_return_sequences=beams, on_device=False)
+        torch.cuda.synchronize()
+        assert tuple(out.shape) == (R, L + new)
+        return time.perf_counter() - t0
+
+    for _ in range(2):
+        call(False), call(True)
+    first = {b: statistics.median(call(b, 1) for _ in range(3)) for b in (False, True)}
+    times = {False: [], True: []}
+    sampler, w0 = PowerSampler(), time.time()
+    for _ in range(rounds):
+        for b in (False, True):
+            times[b].append(call(b))
+    power = sampler.report(w0, time.time())
+    rec = {}
+    for b, tag in ((False, "sampled_host_loop"), (True, "beam_search")):
+        step_ms = [1e3 * (t - first[b]) / (NEW - 1) for t in times[b]]
+        rec[tag] = {"call_s": [round(t, 4) for t in times[b]], "first_token_call_s": round(first[b], 4),
+                    "ms_per_step": [round(m, 4) for m in step_ms], "tokens_per_s": [round(1e3 * R / m, 1) for m in step_ms],
+                    "median_tokens_per_s": round(1e3 * R / statistics.median(step_ms), 1)}
+    med = lambda tag: statistics.median(rec[tag]["ms_per_step"])
+    rec["beam_over_sampled_step_time"] = round(med("beam_search") / med("sampled_host_loop"), 3)
+    print(json.dumps({"prompt": L, "new_tokens": NEW, "prompts": prompts, "num_beams": beams, "rows": R, "power": power, **rec}))
+
+
 def main():
     dev = torch.device("cuda:0")
     rows = [int(r) for r in os.environ.get("ROWS", "1,16").split(",")]
@@ -157,5 +206,7 @@ if __name__ == "__main__":
         penalty_pair(float(sys.argv[2]))
     elif len(sys.argv) > 1 and sys.argv[1] == "--constraints":
         paired(constraint_modes(), {"constraints": True})
+    elif len(sys.argv) > 1 and sys.argv[1] == "--beam":
+        beam_pair()
     else:
         main()
