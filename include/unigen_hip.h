@@ -195,6 +195,8 @@ int ug_attn_bwd(const void* q, const void* k, const void* v, int64_t ldq,
 int ug_kv_store(const void* qkv, int64_t ldq, int64_t k_col, int64_t v_col, void* cache_k, void* cache_v,
                 int64_t rows, int64_t L, int HKV, int head_dim, int64_t Tmax, const int* pos_dev, int pos_host,
                 hipStream_t stream);
+/* ug_rope's rotation for `rows` single-token rows, all at table row *pos_dev of cos / sin [max_pos, head_dim/2].  A *pos_dev at or
+ * past max_pos is clamped to the last table row, max_pos - 1 (no error is raised; the table is never read past its end). */
 int ug_rope_at(void* qkv, const float* cos_tab, const float* sin_tab, int64_t rows, int64_t ldq, int nheads,
                int head_dim, const int* pos_dev, int64_t max_pos, hipStream_t stream);
 int ug_attn_decode(const void* q, int64_t ldq, const void* cache_k, const void* cache_v, const uint8_t* key_valid,
@@ -560,7 +562,11 @@ int ug_text_stop_seq(const int* seq_ids, const int* seq_off, int64_t ns, int64_t
 /* ---- loss ------------------------------------------------------------------------------------ */
 /* replaces: F.cross_entropy(ignore_index=-100) x3 in UniGen.forward (models/unigen.py:310-338) and
  * get_batch_logps (training/train_dpo.py:51-90).  logits bf16 [R, ld], ld % 8 == 0.
- * loss_and_count (optional): [0] = mean loss over valid rows, [1] = number of valid rows. */
+ * loss_and_count (optional): [0] = mean loss over valid rows, [1] = number of valid rows.
+ * A row whose label equals ignore_index or lies outside [0, V) is an ignored row everywhere: it gets loss_row = logp = 0.0 (its lse
+ * is written as usual), it is not counted in loss_and_count[1], and ug_ce_bwd writes it a zero gradient row, in the mean form and
+ * in the row_scale form alike.  With no valid row the mean is 0 / 0 = NaN like F.cross_entropy's, and the gradient is all zeros.
+ * Finite logits are a precondition: a lane whose first chunk of a row is all -inf forms -inf - -inf in its running sum. */
 int ug_ce_fwd(const void* logits, int64_t ld, int64_t R, int64_t V, const int64_t* labels,
               int64_t ignore_index, float* lse, float* loss_row, float* logp_label, float* loss_and_count,
               hipStream_t stream);

@@ -89,16 +89,22 @@ __device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack_bf2(f, f)
 // ---------------------------------------------------------------- SiLU of the training forward (one definition for every kernel)
 // silu(g) = g / (1 + exp(-g)) with the quotient as rcp + one residual correction (6 VALU operations; the IEEE division sequence
 // -- div_scale x 2, rcp, five fma, div_fmas, div_fixup -- was 34 of the fused gate_up epilogue's 60 extra us per launch).  The
-// divisor is in [1, inf): no scaling needed; exp(-g) = inf (g < -88.7) gives the signed zero the exact quotient rounds to.
+// divisor is in [1, inf): no scaling against overflow of the reciprocal needed; exp(-g) = inf (g < -88.7) gives the signed zero the exact quotient rounds to.
 // swiglu_fwd_kernel and the GEMM epilogues share it, so the fused and the two-launch forms stay bit-identical to each other;
 // against the fp32 reference the quotient is within 1 ulp before the bf16 rounding that follows it everywhere.
+// v_rcp_f32 flushes a subnormal RESULT to zero: for a divisor above 2^126 (g = -88.5, -88, -87.5 of the bf16 gates) the quotient,
+// about -1e-36 and a normal number, used to come out as zero.  So the reciprocal is taken of d / 4 (at most 2^126 for every finite d;
+// formed as fma(e, 1/4, 1/4), the same rounding as 1 + e) and the dividend is g / 4: every step is the old one scaled by a power of
+// two, the result the same bits as before wherever the old one was right -- one multiplication more.
+#define UG_SILU_OVERFLOW (3.0e38f * 0.25f)               /* d / 4 above this: exp(-g) overflowed, or is about to */
 __device__ __forceinline__ float silu_train(float g) {
-  const float d = 1.f + __expf(-g);
+  const float d = __builtin_fmaf(__expf(-g), 0.25f, 0.25f);
+  const float gq = g * 0.25f;
   const float y = __builtin_amdgcn_rcpf(d);
-  const float q = g * y;
-  const float r = __builtin_fmaf(-d, q, g);
+  const float q = gq * y;
+  const float r = __builtin_fmaf(-d, q, gq);
   const float v = __builtin_fmaf(r, y, q);
-  return (d > 3.0e38f) ? g * 0.f : v;
+  return (d > UG_SILU_OVERFLOW) ? g * 0.f : v;
 }
 
 // One element of the SwiGLU backward (autograd of act = bf16(bf16(silu(gate)) * up) under bf16 autocast, Qwen2MLP.forward,
@@ -106,10 +112,10 @@ __device__ __forceinline__ float silu_train(float g) {
 // so the fused and the two-launch forms are bit-identical to each other.  sigmoid = rcp + one Newton step (divisor in [1, inf)).
 __device__ __forceinline__ void swiglu_bwd_elem(float gf, float uf, float df, float& dgate, float& dup) {
 #pragma clang fp contract(off)
-  const float d = 1.f + __expf(-gf);
+  const float d = __builtin_fmaf(__expf(-gf), 0.25f, 0.25f);      // (1 + e) / 4, see silu_train: a sigmoid below 2^-126 is a subnormal, not zero
   const float y0 = __builtin_amdgcn_rcpf(d);
-  const float y1 = __builtin_fmaf(y0, __builtin_fmaf(-d, y0, 1.f), y0);
-  const float sg = (d > 3.0e38f) ? 0.f : y1;
+  const float y1 = __builtin_fmaf(y0, __builtin_fmaf(-d, y0, 1.f), y0) * 0.25f;
+  const float sg = (d > UG_SILU_OVERFLOW) ? 0.f : y1;
   const float s = bf2f(f2bf(gf * sg));                    // bf16 silu output saved by autograd
   const float dsilu = bf2f(f2bf(df * uf));                // grad wrt silu output (bf16 mul backward)
   dup = df * s;

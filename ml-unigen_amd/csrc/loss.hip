@@ -8,6 +8,12 @@
 
 namespace {
 
+// A label that is neither ignore_index nor inside [0, V) is treated as ignored: one rule for the
+// loss row, the count and the gradient (the same rule as ug_head_score).
+__device__ __forceinline__ bool ce_label_valid(int64_t lab, int64_t ignore_index, int V) {
+  return lab != ignore_index && lab >= 0 && lab < V;
+}
+
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ logits, int64_t ld, int V,
                                                      const int64_t* __restrict__ labels, int64_t ignore_index,
                                                      float* __restrict__ lse_out, float* __restrict__ loss_row,
@@ -43,7 +49,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ 
     lse_out[row] = lse;
     const int64_t lab = labels ? labels[row] : ignore_index;
     float lr = 0.f, lp = 0.f;
-    if (lab != ignore_index && lab >= 0 && lab < V) { lp = bf2f(x[lab]) - lse; lr = -lp; }
+    if (ce_label_valid(lab, ignore_index, V)) { lp = bf2f(x[lab]) - lse; lr = -lp; }
     if (loss_row) loss_row[row] = lr;
     if (logp_label) logp_label[row] = lp;
   }
@@ -52,11 +58,11 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ 
 // loss = sum(loss_row over valid rows) / count ;  out[0] = loss, out[1] = count
 __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict__ loss_row,
                                                         const int64_t* __restrict__ labels, int64_t ignore_index,
-                                                        int R, float* __restrict__ out) {
+                                                        int R, int V, float* __restrict__ out) {
   __shared__ float red[4];
   float s = 0.f, c = 0.f;
   for (int i = threadIdx.x; i < R; i += 256) {
-    if (labels[i] != ignore_index) { s += loss_row[i]; c += 1.f; }
+    if (ce_label_valid(labels[i], ignore_index, V)) { s += loss_row[i]; c += 1.f; }
   }
   const float S = block_sum<4>(s, red);
   const float C = block_sum<4>(c, red);
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(bf16_t* __restrict__ logits
   const int row = blockIdx.x;
   bf16_t* x = logits + (int64_t)row * ld;
   const int64_t lab = labels[row];
-  const bool valid = (lab != ignore_index);
+  const bool valid = ce_label_valid(lab, ignore_index, V);
   // mean-CE gradient (*gscale / count) or, with row_scale, an arbitrary upstream gradient per row (log-prob sums of DPO)
   const float sc = !valid ? 0.f : row_scale ? row_scale[row] : (gscale ? *gscale : 1.f) / loss_cnt[1];
   const float l = lse[row];
@@ -101,7 +107,8 @@ extern "C" int ug_ce_fwd(const void* logits, int64_t ld, int64_t R, int64_t V, c
   UG_CHECK_LAUNCH("ug_ce_fwd");
   if (loss_and_count) {
     UG_REQUIRE(labels && loss_row, "ug_ce_fwd: loss reduction needs labels and loss_row");
-    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, st, loss_row, labels, ignore_index, (int)R, loss_and_count);
+    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, st, loss_row, labels, ignore_index, (int)R, (int)V,
+                       loss_and_count);
     UG_CHECK_LAUNCH("ug_ce_fwd(reduce)");
   }
   return UG_OK;
