@@ -252,6 +252,21 @@ int ug_attn_decode_fused(const float* acc_qkv, int64_t ldacc, const float* ss_in
                          const float* cos_tab, const float* sin_tab, const int* pos_dev, void* cache_k, void* cache_v,
                          const uint8_t* key_valid, void* o, int64_t ldo, int64_t rows, int H, int HKV, int head_dim,
                          int64_t Tmax, int64_t max_pos, float scale, hipStream_t stream);
+/* ug_attn_decode_fused for the VERIFY step of speculative decoding (ug_spec_verify below): the same inputs and the same finishing
+ * arithmetic, but the rows are `rows` CONSECUTIVE positions of ONE sequence, 1 <= rows <= UG_SPEC_MAX_ROWS.
+ *   acc_qkv fp32 [rows][ldacc], ss_in [rows], eps, norm_cols, bias, cos_tab / sin_tab, max_pos, scale: as above;
+ *   cache_k / cache_v: ONE cache row [1][HKV][Tmax][128]; key_valid [1][Tmax] or null; o bf16 [rows][ldo].
+ * With p = *pos_dev, row s sits at position p + s: its q / k / v are bf16(rstd * acc + bias), rotate-half RoPE with separately rounded
+ * products at table row min(p + s, max_pos - 1) -- the bits a one-row ug_attn_decode_fused launch at p + s builds -- and its k / v are
+ * appended at p + s when that is < Tmax.  Row s attends to the cache keys [0, min(p, Tmax)) that key_valid allows and to the new keys
+ * of rows 0 .. s of this launch, nothing else: no new key or value is read back from the cache (the workgroups of row s rebuild rows
+ * 0 .. s from the accumulator), so what is stored at or past p before the launch reaches no output, and output row s is the same bits
+ * whatever `rows` is and whatever rows > s hold.  Plain stores, no atomics.  A default-mode kernel: there is no ordered form. */
+#define UG_SPEC_MAX_ROWS 8
+int ug_attn_decode_seq(const float* acc_qkv, int64_t ldacc, const float* ss_in, float eps, int64_t norm_cols, const void* bias,
+                       const float* cos_tab, const float* sin_tab, const int* pos_dev, void* cache_k, void* cache_v,
+                       const uint8_t* key_valid, void* o, int64_t ldo, int64_t rows, int H, int HKV, int head_dim, int64_t Tmax,
+                       int64_t max_pos, float scale, hipStream_t stream);
 /* Single-writer decode projections (round 6; the same reference call sites: models/unigen.py:496-502 per-token forward, transformers
  * modeling_qwen2.py Qwen2DecoderLayer.forward / Qwen2MLP.forward / Qwen2Model.norm + lm_head).  Every output element has ONE writer -- a
  * workgroup owns a few weight rows for the whole contraction -- so these launches use no fp32 atomics and leave FINISHED values:
@@ -558,6 +573,35 @@ int ug_text_constrain(float* logits, int64_t ld, int64_t R, int64_t V, const voi
  * that is done -- by a stop id of this very step too -- is left alone: a row never finishes twice, whatever number of sequences match. */
 int ug_text_stop_seq(const int* seq_ids, const int* seq_off, int64_t ns, int64_t n_ids, const int* out_tokens, int64_t nsteps, int64_t R,
                      int* state, int* lengths, hipStream_t stream);
+
+/* ---- prompt-lookup speculative decoding of one greedy row (csrc/spec_decode.hip; the rules: csrc/spec_plan.h) ----
+ * One verify step runs the decoder stack on S = 1 + K rows: the last emitted token and a draft of up to K tokens copied from an earlier
+ * occurrence of the sequence's last ids (transformers' prompt_lookup_num_tokens), at consecutive positions of one cache row
+ * (ug_attn_decode_seq).  This entry point runs behind the head and owns everything a step decides; two launches, no host
+ * synchronisation, no shape depends on the step.
+ *   logits fp32 [rows][ld], V <= ld: the head's output for the step's rows; clear != 0 leaves the V read entries of every row zeroed.
+ *   tok int64 [next_rows]: the step's inputs, tok[0] = the last emitted token, tok[1 .. n_draft] the draft; rewritten for the next step.
+ *   state int32 [16]: [0] emitted, [1] done, [2] steps, [3] drafted, [4] accepted, [5] n_draft (of tok as it stands), [6] the
+ *   history's length, [8 + s] the picks of this call.  The host zeroes it at the start of a call and sets [6].
+ *   hist int32 [hist_cap]: the searchable history, state[6] ids of it filled (lookup ids, then the prompt's, then everything emitted).
+ *   (a) pick    g[s] = the LOWEST index attaining the maximum of the bf16-rounded logits of row s (ug_text_pick's steps 1 and 2);
+ *   (b) accept  a = the number of leading s < n_draft with g[s] == tok[s + 1];
+ *   (c) emit    g[0 .. a], cut after the first stop id (inclusive) and at `width`; either cut sets done (and lengths[0] = emitted, if
+ *               given).  The tokens go to out_tokens [width] and to the history; with pos / len given (a decoder step; both or neither)
+ *               *pos += the number emitted, *len = *pos + 1, ++steps, drafted += n_draft, accepted += a.  Both null: the first token,
+ *               picked from the prefill's hidden state, moves no position and counts no step.
+ *   (d) draft   on the history h[0, n): for G' = min(ngram, n - 1) down to 1 the smallest i with i + G' < n and
+ *               h[i, i + G') == h[n - G', n); the draft is h[i + G', min(i + G' + num_draft, n)); the first G' with a match wins, none
+ *               leaves n_draft = 0 (PromptLookupCandidateGenerator.get_candidates' rule);
+ *   (e) next    tok[0] = the last emitted token, tok[1 ..] = the draft, rows behind it repeat the last valid one (padding: finite,
+ *               their results are ignored); x[s] = embed[tok[s]] (H floats) for all next_rows rows.
+ * A call on a done state picks (and clears) and changes nothing else; the call that sets done leaves tok, x and n_draft as they were.
+ * rows, next_rows <= UG_SPEC_MAX_ROWS, num_draft < next_rows, 1 <= ngram <= 4, n_stop <= 8.  No atomics: a step is a function of its
+ * inputs. */
+int ug_spec_verify(float* logits, int64_t ld, int64_t rows, int64_t V, int clear, const int64_t* stop_ids, int64_t n_stop,
+                   const float* embed, int64_t ld_embed, int64_t embed_rows, int64_t H, int* state, int64_t width, int64_t* tok,
+                   int64_t next_rows, int* out_tokens, int* lengths, int* hist, int64_t hist_cap, int64_t ngram, int64_t num_draft,
+                   int* pos, int* len, float* x, hipStream_t stream);
 
 /* ---- loss ------------------------------------------------------------------------------------ */
 /* replaces: F.cross_entropy(ignore_index=-100) x3 in UniGen.forward (models/unigen.py:310-338) and

@@ -393,6 +393,157 @@ __global__ __launch_bounds__(64 * ADF_WAVES) void attn_decode_fused_kernel(
   }
 }
 
+// Cache attention of one VERIFY step of speculative decoding (ug_attn_decode_seq): the S rows of the raw qkv accumulator are S
+// CONSECUTIVE positions p, p + 1, ... of ONE sequence (one cache row), where attn_decode_fused_kernel's rows are independent sequences at
+// one position.  One workgroup per (row s, query head): it finishes q of row s and k / v of rows 0 .. s of its kv head from the
+// accumulator itself, with attn_decode_fused_kernel's arithmetic (the appended rows are the bits S one-row launches of that kernel
+// append), so no new key or value is ever read back from the cache -- another workgroup writes it and nothing orders the two.  The first
+// query head of a kv head appends ITS row's k / v at p + s.  Row s attends to the cache keys [0, min(p, Tmax)) that key_valid allows and
+// to the new keys 0 .. s; what the workgroup of row s computes does not depend on S or on rows > s.
+// Cache keys, 64 per wave and pass: lane (kq = lane >> 4, dc = lane & 15) loads the 16-byte piece dc of the keys 4 jj + kq -- every
+// load instruction covers four whole 256-byte rows, contiguous in the cache -- for K and V alike; a score is the 16-lane sum of the
+// pieces' partial dot products, after which every lane of the group holds the probability its V pieces need.  Plain loads and stores, no
+// atomics, 9.6 KB of LDS (no K tile: the 128 KB of the fused kernel would leave one workgroup per CU for S x H of them).
+constexpr int ADS_WAVES = 4;
+constexpr int ADS_MAX_ROWS = UG_SPEC_MAX_ROWS;
+__global__ __launch_bounds__(64 * ADS_WAVES) void attn_decode_seq_kernel(
+    const float* __restrict__ acc_qkv, const float* __restrict__ ss, const int* __restrict__ pos_dev, bf16_t* __restrict__ ck,
+    bf16_t* __restrict__ cv, int HKV, int H, int lda, int Tmax, int max_pos, const bf16_t* __restrict__ bias,
+    const float* __restrict__ cs, const float* __restrict__ sn, const uint8_t* __restrict__ key_valid, bf16_t* __restrict__ o, int64_t ldo,
+    float eps, int norm_cols, float scale) {
+  __shared__ float qs[DHD];
+  __shared__ float kn[ADS_MAX_ROWS][DHD], vn[ADS_MAX_ROWS][DHD];
+  __shared__ float om[ADS_WAVES][DHD];
+  __shared__ float ml[ADS_WAVES][2];
+  __shared__ float sc[ADS_MAX_ROWS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int h = blockIdx.x, s = blockIdx.y;
+  const int per = H / HKV;
+  const int hk = h / per, hq = h - hk * per;
+  const int pos0 = max(*pos_dev, 0);
+  // task 0: q of row s; tasks 1 + 2 j, 2 + 2 j: k, v of row j <= s.  A wave per task, lane l builds the rotate-half pair (l, l + 64).
+  for (int task = wave; task < 3 + 2 * s; task += ADS_WAVES) {
+    const int j = task == 0 ? s : (task - 1) >> 1;
+    const int kind = task == 0 ? 0 : 1 + ((task - 1) & 1);          // 0 q, 1 k, 2 v
+    const int col0 = kind == 0 ? h * DHD : kind == 1 ? (H + hk) * DHD : (H + HKV + hk) * DHD;
+    const float* arow = acc_qkv + (int64_t)j * lda;
+    const float ssr = ss[j];
+    const float a1 = arow[col0 + lane], a2 = arow[col0 + lane + DHD / 2];
+    const int rpos = min(pos0 + j, max_pos - 1);
+    float b1 = 0.f, b2 = 0.f, rc = 1.f, rsn = 0.f;
+    if (bias) { b1 = bf2f(bias[col0 + lane]); b2 = bf2f(bias[col0 + lane + DHD / 2]); }
+    if (kind < 2) { rc = cs[(int64_t)rpos * (DHD / 2) + lane]; rsn = sn[(int64_t)rpos * (DHD / 2) + lane]; }
+    float x1, x2;
+    {
+#pragma clang fp contract(off)
+      // attn_decode_fused_kernel's finishing, operation for operation: bf16(rstd * acc + bias), rotate-half with separately rounded products
+      const float rs = rsqrtf(ssr / (float)norm_cols + eps);
+      float v1 = rs * a1, v2 = rs * a2;
+      if (bias) { v1 += b1; v2 += b2; }
+      x1 = bf2f(f2bf(v1)); x2 = bf2f(f2bf(v2));
+      if (kind < 2) {
+        const float p1 = x1 * rc, p2 = x2 * rc;
+        const float q1 = x2 * rsn, q2 = x1 * rsn;
+        x1 = bf2f(f2bf(p1 - q1)); x2 = bf2f(f2bf(p2 + q2));
+      }
+    }
+    float* dst = kind == 0 ? qs : kind == 1 ? kn[j] : vn[j];
+    dst[lane] = x1; dst[lane + DHD / 2] = x2;
+    if (kind > 0 && j == s && hq == 0 && pos0 + s < Tmax) {
+      bf16_t* row = (kind == 1 ? ck : cv) + ((int64_t)hk * Tmax + pos0 + s) * DHD;
+      row[lane] = f2bf(x1); row[lane + DHD / 2] = f2bf(x2);
+    }
+  }
+  __syncthreads();
+  const int len = min(pos0, Tmax);                          // cache keys visible to every row of the step
+  const bf16_t* kb = ck + (int64_t)hk * Tmax * DHD;
+  const bf16_t* vb = cv + (int64_t)hk * Tmax * DHD;
+  const int kq = lane >> 4, dc = lane & 15;
+  float qf[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) qf[e] = qs[dc * 8 + e];
+  float m = -INFINITY, l = 0.f;
+  float acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+  for (int t0 = wave * 64; t0 < len; t0 += 64 * ADS_WAVES) {
+    bf16x8_t kf[16], vf[16];
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) {
+      const int64_t tt = min(t0 + jj * 4 + kq, len - 1);    // (nothing at or past len is ever read)
+      kf[jj] = *reinterpret_cast<const bf16x8_t*>(kb + tt * DHD + dc * 8);
+      vf[jj] = *reinterpret_cast<const bf16x8_t*>(vb + tt * DHD + dc * 8);
+    }
+    float sj[16];
+    float mc = -INFINITY;
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) {
+      float d = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) d += bf2f((bf16_t)kf[jj][e]) * qf[e];
+      d += __shfl_xor(d, 1, 64); d += __shfl_xor(d, 2, 64); d += __shfl_xor(d, 4, 64); d += __shfl_xor(d, 8, 64);
+      const int t = t0 + jj * 4 + kq;
+      sj[jj] = (t < len && (!key_valid || key_valid[t])) ? d * scale : -INFINITY;
+      mc = fmaxf(mc, sj[jj]);
+    }
+    mc = fmaxf(mc, __shfl_xor(mc, 16, 64));
+    mc = fmaxf(mc, __shfl_xor(mc, 32, 64));
+    const float mn = fmaxf(m, mc);
+    const float mu = (mn == -INFINITY) ? 0.f : mn;
+    const float alpha = __expf(m - mu);
+    m = mn;
+    float ps = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] *= alpha;
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) {
+      const float p = __expf(sj[jj] - mu);                  // 0 for keys past len / masked keys
+      ps += p;
+      const float pb = bf2f(f2bf(p));                       // P is rounded to bf16 before P.V like the bf16 SDPA paths
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += pb * bf2f((bf16_t)vf[jj][e]);
+    }
+    ps += __shfl_xor(ps, 16, 64);
+    ps += __shfl_xor(ps, 32, 64);
+    l = l * alpha + ps;
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    acc[e] += __shfl_xor(acc[e], 16, 64);
+    acc[e] += __shfl_xor(acc[e], 32, 64);
+  }
+  if (lane < 16) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) om[wave][dc * 8 + e] = acc[e];
+  }
+  if (lane == 0) { ml[wave][0] = m; ml[wave][1] = l; }
+  // the scores of the step's own keys 0 .. s (a wave each)
+  for (int j = wave; j <= s; j += ADS_WAVES) {
+    const float d = wave_sum(qs[lane] * kn[j][lane] + qs[lane + DHD / 2] * kn[j][lane + DHD / 2]) * scale;
+    if (lane == 0) sc[j] = d;
+  }
+  __syncthreads();
+  if (threadIdx.x < DHD) {
+    float M = sc[0];
+    for (int j = 1; j <= s; ++j) M = fmaxf(M, sc[j]);
+#pragma unroll
+    for (int w = 0; w < ADS_WAVES; ++w) M = fmaxf(M, ml[w][0]);
+    float L = 0.f, O = 0.f;
+    for (int j = 0; j <= s; ++j) {
+      const float wn = __expf(sc[j] - M);
+      L += wn;
+      O += wn * vn[j][threadIdx.x];
+    }
+#pragma unroll
+    for (int w = 0; w < ADS_WAVES; ++w) {
+      const float wgt = (ml[w][0] == -INFINITY) ? 0.f : __expf(ml[w][0] - M);
+      L += wgt * ml[w][1];
+      O += wgt * om[w][threadIdx.x];
+    }
+    o[(int64_t)s * ldo + h * DHD + threadIdx.x] = f2bf(O / L);
+  }
+}
+
 // Finish a split-K fp32 accumulation of a skinny GEMM:  mode 0: out_bf16 = bf16(acc + bias)
 //                                                      mode 1: resid_f32 += bf16round(acc)      (in place)
 __global__ __launch_bounds__(256) void skinny_finish_kernel(const float* __restrict__ acc, const bf16_t* __restrict__ bias,
@@ -1302,6 +1453,22 @@ extern "C" int ug_attn_decode_fused(const float* acc_qkv, int64_t ldacc, const f
   UG_REQUIRE(ldacc > 0 && ldacc < (1ll << 31), "ug_attn_decode_fused: ldacc out of range");
   return launch_attn_decode_fused("ug_attn_decode_fused", 0, acc_qkv, ldacc, ss_in, eps, norm_cols, bias, cos_tab, sin_tab, pos_dev, cache_k, cache_v,
                                   key_valid, o, ldo, rows, H, HKV, Tmax, max_pos, scale, st);
+}
+
+extern "C" int ug_attn_decode_seq(const float* acc_qkv, int64_t ldacc, const float* ss_in, float eps, int64_t norm_cols,
+                                  const void* bias, const float* cos_tab, const float* sin_tab, const int* pos_dev, void* cache_k,
+                                  void* cache_v, const uint8_t* key_valid, void* o, int64_t ldo, int64_t rows, int H, int HKV,
+                                  int head_dim, int64_t Tmax, int64_t max_pos, float scale, hipStream_t st) {
+  UG_REQUIRE(head_dim == DHD && rows >= 1 && rows <= ADS_MAX_ROWS && HKV > 0 && H > 0 && H % HKV == 0 && H <= 1024 && Tmax > 0 &&
+                 Tmax < (1ll << 24) && max_pos > 0 && max_pos < (1ll << 24) && norm_cols > 0 && acc_qkv && ss_in && cos_tab && sin_tab &&
+                 pos_dev && cache_k && cache_v && o,
+             "ug_attn_decode_seq: bad args (head_dim 128, 1 <= rows <= %d consecutive positions of one sequence)", ADS_MAX_ROWS);
+  UG_REQUIRE(ldacc >= (int64_t)(H + 2 * HKV) * DHD && ldacc < (1ll << 27) && ldo >= (int64_t)H * DHD && ug_aligned16(cache_k) &&
+                 ug_aligned16(cache_v),
+             "ug_attn_decode_seq: ldacc / ldo below the q/k/v width or out of range, or a cache that is not 16-byte aligned");
+  return ug_launch("ug_attn_decode_seq", attn_decode_seq_kernel, dim3((unsigned)H, (unsigned)rows), dim3(64 * ADS_WAVES), st, acc_qkv, ss_in,
+                   pos_dev, (bf16_t*)cache_k, (bf16_t*)cache_v, HKV, H, (int)ldacc, (int)Tmax, (int)max_pos, (const bf16_t*)bias, cos_tab,
+                   sin_tab, key_valid, (bf16_t*)o, ldo, eps, (int)norm_cols, scale);
 }
 
 extern "C" int ug_skinny_finish(const float* acc, const void* bias, void* out_bf16, float* resid, int64_t M, int64_t N,

@@ -249,6 +249,7 @@ class TextCall:
     deterministic: bool
     use_graph: bool
     trace: Optional[list]
+    spec: Optional[tuple] = None    # prompt-lookup speculative decoding: None (off) or (K, G, lookup ids or None) (checked_prompt_lookup)
 
     @property
     def stops(self):
@@ -282,9 +283,52 @@ def mmu_rule(temperature, top_k):
     return (lambda last: UniGen._process_next(last, temperature, top_k)), (lambda scores: UniGen._choose_next(scores, temperature))
 
 
+SPEC_REFUSED = ("repetition_penalty", "logit_bias", "suppress_tokens", "min_new_tokens", "no_repeat_ngram_size", "stop_sequences",
+                "return_logprobs", "deterministic", "num_return_sequences", "on_device")
+
+
+def checked_prompt_lookup(who, vocab, sampling, given, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, lookup_ids=None):
+    """The speculative-decoding option of a call -> None (prompt_lookup_num_tokens None or 0: off, and nothing else is looked at) or
+    (K, G, lookup ids as a long 1-D tensor or None).  On: K = 1 .. 7 draft tokens per step, G = 1 .. 4 (default 2, transformers')
+    ids at most matched; the call must pick greedily, and `given` -- the values of the options in SPEC_REFUSED as the call resolved
+    them -- must all be off: each one that is not is refused by name, before any launch."""
+    if prompt_lookup_num_tokens is None or int(prompt_lookup_num_tokens) == 0:
+        return None
+    K, G = int(prompt_lookup_num_tokens), 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
+    if not 1 <= K <= ops.SPEC_MAX_ROWS - 1:
+        raise UniGenHipError(f"{who}: prompt_lookup_num_tokens={K} must be between 1 and {ops.SPEC_MAX_ROWS - 1}")
+    if not 1 <= G <= ops.SPEC_MAX_NGRAM:
+        raise UniGenHipError(f"{who}: max_matching_ngram_size={G} must be between 1 and {ops.SPEC_MAX_NGRAM}")
+    off = {"repetition_penalty": (None, 1, 1.0), "min_new_tokens": (None, 0), "no_repeat_ngram_size": (None, 0),
+           "num_return_sequences": (None, 1), "on_device": (None, True)}
+    refused = [k for k in SPEC_REFUSED if given.get(k) not in off.get(k, (None, False)) and given.get(k) != [] and given.get(k) != {}]
+    if refused:
+        raise UniGenHipError(f"{who}: {refused} are not implemented with prompt_lookup_num_tokens (one greedy row on the device loop, "
+                             f"default decode mode)")
+    if sampling is not None:
+        raise UniGenHipError(f"{who}: prompt_lookup_num_tokens needs greedy picking (do_sample=False; temperature 0 or top_k=1 in the mmu "
+                             f"calls): only tokens the model itself would pick are accepted")
+    if lookup_ids is not None:
+        if not torch.is_tensor(lookup_ids) or lookup_ids.dim() != 1 or lookup_ids.dtype != torch.long:
+            raise UniGenHipError(f"{who}: lookup_ids must be a long 1-D tensor of token ids")
+        V = int(vocab())
+        if lookup_ids.numel() and not (0 <= int(lookup_ids.min()) and int(lookup_ids.max()) < V):
+            raise UniGenHipError(f"{who}: lookup_ids outside [0, {V})")
+    return K, G, lookup_ids
+
+
+def check_spec_call(call, rows, engine):
+    """what a speculative call checks once its prompt's shape is at hand, still before any launch: one row, and an engine whose
+    verify step takes the sw or splitk form (Qwen2Engine.spec_form raises, naming the form)"""
+    if rows != 1:
+        raise UniGenHipError(f"{call.who}: prompt_lookup_num_tokens serves one row per call, got {rows} (rows > 1 need per-row cache "
+                             f"positions)")
+    engine.spec_form(call.spec[0] + 1)
+
+
 def text_call(who, vocab, sampling, rule, stop, pad_finished=False, pad_token_id=None, generator=None, repetition_penalty=None,
               deterministic=None, return_logprobs=False, use_graph=True, trace=None, logit_bias=None, suppress_tokens=None,
-              min_new_tokens=None, no_repeat_ngram_size=None, stop_sequences=None):
+              min_new_tokens=None, no_repeat_ngram_size=None, stop_sequences=None, prompt_lookup=None):
     """The TextCall of one public call, with every check that needs no prompt, before any launch.  vocab: a callable that returns V
     (checked_constraints).  rule: the (process, choose) of generate_rule / mmu_rule.  stop: the caller's stop ids in any form
     stop_list takes -- a device tensor is read here, once; the stop sequences of one id join them unless already there (the caller's
@@ -292,8 +336,18 @@ def text_call(who, vocab, sampling, rule, stop, pad_finished=False, pad_token_id
     stop id, and stop sequences need one of the two.
     host_stop keeps the operand of the host loop's per-token compare what each entry point has always handed emit_until_stop (the
     same launches): `generate` a tensor of the ids, or None when no row can finish; the mmu entry points the caller's own id or
-    tensor while nothing was merged into it and no constraint is on, else the list (a list becomes a tensor: text_pick_emit)."""
+    tensor while nothing was merged into it and no constraint is on, else the list (a list becomes a tensor: text_pick_emit).
+    prompt_lookup: None, or the dict of the entry point's prompt_lookup_num_tokens / max_matching_ngram_size / lookup_ids with its
+    on_device and num_return_sequences (checked_prompt_lookup: resolved here, where the other options are)."""
     from unigen_hip.qwen2 import resolve_deterministic
+    det = resolve_deterministic(deterministic)
+    spec = None
+    if prompt_lookup:
+        given = dict(repetition_penalty=repetition_penalty, logit_bias=logit_bias, suppress_tokens=suppress_tokens, min_new_tokens=min_new_tokens,
+                     no_repeat_ngram_size=no_repeat_ngram_size, stop_sequences=stop_sequences, return_logprobs=bool(return_logprobs),
+                     deterministic=det, num_return_sequences=prompt_lookup.get("num_return_sequences"), on_device=prompt_lookup.get("on_device"))
+        spec = checked_prompt_lookup(who, vocab, sampling, given, **{k: prompt_lookup.get(k) for k in
+                                                                      ("prompt_lookup_num_tokens", "max_matching_ngram_size", "lookup_ids")})
     penalty = checked_repetition_penalty(repetition_penalty, who)
     cons, singles = checked_constraints(who, vocab, logit_bias, suppress_tokens, min_new_tokens, no_repeat_ngram_size, stop_sequences)
     ids = stop_list(stop)
@@ -308,12 +362,12 @@ def text_call(who, vocab, sampling, rule, stop, pad_finished=False, pad_token_id
     else:
         host_stop = ids if cons is not None or singles or isinstance(stop, (list, tuple)) else stop
     return TextCall(who, sampling, rule[0], rule[1], generator, ids, host_stop, pad_token_id, penalty, cons, bool(return_logprobs),
-                    resolve_deterministic(deterministic), bool(use_graph), trace)
+                    det, bool(use_graph), trace, spec)
 
 
 def generate_call(vocab, do_sample, temperature, top_k, top_p, eos_token_id, pad_token_id, generator, deterministic, return_logprobs,
-                  kwargs):
-    """`generate`'s arguments -> (TextCall, num_return_sequences)"""
+                  kwargs, prompt_lookup=None):
+    """`generate`'s arguments -> (TextCall, num_return_sequences).  prompt_lookup: text_call's, without num_return_sequences"""
     unsupported = [k for k in ("num_beams", "penalty_alpha") if kwargs.get(k) not in (None, 1, 1.0)]
     if unsupported:
         raise UniGenHipError(f"generate: {unsupported} are not implemented in generate (greedy / sampling only): call UniGen.beam_search")
@@ -323,6 +377,7 @@ def generate_call(vocab, do_sample, temperature, top_k, top_p, eos_token_id, pad
     call = text_call("generate", vocab, sampling, generate_rule(do_sample, temperature, top_k, top_p, generator), eos_token_id,
                      pad_finished=True, pad_token_id=pad_token_id, generator=generator, deterministic=deterministic,
                      return_logprobs=return_logprobs, use_graph=kwargs.get("use_graph", True), trace=kwargs.get("trace"),
+                     prompt_lookup=prompt_lookup and dict(prompt_lookup, num_return_sequences=kwargs.get("num_return_sequences")),
                      **{k: kwargs.get(k) for k in ("repetition_penalty", "logit_bias", "suppress_tokens", "min_new_tokens",
                                                    "no_repeat_ngram_size", "stop_sequences")})
     n_ret = kwargs.get("num_return_sequences")
@@ -373,6 +428,9 @@ def beam_call(rows, max_new_tokens, num_beams, num_return_sequences, length_pena
 def mmu_call(who, vocab, temperature, top_k, eot_token, **how):
     """the arguments of `mmu_generate` / `mmu_generate_batch` -> TextCall (temperature 0 is greedy; `how`: text_call's keywords)"""
     sampling = (float(temperature), int(top_k or 0), 1.0) if temperature > 0 else None
+    lookup = how.get("prompt_lookup")
+    if lookup and lookup.get("prompt_lookup_num_tokens") and top_k == 1:
+        sampling = None                             # (top_k=1 keeps the maximum alone: greedy, whatever the temperature)
     return text_call(who, vocab, sampling, mmu_rule(temperature, top_k), eot_token, **how)
 
 
@@ -1098,6 +1156,7 @@ class UniGen(ModelMixin, ConfigMixin):
         if eng is not None:
             eng._ar_session = None
             eng._text_session = None              # (the on-device text loop keeps one too: _decode_text_on_device)
+            eng._spec_session = None              # (and its speculative form: _decode_text_spec)
 
     def train(self, mode: bool = True):
         if mode:
@@ -1264,7 +1323,8 @@ class UniGen(ModelMixin, ConfigMixin):
     @torch.no_grad()
     def generate(self, input_ids=None, input_embeddings=None, attention_mask=None, max_new_tokens=20, do_sample=False,
                  temperature=1.0, top_k=None, top_p=None, eos_token_id=None, pad_token_id=None, use_cache=True,
-                 generator=None, deterministic=None, on_device=None, return_logprobs=False, **kwargs):
+                 generator=None, deterministic=None, on_device=None, return_logprobs=False, prompt_lookup_num_tokens=None,
+                 max_matching_ngram_size=None, lookup_ids=None, **kwargs):
         """Causal text generation with the conventions of transformers' `generate`, which the reference delegates to
         (models/unigen.py:584-588; caller evaluation/inference_unigen_cot.py:360): prompts as ids [B, L] or as
         `input_embeddings` [B, L, H] with an optional 2-D [B, L] key-validity mask (left padding); greedy when
@@ -1309,9 +1369,24 @@ class UniGen(ModelMixin, ConfigMixin):
         return_logprobs reports the log-softmax of the constrained scores.  Both loops; the on-device loop serves 1024 bias + suppress
         entries, n <= 16 and 8 stop sequences of at most 16 ids (an explicit on_device=True beyond that raises, a default-derived one
         falls back to the host loop).  An id in both lists, twice in one, or outside [0, V) raises before any launch.
+        prompt_lookup_num_tokens=K (1 .. 7; None or 0: off, the paths above untouched), max_matching_ngram_size=G (1 .. 4, default 2),
+        lookup_ids (a long 1-D tensor or None): prompt-lookup speculative decoding, transformers' option of the same name.  Every
+        decode step runs K + 1 positions of the one row -- the last token and a draft of up to K tokens copied from behind the earliest
+        earlier occurrence of the sequence's last G' <= G ids -- and keeps the longest prefix of the draft that the model's own greedy
+        picks confirm, plus the pick behind it: the tokens are the plain device loop's, up to near-ties between the step forms.  The
+        searched history is `lookup_ids` (extra text that is not part of the prompt: for prompts given as embeddings, whose image span
+        has no ids), then the prompt's ids, then everything emitted.  Selects the on-device loop; needs one row and do_sample=False, the
+        sw or splitk decode form and the default decode mode; repetition_penalty, logit_bias, suppress_tokens, min_new_tokens,
+        no_repeat_ngram_size, stop_sequences, return_logprobs, deterministic, num_return_sequences > 1 and on_device=False are refused
+        by name.  `engine.last_spec_stats` = {steps, drafted, accepted, emitted} of the call (Qwen2Engine.spec_step).
         num_beams and penalty_alpha are refused."""
+        lookup = dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
+                      lookup_ids=lookup_ids, on_device=on_device)
         call, n_ret = generate_call(lambda: self.config.vocab_size, do_sample, temperature, top_k, top_p, eos_token_id, pad_token_id, generator,
-                                    deterministic, return_logprobs, kwargs)
+                                    deterministic, return_logprobs, kwargs, prompt_lookup=lookup)
+        if call.spec is not None:
+            check_spec_call(call, int((input_ids if input_embeddings is None else input_embeddings).shape[0]), self.llm.engine)
+            on_device = True
         if n_ret > 1:
             input_ids = None if input_ids is None else input_ids.repeat_interleave(n_ret, dim=0)
             input_embeddings = None if input_embeddings is None else input_embeddings.repeat_interleave(n_ret, dim=0)
@@ -1472,7 +1547,8 @@ class UniGen(ModelMixin, ConfigMixin):
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
                      top_k=None, eot_token=None, use_cache=True, deterministic=None, on_device=None, use_graph=True, repetition_penalty=1.0,
                      return_logprobs=False, trace=None, prefix=None, logit_bias=None, suppress_tokens=None, min_new_tokens=None,
-                     no_repeat_ngram_size=None, stop_sequences=None):
+                     no_repeat_ngram_size=None, stop_sequences=None, prompt_lookup_num_tokens=None, max_matching_ngram_size=None,
+                     lookup_ids=None):
         """Greedy / top-k text continuation (reference models/unigen.py:523-581).  The reference re-runs the whole
         growing sequence every step and extends the additive mask by one row that copies the previous last row;
         here the prompt is prefilled once under its mask into the static KV cache and every new token is one decode
@@ -1490,7 +1566,14 @@ class UniGen(ModelMixin, ConfigMixin):
         logit_bias, suppress_tokens, min_new_tokens, no_repeat_ngram_size, stop_sequences: as in `generate`, cached form only (both loops);
         min_new_tokens holds `eot_token` back, a stop sequence ends the list like `eot_token` does.  The recompute form raises for them.
         prefix: an `mmu_prefix` object; `idx` / `input_embeddings` are then only the continuation [1, S], which is causal (no
-        attention_mask) and sees of the prefix what its mask's last row saw.  Cached form only; everything else as without."""
+        attention_mask) and sees of the prefix what its mask's last row saw.  Cached form only; everything else as without.
+        prompt_lookup_num_tokens, max_matching_ngram_size, lookup_ids: prompt-lookup speculative decoding as in `generate`, cached form
+        only, with or without a prefix; needs temperature == 0 or top_k == 1.  The searched history is lookup_ids, then the ids the
+        repetition penalty would count (the prefix's and `idx` at the keys the last row sees), then everything emitted -- with an
+        `input_embeddings` prompt (an image span has no ids) lookup_ids is all there is to search at first, e.g. the generation prompt's
+        tokens when an image is rated against it."""
+        lookup = dict(prompt_lookup_num_tokens=prompt_lookup_num_tokens, max_matching_ngram_size=max_matching_ngram_size,
+                      lookup_ids=lookup_ids, on_device=on_device)
         if prefix is not None:
             check_mmu_prefix_call("mmu_generate", self.llm.engine, prefix, idx, input_embeddings, attention_mask, None)
             if (idx if input_embeddings is None else input_embeddings).shape[0] != 1:
@@ -1500,7 +1583,10 @@ class UniGen(ModelMixin, ConfigMixin):
         call = mmu_call("mmu_generate", lambda: self.config.vocab_size, temperature, top_k, eot_token, repetition_penalty=repetition_penalty,
                         deterministic=deterministic, return_logprobs=return_logprobs, use_graph=use_graph, trace=trace, logit_bias=logit_bias,
                         suppress_tokens=suppress_tokens, min_new_tokens=min_new_tokens, no_repeat_ngram_size=no_repeat_ngram_size,
-                        stop_sequences=stop_sequences)
+                        stop_sequences=stop_sequences, prompt_lookup=lookup)
+        if call.spec is not None:
+            check_spec_call(call, int((idx if input_embeddings is None else input_embeddings).shape[0]), self.llm.engine)
+            on_device = True
         eng = self.llm.engine
         eng.last_decode_deterministic = call.deterministic
         cached = prefix is not None or bool(use_cache and attention_mask is not None and attention_mask.shape[0] == 1)
@@ -1592,6 +1678,8 @@ class UniGen(ModelMixin, ConfigMixin):
         options launch: include/unigen_hip.h and TextDecodeSession.
         -> (tokens int64 [R, steps], lengths int64 [R], steps, log-probabilities fp32 [R, steps] or None)."""
         from unigen_hip.qwen2 import TextDecodeSession, decode_loop, put_session, take_session
+        if call.spec is not None:
+            return self._decode_text_spec(call, prompt, max_new_tokens)
         eng = self.llm.engine
         dev = eng.device
         R, L, key_valid, cons, det = prompt.rows, prompt.L, prompt.key_valid, call.constraints, call.deterministic
@@ -1633,6 +1721,49 @@ class UniGen(ModelMixin, ConfigMixin):
         logp = sess.logp[:, :steps].clone() if call.return_logprobs else None
         put_session(eng, "_text_session", sess, call.use_graph)
         return tokens, lengths, steps, logp
+
+    def _decode_text_spec(self, call, prompt, max_new_tokens):
+        """_decode_text_on_device for a call with prompt-lookup speculative decoding (call.spec = (K, G, lookup ids)): prefill, token 0
+        eagerly from the prefill's hidden state (Qwen2Engine.spec_first_token), then decode_loop over verify steps of K + 1 rows
+        (Qwen2Engine.spec_step: step 1 eagerly, step 2 captured, replays from there).  A step emits between one and K + 1 tokens and the
+        device cuts the emission at the stop id and at max_new_tokens, so the host only needs to know when to stop launching: it reads
+        `done` every 4 steps.  The session (SpecDecodeSession) is kept on the engine like the plain loop's, under a key of every size
+        and constant the captured step holds.  Sets eng.last_spec_stats.  -> _decode_text_on_device's tuple."""
+        from unigen_hip.qwen2 import SpecDecodeSession, decode_loop, put_session, take_session
+        eng = self.llm.engine
+        dev = eng.device
+        (K, G, lookup), L, key_valid = call.spec, prompt.L, prompt.key_valid
+        n, V = int(max_new_tokens), self.config.vocab_size
+        history = [torch.zeros(0, dtype=torch.long, device=dev) if lookup is None else lookup.to(dev)]
+        if prompt.prompt_ids is not None:
+            ids = prompt.prompt_ids[0].to(dev).long()
+            ok = (ids >= 0) & (ids < V)
+            if prompt.prompt_valid is not None:
+                ok &= prompt.prompt_valid[0].to(dev) != 0
+            history.append(ids[ok])
+        history = torch.cat(history).int()
+        cap = ops.round_up(L + n + K, 128)
+        hist_cap = ops.round_up(int(history.numel()) + n, 256)
+        key = (cap, n, V, eng.spec_form(K + 1), K, G, hist_cap, tuple(call.stop), key_valid is None, str(dev)) + eng.storage_key(cap)
+        sess = take_session(eng, "_spec_session", key, call.use_graph)
+        if sess is None:
+            sess = SpecDecodeSession(eng, cap, n, V, K, G, hist_cap, stop_ids=call.stop, key_valid=key_valid)
+            sess.key = key
+            sess.begin(history)
+        else:
+            sess.begin(history, key_valid, L)
+        hn = prompt.prefill(eng, sess.st)
+        eng.check_errors()
+        eng.spec_first_token(sess, hn)
+        done = lambda i: i % 4 == 1 and int(sess.state[ops.SPEC_DONE]) != 0        # (asked before step i: one host read per 4 steps)
+        if decode_loop(sess, lambda: eng.spec_step(sess), range(1, n), call.use_graph, stop=done):
+            eng.text_graph_captures = getattr(eng, "text_graph_captures", 0) + 1
+        eng.last_spec_stats = sess.stats()
+        steps = eng.last_spec_stats["emitted"]
+        eng.last_decode_graph = sess.graph is not None
+        tokens, lengths = sess.out_tokens[None, :steps].long(), sess.lengths.long()    # (copies: the next call overwrites the session's)
+        put_session(eng, "_spec_session", sess, call.use_graph)
+        return tokens, lengths, steps, None
 
     def _decode_text(self, st, hn, max_new_tokens, pick, emit):
         """text_token_loop on this model's engine from a prefilled state: vocabulary logits, embedding table, decode_step."""

@@ -101,6 +101,8 @@ def family_of(name):
         return "tokenizer_and_towers"
     if name in ("ug_adamw_flat", "ug_adamw_flat_dev"):
         return "adamw"
+    if name in ("ug_attn_decode_seq", "ug_spec_verify"):
+        return "spec_decode"                    # the two launches a speculative verify step adds to the decode forms' own
     return "elementwise"
 
 

@@ -651,6 +651,39 @@ def attn_decode_fused(acc_qkv, ss_in, eps, norm_cols, bias, cos, sin, pos_dev, c
     return out
 
 
+def attn_decode_seq(acc_qkv, ss_in, eps, norm_cols, bias, cos, sin, pos_dev, cache_k, cache_v, key_valid, out, H, HKV, hd, Tmax,
+                    scale=None):
+    """attn_decode_fused's arguments, read differently: the rows of acc_qkv are CONSECUTIVE positions *pos_dev, *pos_dev + 1, ... of the
+    ONE sequence in cache_k / cache_v [1, HKV, Tmax, hd] (include/unigen_hip.h: ug_attn_decode_seq; at most SPEC_MAX_ROWS rows)."""
+    scale = 1.0 / math.sqrt(hd) if scale is None else scale
+    if cache_k.shape[0] != 1 or cache_v.shape[0] != 1 or (key_valid is not None and key_valid.shape[0] != 1):
+        raise _l.UniGenHipError("attn_decode_seq: the rows are positions of ONE sequence: the cache and key_valid hold one row")
+    _l.api().ug_attn_decode_seq(_p(acc_qkv), acc_qkv.stride(0), _p(ss_in), eps, norm_cols, _p(bias), _p(cos), _p(sin),
+                                _p(pos_dev), _p(cache_k), _p(cache_v), _p(key_valid), _p(out), out.stride(0),
+                                acc_qkv.shape[0], H, HKV, hd, Tmax, cos.shape[0], scale, _stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------ prompt-lookup speculative decoding
+SPEC_MAX_ROWS, SPEC_MAX_NGRAM = 8, 4       # include/unigen_hip.h: UG_SPEC_MAX_ROWS; csrc/spec_plan.h
+SPEC_STATE_INTS = 16                       # emitted, done, steps, drafted, accepted, n_draft, history length, -, picks[8]
+SPEC_EMITTED, SPEC_DONE, SPEC_STEPS, SPEC_DRAFTED, SPEC_ACCEPTED, SPEC_NDRAFT, SPEC_HIST_LEN, SPEC_PICK = 0, 1, 2, 3, 4, 5, 6, 8
+
+
+def spec_verify_(logits, rows, V, state, width, embed_master, tok, out_tokens, x, hist, ngram, num_draft, clear=False, stop_ids=None,
+                 lengths=None, advance=None):
+    """The token side of one verify step of prompt-lookup speculative decoding behind the head (include/unigen_hip.h: ug_spec_verify):
+    pick of the first `rows` rows of fp32 logits [>= rows, ld >= V], accept, emit, history, next draft, next tok int64 [S] and x fp32
+    [S, H].  state: int32 [SPEC_STATE_INTS]; out_tokens int32 [width]; hist int32 [capacity]; advance = (pos, len) of the decode state
+    (None: the first token, which moves no position)."""
+    _need_cuda(logits, state, embed_master, tok, out_tokens, x, hist)
+    pos, ln = advance if advance is not None else (None, None)
+    _l.api().ug_spec_verify(_p(logits), logits.stride(0), int(rows), int(V), int(bool(clear)), _p(stop_ids),
+                            0 if stop_ids is None else stop_ids.numel(), _p(embed_master), embed_master.stride(0), embed_master.shape[0],
+                            embed_master.shape[1], _p(state), int(width), _p(tok), tok.numel(), _p(out_tokens), _p(lengths), _p(hist),
+                            hist.numel(), int(ngram), int(num_draft), _p(pos), _p(ln), _p(x), _stream())
+
+
 # ------------------------------------------------------------------------------------ ordered (deterministic) decode forms
 # Every split-K product lands in slots of its own by plain stores and is summed by its consumer in ascending slot order (fp32), then
 # rounded as the default form rounds it: bit-reproducible run to run (include/unigen_hip.h, "Ordered (deterministic) decode forms").

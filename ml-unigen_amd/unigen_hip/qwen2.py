@@ -188,10 +188,13 @@ class DecodeState:
     position and visible length as DEVICE ints (so one captured graph serves every step).
     deterministic: the decode steps on this state use the ORDERED forms (no float atomics: every split-K partial lands in a slot
     of its own and its consumer sums the slots in ascending order), so the same inputs give the same bits on every run, eager or
-    captured.  The state's scratch is then partial slots instead of accumulators, so a captured step belongs to one mode."""
+    captured.  The state's scratch is then partial slots instead of accumulators, so a captured step belongs to one mode.
+    step_rows: the rows of a decode step's operands and scratch -- `rows` (the default) everywhere except in a speculative session
+    (SpecDecodeSession), whose step rows are consecutive positions of its ONE cache row."""
 
-    def __init__(self, dims, rows, Tmax, device, key_valid=None, deterministic=False):
+    def __init__(self, dims, rows, Tmax, device, key_valid=None, deterministic=False, step_rows=None):
         self.rows, self.Tmax = rows, Tmax
+        self.step_rows = rows if step_rows is None else int(step_rows)
         self.deterministic = bool(deterministic)
         n, hk, hd = dims.num_hidden_layers, dims.num_key_value_heads, dims.head_dim
         self.k = [torch.zeros((rows, hk, Tmax, hd), dtype=torch.bfloat16, device=device) for _ in range(n)]
@@ -225,7 +228,7 @@ class DecodeState:
         if getattr(self, {"splitk": "acc_gu", "sw": "acc_down2", "ord_sw": "qkv_part"}[form], None) is not None:
             return                                 # (every step asks; the buffer only this form has says it is all there)
         dev = self.pos.device
-        R, H, I = self.rows, dims.hidden_size, dims.intermediate_size
+        R, H, I = self.step_rows, dims.hidden_size, dims.intermediate_size
         nqkv = (dims.num_attention_heads + 2 * dims.num_key_value_heads) * dims.head_dim
         z = lambda *shape: lambda: torch.zeros(shape, dtype=torch.float32, device=dev)
         e = lambda *shape: lambda: torch.empty(shape, dtype=torch.float32, device=dev)
@@ -356,6 +359,51 @@ class ArDecodeSession:
             self.st.key_valid[:, :self.P].copy_(key_valid)
         if self.uniforms is not None:
             self.uniforms.copy_(self.draw_uniforms(generator))
+
+
+class SpecDecodeSession:
+    """Everything a verify step of prompt-lookup speculative decoding reads or writes (Qwen2Engine.spec_step), kept across calls with
+    the captured step like TextDecodeSession: ONE greedy row whose step runs S = num_draft + 1 rows -- the last emitted token and a draft
+    of up to num_draft tokens, at consecutive positions of the one cache row.  A one-row DecodeState of `capacity` >= prompt +
+    max_new_tokens + num_draft positions with S step rows, the inputs `x` fp32 [S, H] and `tok` int64 [S], the head's logits
+    [S, round_up(vocab, 8)], the state block (ops.SPEC_*: emitted, done, the counters, the draft length of `tok`, the history's
+    length), the searchable history `hist` int32 [hist_cap] (lookup ids, then the prompt's, then everything emitted), the token
+    buffer and the row's length.  new_tokens is a kernel argument of the captured step (the width the emission is cut at)."""
+
+    def __init__(self, eng, capacity, new_tokens, vocab, num_draft, ngram, hist_cap, stop_ids=(), key_valid=None):
+        dev, d = eng.device, eng.dims
+        self.S, self.K, self.G, self.V, self.n = num_draft + 1, int(num_draft), int(ngram), vocab, int(new_tokens)
+        self.form = eng.spec_form(self.S)
+        self.st = DecodeState(d, 1, capacity, dev, key_valid=key_valid, step_rows=self.S)
+        self.state = torch.zeros(ops.SPEC_STATE_INTS, dtype=torch.int32, device=dev)
+        self.x = torch.zeros((self.S, d.hidden_size), dtype=torch.float32, device=dev)
+        self.tok = torch.zeros((self.S,), dtype=torch.long, device=dev)
+        self.logits = torch.zeros((self.S, ops.round_up(vocab, 8)), dtype=torch.float32, device=dev)
+        self.out_tokens = torch.zeros((ops.round_up(self.n, 64),), dtype=torch.int32, device=dev)
+        self.lengths = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.hist = torch.zeros((int(hist_cap),), dtype=torch.int32, device=dev)
+        self.stop_ids = torch.tensor([int(s) for s in stop_ids], dtype=torch.long, device=dev) if len(stop_ids) else None
+        self.graph, self.key = None, None
+
+    def begin(self, history, key_valid=None, prompt_len=0):
+        """the host's part of a call's start: the state block zeroed, the history = `history` (int 1-D: lookup ids, then the prompt's
+        valid ids), and (a reused session) the key-validity columns.  The prefill sets position and length."""
+        n = int(history.numel())
+        if n + self.n > self.hist.numel():
+            raise UniGenHipError(f"SpecDecodeSession: a history of {n} ids + {self.n} new tokens exceeds the session's {self.hist.numel()}")
+        self.state.zero_()
+        self.state[ops.SPEC_HIST_LEN:ops.SPEC_HIST_LEN + 1].fill_(n)
+        self.hist[:n].copy_(history)
+        self.lengths.fill_(self.n)
+        self.logits.zero_()                         # (the first token's GEMV head adds into row 0; the splitk head into all rows)
+        if key_valid is not None:
+            self.st.key_valid[:, :prompt_len].copy_(key_valid)
+            self.st.key_valid[:, prompt_len:].fill_(1)
+
+    def stats(self):
+        """-> {steps, drafted, accepted, emitted} of the call so far (one host read)"""
+        s = self.state.tolist()
+        return {"steps": s[ops.SPEC_STEPS], "drafted": s[ops.SPEC_DRAFTED], "accepted": s[ops.SPEC_ACCEPTED], "emitted": s[ops.SPEC_EMITTED]}
 
 
 def _keeping(wanted):
@@ -772,7 +820,7 @@ class Qwen2Engine:
             ops.decode_sw_kblock_ord_(st.act, fp.w(f"l{i}.wdown"), st.down_part)
         return bufs[n & 1], st.down_part
 
-    def _decode_layers_sw(self, st, x):
+    def _decode_layers_sw(self, st, x, attn=ops.attn_decode_fused):
         """The decoder stack of one decode step, five launches per layer (measured forms: profiles/r06_decode_forms.md):
           q/k/v      split-K (operand = the stream + the previous layer's pending down projection; leaves a raw accumulator)
           attention  finishes q/k/v from that accumulator, appends k / v, attends to the cache
@@ -782,10 +830,12 @@ class Qwen2Engine:
         -> (stream, pending): the residual stream after the last layer is stream + bf16round(pending).
         Accumulators: layer i adds into accd[i & 1] and clears accd[(i + 1) & 1].  `pending` is accd[(n - 1) & 1]; its reader may
         leave it uncleared (the head launch of decode_step_logits does).  At even depth that is accd[1], which layer 0's down projection
-        clears; at odd depth it is accd[0], the one layer 0 adds into, so layer 0's q/k/v launch clears it first (even depth: no clear)."""
+        clears; at odd depth it is accd[0], the one layer 0 adds into, so layer 0's q/k/v launch clears it first (even depth: no clear).
+        attn: the attention launch -- ops.attn_decode_fused, or ops.attn_decode_seq for a speculative verify step (spec_step); the two
+        take the same arguments."""
         d, fp = self.dims, self.fp
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
-        R, H = st.rows, d.hidden_size
+        R, H = st.step_rows, d.hidden_size
         cos, sin = self.rope(st.Tmax)
         st.ensure_scratch(d, "sw")
         eps = d.rms_norm_eps
@@ -802,21 +852,20 @@ class Qwen2Engine:
             # head reads it without clearing it, so layer 0's q/k/v launch clears it (even depth: layer 0's down clears accd[1] itself)
             clr = accd[0] if i == 0 and n & 1 else None
             ops.decode_gemv_resid_norm_(xin, pend, fp.p(f"l{i}.ln1"), xout, st.ss_attn, fp.w(f"l{i}.wqkv"), st.acc_qkv, zero1=clr)
-            ops.attn_decode_fused(st.acc_qkv, st.ss_attn, eps, H, fp.w(f"l{i}.bqkv"), cos, sin, st.pos, st.k[i], st.v[i],
-                                  st.key_valid, o, Hq, Hk, hd, st.Tmax)
+            attn(st.acc_qkv, st.ss_attn, eps, H, fp.w(f"l{i}.bqkv"), cos, sin, st.pos, st.k[i], st.v[i], st.key_valid, o, Hq, Hk, hd, st.Tmax)
             ops.decode_sw_resid_(o, fp.w(f"l{i}.wo"), xout)
             ops.decode_sw_gate_up_(xout, fp.p(f"l{i}.ln2"), eps, fp.w(f"l{i}.wgu"), st.act)
             down(st.act, fp.w(f"l{i}.wdown"), accd[i & 1], zero0=st.acc_qkv, zero1=accd[(i + 1) & 1], ss_zero=st.ss_attn)
         return bufs[n & 1], accd[(n - 1) & 1]
 
-    def _decode_layers_splitk(self, st, x):
+    def _decode_layers_splitk(self, st, x, attn=ops.attn_decode_fused):
         """The decoder stack of one decode step as five split-K launches per layer (see include/unigen_hip.h): a split-K projection leaves
         its raw fp32 accumulator behind and the NEXT kernel applies bias / RoPE / residual add / RMSNorm / SiLU-mul while it builds its
         own operand, so kernel boundaries are the only synchronisation.
-        -> (stream, pending): the residual stream after the last layer is stream + bf16round(pending = st.acc_down)."""
+        -> (stream, pending): the residual stream after the last layer is stream + bf16round(pending = st.acc_down).  attn: as in _decode_layers_sw."""
         d, fp = self.dims, self.fp
         Hq, Hk, hd = d.num_attention_heads, d.num_key_value_heads, d.head_dim
-        R, H, eps = st.rows, d.hidden_size, d.rms_norm_eps
+        R, H, eps = st.step_rows, d.hidden_size, d.rms_norm_eps
         cos, sin = self.rope(st.Tmax)
         st.ensure_scratch(d, "splitk")
         o = torch.empty((R, Hq * hd), dtype=torch.bfloat16, device=x.device)
@@ -824,17 +873,16 @@ class Qwen2Engine:
             # x (+ pending down_proj of the previous layer) -> x_mid ; q/k/v accumulator ; clears gate_up acc
             ops.decode_gemv_resid_norm_(x, st.acc_down, fp.p(f"l{i}.ln1"), st.x_mid, st.ss_attn, fp.w(f"l{i}.wqkv"), st.acc_qkv,
                                         zero0=st.acc_gu, ss_zero=st.ss_mlp)
-            ops.attn_decode_fused(st.acc_qkv, st.ss_attn, eps, H, fp.w(f"l{i}.bqkv"), cos, sin, st.pos, st.k[i], st.v[i],
-                                  st.key_valid, o, Hq, Hk, hd, st.Tmax)
+            attn(st.acc_qkv, st.ss_attn, eps, H, fp.w(f"l{i}.bqkv"), cos, sin, st.pos, st.k[i], st.v[i], st.key_valid, o, Hq, Hk, hd, st.Tmax)
             ops.decode_gemv_(o, fp.w(f"l{i}.wo"), st.acc_o, zero0=st.acc_qkv, zero1=st.acc_down, ss_zero=st.ss_attn)
             # x_mid + pending o_proj -> x ; gate/up accumulator
             ops.decode_gemv_resid_norm_(st.x_mid, st.acc_o, fp.p(f"l{i}.ln2"), x, st.ss_mlp, fp.w(f"l{i}.wgu"), st.acc_gu)
             ops.decode_gemv_swiglu_(st.acc_gu, st.ss_mlp, eps, H, fp.w(f"l{i}.wdown"), st.acc_down, zero0=st.acc_o)
         return x, st.acc_down
 
-    def _decode_layers(self, form, st, x):
+    def _decode_layers(self, form, st, x, **how):
         layers = {"sw": self._decode_layers_sw, "splitk": self._decode_layers_splitk, "ord_sw": self._decode_layers_ord}
-        return layers[form](st, x)
+        return layers[form](st, x, **how)
 
     def decode_step_logits(self, st, x, w_head, logits):
         """decode_step + the head slice in one go: logits fp32 [rows, N] = rows `w_head` of the tied embedding applied to the final-norm
@@ -971,6 +1019,46 @@ class Qwen2Engine:
         self.text_penalize(sess)
         self.text_pick(sess)
         self.text_stop_seq(sess)
+
+    # ---- prompt-lookup speculative decoding of one greedy row: a verify step runs the decoder stack on S consecutive positions
+    def spec_form(self, S):
+        """The layer form of a verify step on S rows: sw or splitk.  The other forms are refused by name before any launch (wide has
+        no fused attention launch to stand ug_attn_decode_seq in for; there is no ordered ug_attn_decode_seq)."""
+        form = self.decode_form(S, False)
+        if form not in ("sw", "splitk"):
+            raise UniGenHipError(f"prompt_lookup_num_tokens: this engine's decode steps take the {form} form; speculative decoding "
+                                 f"serves the sw and splitk forms only")
+        return form
+
+    def _spec_verify(self, sess, rows, advance):
+        ops.spec_verify_(sess.logits, rows, sess.V, sess.state, sess.n, self.fp.p("embed"), sess.tok, sess.out_tokens, sess.x, sess.hist,
+                         sess.G, sess.K, clear=sess.form == "splitk", stop_ids=sess.stop_ids, lengths=sess.lengths, advance=advance)
+
+    def spec_first_token(self, sess, hn):
+        """token 0 from the prefill's final-norm hidden state, as text_first_token picks it (the GEMV head into the zeroed row 0), pushed
+        through the verify entry with no draft and no advance: it lands in the history, so the first draft exists before step 1."""
+        self.first_head(sess.st, hn, self.fp.w("embed")[:sess.V], sess.logits[:1])
+        self._spec_verify(sess, 1, None)
+
+    def spec_step(self, sess):
+        """One verify step into the session's static buffers: the decoder stack on the S rows of sess.x in the session's form with
+        ug_attn_decode_seq where the form has ug_attn_decode_fused, the head with NO position advance, then ug_spec_verify, which owns
+        the advance (by the number of tokens emitted).  Always all S rows -- the weight stream dominates, and a fixed shape gives one
+        captured graph.  No host sync, no shape depends on the step: capturable.
+        Stale keys: a rejected row's k / v stay in the cache at positions >= the new position p'.  Nothing reads at or past p' (a step
+        attends to the cache keys below its position and to its own rows from the accumulator), and the next step overwrites
+        [p', p' + S), which covers every row this step wrote: a stale key is never visible."""
+        d, fp, st = self.dims, self.fp, sess.st
+        self.last_decode_deterministic = False
+        stream, pending = self._decode_layers(sess.form, st, sess.x, attn=ops.attn_decode_seq)
+        w_head = fp.w("embed")[:sess.V]
+        if sess.form == "sw":
+            ops.decode_sw_head_(stream, fp.p("norm"), d.rms_norm_eps, w_head, sess.logits, pend=pending, advance=None)
+        else:
+            hn = torch.empty((sess.S, d.hidden_size), dtype=torch.bfloat16, device=stream.device)
+            ops.decode_finish_resid_norm_(pending, stream, fp.p("norm"), hn, d.rms_norm_eps, advance=None)
+            ops.decode_gemv_(hn, w_head, sess.logits)
+        self._spec_verify(sess, sess.S, (st.pos, st.len))
 
     def decode_step(self, st, x):
         """x fp32 [rows, H] = embedding of the newest token (updated in place as the residual stream);
