@@ -240,15 +240,6 @@ struct AttnArgs {
   int ablate;               // probe builds of the timing tools only (UNIGEN_ATTN_ABLATE): 1 = no K / V staging after the first tile
 };
 
-// RoPE backward of one rotary pair, the arithmetic of rope_kernel<true> (elementwise.hip): the gradient is rounded to bf16
-// first (it arrives as a bf16 tensor in the reference), products and sums round separately
-__device__ __forceinline__ void rope_bwd_pair(float& g1, float& g2, float c, float s) {
-#pragma clang fp contract(off)
-  const float x1 = bf2f(f2bf(g1)), x2 = bf2f(f2bf(g2));
-  const float a1 = x1 * c, a2 = x2 * c;
-  const float b1 = x2 * s, b2 = x1 * s;
-  g1 = a1 + b1; g2 = a2 - b2;
-}
 // sum of x[v] over the 32 lanes n = lane & 31 (same lane half) by recursive halving: 62 exchanges instead of 320; lane n ends up
 // with the sums of v = 2 n and 2 n + 1 in x[0], x[1]
 template <int N>

@@ -122,6 +122,26 @@ __device__ __forceinline__ void swiglu_bwd_elem(float gf, float uf, float df, fl
   dgate = dsilu * (sg * (1.f + gf * (1.f - sg)));
 }
 
+// ---------------------------------------------------------------- RoPE pair (one definition for every kernel)
+// One rotate-half pair as apply_rotary_pos_emb computes it (modeling_qwen2.py:131-135): products and sums round separately, contraction
+// off.  rope_kernel<false>, rope_at_kernel, the GEMM's EPI_ROPE epilogue and the decode attention kernels' qkv_finish_pair share it, so
+// the fused and the separate forms stay bit-identical to each other.
+__device__ __forceinline__ void rope_pair(float x1, float x2, float c, float s, float& o1, float& o2) {
+#pragma clang fp contract(off)
+  const float a1 = x1 * c, a2 = x2 * c;
+  const float b1 = x2 * s, b2 = x1 * s;
+  o1 = a1 - b1; o2 = a2 + b2;
+}
+// Its backward (the transposed rotation), the arithmetic of rope_kernel<true>: the gradient is rounded to bf16 first (it arrives as a
+// bf16 tensor in the reference), products and sums round separately.  Shared by the attention backward kernels.
+__device__ __forceinline__ void rope_bwd_pair(float& g1, float& g2, float c, float s) {
+#pragma clang fp contract(off)
+  const float x1 = bf2f(f2bf(g1)), x2 = bf2f(f2bf(g2));
+  const float a1 = x1 * c, a2 = x2 * c;
+  const float b1 = x2 * s, b2 = x1 * s;
+  g1 = a1 + b1; g2 = a2 - b2;
+}
+
 // ---------------------------------------------------------------- wave reductions (64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

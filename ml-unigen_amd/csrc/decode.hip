@@ -3,6 +3,7 @@
 // generation, position / length read from DEVICE memory so one captured hipGraph replays all 256 steps.
 //   cache layout: K,V [rows][HKV][Tmax][128] bf16 (keys of one (row, kv-head) contiguous)
 #include "common.h"
+#include "decode_common.h"
 #include "decode_plan.h"
 #include "unigen_hip.h"
 #include "vmem_asm.h"
@@ -11,9 +12,6 @@
 namespace {
 
 constexpr int DHD = 128;
-// workgroup barrier for an LDS hand-off: __syncthreads() also drains vmcnt (its fence covers global memory), i.e. waits for the
-// weight tiles in flight and the clears' write acknowledgements, which no wave needs at this point
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 typedef const __attribute__((address_space(1))) void* gptr_t;      // LDS-DMA operands (global_load_lds)
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -36,11 +34,10 @@ __global__ __launch_bounds__(256) void kv_store_kernel(const bf16_t* __restrict_
   }
 }
 
-// RoPE for single-token rows at position *pos_dev (same arithmetic as rope_kernel in elementwise.hip)
+// RoPE for single-token rows at position *pos_dev (rope_pair, common.h: the arithmetic of rope_kernel in elementwise.hip)
 __global__ __launch_bounds__(256) void rope_at_kernel(bf16_t* __restrict__ qkv, const float* __restrict__ cs,
                                                       const float* __restrict__ sn, int rows, int ldq, int nheads, int hd,
                                                       const int* __restrict__ pos_dev, int max_pos) {
-#pragma clang fp contract(off)
   const int half = hd >> 1, per_head = half >> 2;
   const int pos = min(*pos_dev, max_pos - 1);
   const int total = rows * nheads * per_head;
@@ -58,16 +55,72 @@ __global__ __launch_bounds__(256) void rope_at_kernel(bf16_t* __restrict__ qkv, 
     const float cc[4] = {c.x, c.y, c.z, c.w}, ss[4] = {s.x, s.y, s.z, s.w};
     float o1[4], o2[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float a1 = x1[k] * cc[k], a2 = x2[k] * cc[k];
-      const float b1 = x2[k] * ss[k], b2 = x1[k] * ss[k];
-      o1[k] = a1 - b1; o2[k] = a2 + b2;
-    }
+    for (int k = 0; k < 4; ++k) rope_pair(x1[k], x2[k], cc[k], ss[k], o1[k], o2[k]);
     uint2 olo, ohi;
     olo.x = pack_bf2(o1[0], o1[1]); olo.y = pack_bf2(o1[2], o1[3]);
     ohi.x = pack_bf2(o2[0], o2[1]); ohi.y = pack_bf2(o2[2], o2[3]);
     *reinterpret_cast<uint2*>(base) = olo;
     *reinterpret_cast<uint2*>(base + half) = ohi;
+  }
+}
+
+// ---- steps the three cache-attention kernels share (attn_decode_kernel, attn_decode_fused_kernel, attn_decode_seq_kernel): one
+// definition each, so the kernels cannot drift apart (tests/test_attn_decode_seq_gpu.py, tests/test_decode_parity_gpu.py)
+// A pass's score maximum mc joins the wave's running maximum m: returns the exponent offset mu of the pass (p = exp(s - mu); 0 while
+// every key so far is masked) and sets alpha, the rescale of what l and O hold from earlier passes.
+__device__ __forceinline__ float softmax_offset(float& m, float mc, float& alpha) {
+  const float mn = fmaxf(m, mc);
+  const float mu = (mn == -INFINITY) ? 0.f : mn;
+  alpha = __expf(m - mu);
+  m = mn;
+  return mu;
+}
+// Online-softmax step with one key per lane: score s (-inf: no key) joins (m, l); returns this lane's p.
+__device__ __forceinline__ float online_softmax_step(float s, float& m, float& l, float& alpha) {
+  const float mu = softmax_offset(m, wave_max(s), alpha);
+  const float p = __expf(s - mu);
+  l = l * alpha + wave_sum(p);
+  return p;
+}
+// Fold the four key phases (lane >> 4) of a wave's O and park its (m, l, O) partial in LDS (dc = lane & 15, the lane's 8-dim chunk).
+template <int NW>
+__device__ __forceinline__ void park_partial(float (&acc)[8], float m, float l, float (&om)[NW][DHD], float (&ml)[NW][2], int lane, int wave, int dc) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    acc[e] += __shfl_xor(acc[e], 16, 64);
+    acc[e] += __shfl_xor(acc[e], 32, 64);
+  }
+  if (lane < 16) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) om[wave][dc * 8 + e] = acc[e];
+  }
+  if (lane == 0) { ml[wave][0] = m; ml[wave][1] = l; }
+}
+// Merge the NW parked partials into (L, O) of output dim d, relative to the overall maximum M (flash-decoding style split over keys).
+template <int NW>
+__device__ __forceinline__ void merge_partials(const float (&om)[NW][DHD], const float (&ml)[NW][2], float M, int d, float& L, float& O) {
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    const float wgt = (ml[w][0] == -INFINITY) ? 0.f : __expf(ml[w][0] - M);
+    L += wgt * ml[w][1];
+    O += wgt * om[w][d];
+  }
+}
+
+// Consumer-side finishing of one rotate-half pair (a1, a2) of the raw q/k/v accumulator: x = bf16(rstd * acc + bias) with rstd from the
+// row's sum of squares ssr over norm_cols columns, then (q and k heads: rope) rope_pair on the rounded values and one more bf16 rounding.
+// attn_decode_fused_kernel and attn_decode_seq_kernel both call it: the cache rows they append must be the same bits.
+__device__ __forceinline__ void qkv_finish_pair(float a1, float a2, float ssr, int norm_cols, float eps, bool has_bias, float b1, float b2,
+                                                bool rope, float c, float s, float& x1, float& x2) {
+#pragma clang fp contract(off)
+  const float rs = rsqrtf(ssr / (float)norm_cols + eps);
+  float v1 = rs * a1, v2 = rs * a2;
+  if (has_bias) { v1 += b1; v2 += b2; }
+  x1 = bf2f(f2bf(v1)); x2 = bf2f(f2bf(v2));
+  if (rope) {
+    float r1, r2;
+    rope_pair(x1, x2, c, s, r1, r2);
+    x1 = bf2f(f2bf(r1)); x2 = bf2f(f2bf(r2));
   }
 }
 
@@ -120,13 +173,8 @@ __global__ __launch_bounds__(64 * AD_WAVES) void attn_decode_kernel(const bf16_t
         for (int e = 0; e < 8; ++e) d += bf2f((bf16_t)kf[c][e]) * qs[c * 8 + e];
       s = d * scale;
     }
-    const float mc = wave_max(s);
-    const float mn = fmaxf(m, mc);
-    const float mu = (mn == -INFINITY) ? 0.f : mn;
-    const float alpha = __expf(m - mu);
-    const float p = __expf(s - mu);
-    l = l * alpha + wave_sum(p);
-    m = mn;
+    float alpha;
+    const float p = online_softmax_step(s, m, l, alpha);
     const float pb = bf2f(f2bf(p));          // P is rounded to bf16 before P.V like the bf16 SDPA paths
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] *= alpha;
@@ -137,28 +185,14 @@ __global__ __launch_bounds__(64 * AD_WAVES) void attn_decode_kernel(const bf16_t
       for (int e = 0; e < 8; ++e) acc[e] += pj * bf2f((bf16_t)vf[jj][e]);
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    acc[e] += __shfl_xor(acc[e], 16, 64);
-    acc[e] += __shfl_xor(acc[e], 32, 64);
-  }
-  if (lane < 16) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) om[wave][dc * 8 + e] = acc[e];
-  }
-  if (lane == 0) { ml[wave][0] = m; ml[wave][1] = l; }
+  park_partial(acc, m, l, om, ml, lane, wave, dc);
   __syncthreads();
   if (threadIdx.x < DHD) {
     float M = ml[0][0];
 #pragma unroll
     for (int w = 1; w < AD_WAVES; ++w) M = fmaxf(M, ml[w][0]);
     float L = 0.f, O = 0.f;
-#pragma unroll
-    for (int w = 0; w < AD_WAVES; ++w) {
-      const float wgt = (ml[w][0] == -INFINITY) ? 0.f : __expf(ml[w][0] - M);
-      L += wgt * ml[w][1];
-      O += wgt * om[w][threadIdx.x];
-    }
+    merge_partials(om, ml, M, threadIdx.x, L, O);
     const float inv = L > 0.f ? 1.f / L : 0.f;
     o[(int64_t)r * ldo + h * DHD + threadIdx.x] = f2bf(O * inv);
   }
@@ -283,20 +317,7 @@ __global__ __launch_bounds__(64 * ADF_WAVES) void attn_decode_fused_kernel(
     }
     const float b1 = bf2f((bf16_t)bb1), b2 = bf2f((bf16_t)bb2);
     float x1, x2;
-    {
-#pragma clang fp contract(off)
-      // consumer-side finishing of the qkv projection, same arithmetic as finish_qkv_tile / rope_at_kernel: bf16(rstd * acc + bias), rotate-half with
-      // separately rounded products
-      const float rs = rsqrtf(ssr / (float)norm_cols + eps);
-      float v1 = rs * a1, v2 = rs * a2;
-      if (bias) { v1 += b1; v2 += b2; }
-      x1 = bf2f(f2bf(v1)); x2 = bf2f(f2bf(v2));
-      if (wave < 2) {
-        const float p1 = x1 * rc, p2 = x2 * rc;
-        const float q1 = x2 * rsn, q2 = x1 * rsn;
-        x1 = bf2f(f2bf(p1 - q1)); x2 = bf2f(f2bf(p2 + q2));
-      }
-    }
+    qkv_finish_pair(a1, a2, ssr, norm_cols, eps, bias != nullptr, b1, b2, wave < 2, rc, rsn, x1, x2);
     float* dst = wave == 0 ? qs : wave == 1 ? kn : vn;
     dst[lane] = x1; dst[lane + DHD / 2] = x2;
     if (wave == 0) { qb[lane] = f2bf(x1); qb[lane + DHD / 2] = f2bf(x2); }
@@ -337,13 +358,8 @@ __global__ __launch_bounds__(64 * ADF_WAVES) void attn_decode_fused_kernel(
       }
       s = d * scale;
     }
-    const float mc = wave_max(s);
-    const float mn = fmaxf(m, mc);
-    const float mu = (mn == -INFINITY) ? 0.f : mn;
-    const float alpha = __expf(m - mu);
-    const float p = __expf(s - mu);
-    l = l * alpha + wave_sum(p);
-    m = mn;
+    float alpha;
+    const float p = online_softmax_step(s, m, l, alpha);
     const float pb = bf2f(f2bf(p));
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] *= alpha;
@@ -364,16 +380,7 @@ __global__ __launch_bounds__(64 * ADF_WAVES) void attn_decode_fused_kernel(
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    acc[e] += __shfl_xor(acc[e], 16, 64);
-    acc[e] += __shfl_xor(acc[e], 32, 64);
-  }
-  if (lane < 16) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) om[wave][dc * 8 + e] = acc[e];
-  }
-  if (lane == 0) { ml[wave][0] = m; ml[wave][1] = l; }
+  park_partial(acc, m, l, om, ml, lane, wave, dc);
   // the new token's own score (every wave computes it; no extra barrier)
   const float s_new = wave_sum(qs[lane] * kn[lane] + qs[lane + DHD / 2] * kn[lane + DHD / 2]) * scale;
   __syncthreads();
@@ -383,12 +390,7 @@ __global__ __launch_bounds__(64 * ADF_WAVES) void attn_decode_fused_kernel(
     for (int w = 0; w < ADF_WAVES; ++w) M = fmaxf(M, ml[w][0]);
     const float wn = __expf(s_new - M);
     float L = wn, O = wn * vn[threadIdx.x];
-#pragma unroll
-    for (int w = 0; w < ADF_WAVES; ++w) {
-      const float wgt = (ml[w][0] == -INFINITY) ? 0.f : __expf(ml[w][0] - M);
-      L += wgt * ml[w][1];
-      O += wgt * om[w][threadIdx.x];
-    }
+    merge_partials(om, ml, M, threadIdx.x, L, O);
     o[(int64_t)r * ldo + h * DHD + threadIdx.x] = f2bf(O / L);
   }
 }
@@ -396,7 +398,7 @@ __global__ __launch_bounds__(64 * ADF_WAVES) void attn_decode_fused_kernel(
 // Cache attention of one VERIFY step of speculative decoding (ug_attn_decode_seq): the S rows of the raw qkv accumulator are S
 // CONSECUTIVE positions p, p + 1, ... of ONE sequence (one cache row), where attn_decode_fused_kernel's rows are independent sequences at
 // one position.  One workgroup per (row s, query head): it finishes q of row s and k / v of rows 0 .. s of its kv head from the
-// accumulator itself, with attn_decode_fused_kernel's arithmetic (the appended rows are the bits S one-row launches of that kernel
+// accumulator itself, by qkv_finish_pair like attn_decode_fused_kernel (the appended rows are the bits S one-row launches of that kernel
 // append), so no new key or value is ever read back from the cache -- another workgroup writes it and nothing orders the two.  The first
 // query head of a kv head appends ITS row's k / v at p + s.  Row s attends to the cache keys [0, min(p, Tmax)) that key_valid allows and
 // to the new keys 0 .. s; what the workgroup of row s computes does not depend on S or on rows > s.
@@ -434,19 +436,7 @@ __global__ __launch_bounds__(64 * ADS_WAVES) void attn_decode_seq_kernel(
     if (bias) { b1 = bf2f(bias[col0 + lane]); b2 = bf2f(bias[col0 + lane + DHD / 2]); }
     if (kind < 2) { rc = cs[(int64_t)rpos * (DHD / 2) + lane]; rsn = sn[(int64_t)rpos * (DHD / 2) + lane]; }
     float x1, x2;
-    {
-#pragma clang fp contract(off)
-      // attn_decode_fused_kernel's finishing, operation for operation: bf16(rstd * acc + bias), rotate-half with separately rounded products
-      const float rs = rsqrtf(ssr / (float)norm_cols + eps);
-      float v1 = rs * a1, v2 = rs * a2;
-      if (bias) { v1 += b1; v2 += b2; }
-      x1 = bf2f(f2bf(v1)); x2 = bf2f(f2bf(v2));
-      if (kind < 2) {
-        const float p1 = x1 * rc, p2 = x2 * rc;
-        const float q1 = x2 * rsn, q2 = x1 * rsn;
-        x1 = bf2f(f2bf(p1 - q1)); x2 = bf2f(f2bf(p2 + q2));
-      }
-    }
+    qkv_finish_pair(a1, a2, ssr, norm_cols, eps, bias != nullptr, b1, b2, kind < 2, rc, rsn, x1, x2);
     float* dst = kind == 0 ? qs : kind == 1 ? kn[j] : vn[j];
     dst[lane] = x1; dst[lane + DHD / 2] = x2;
     if (kind > 0 && j == s && hq == 0 && pos0 + s < Tmax) {
@@ -488,10 +478,8 @@ __global__ __launch_bounds__(64 * ADS_WAVES) void attn_decode_seq_kernel(
     }
     mc = fmaxf(mc, __shfl_xor(mc, 16, 64));
     mc = fmaxf(mc, __shfl_xor(mc, 32, 64));
-    const float mn = fmaxf(m, mc);
-    const float mu = (mn == -INFINITY) ? 0.f : mn;
-    const float alpha = __expf(m - mu);
-    m = mn;
+    float alpha;
+    const float mu = softmax_offset(m, mc, alpha);
     float ps = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] *= alpha;
@@ -507,16 +495,7 @@ __global__ __launch_bounds__(64 * ADS_WAVES) void attn_decode_seq_kernel(
     ps += __shfl_xor(ps, 32, 64);
     l = l * alpha + ps;
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    acc[e] += __shfl_xor(acc[e], 16, 64);
-    acc[e] += __shfl_xor(acc[e], 32, 64);
-  }
-  if (lane < 16) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) om[wave][dc * 8 + e] = acc[e];
-  }
-  if (lane == 0) { ml[wave][0] = m; ml[wave][1] = l; }
+  park_partial(acc, m, l, om, ml, lane, wave, dc);
   // the scores of the step's own keys 0 .. s (a wave each)
   for (int j = wave; j <= s; j += ADS_WAVES) {
     const float d = wave_sum(qs[lane] * kn[j][lane] + qs[lane + DHD / 2] * kn[j][lane + DHD / 2]) * scale;
@@ -534,28 +513,27 @@ __global__ __launch_bounds__(64 * ADS_WAVES) void attn_decode_seq_kernel(
       L += wn;
       O += wn * vn[j][threadIdx.x];
     }
-#pragma unroll
-    for (int w = 0; w < ADS_WAVES; ++w) {
-      const float wgt = (ml[w][0] == -INFINITY) ? 0.f : __expf(ml[w][0] - M);
-      L += wgt * ml[w][1];
-      O += wgt * om[w][threadIdx.x];
-    }
+    merge_partials(om, ml, M, threadIdx.x, L, O);
     o[(int64_t)s * ldo + h * DHD + threadIdx.x] = f2bf(O / L);
   }
 }
 
-// Finish a split-K fp32 accumulation of a skinny GEMM:  mode 0: out_bf16 = bf16(acc + bias)
-//                                                      mode 1: resid_f32 += bf16round(acc)      (in place)
-__global__ __launch_bounds__(256) void skinny_finish_kernel(const float* __restrict__ acc, const bf16_t* __restrict__ bias,
-                                                            bf16_t* __restrict__ out_bf16, float* __restrict__ resid,
-                                                            int64_t total, int N, int mode) {
+// Finish a split-K fp32 accumulation of a skinny GEMM: np partial slots parts[p * slot + ...] summed in ascending slot order in fp32 (the
+// ordered forms of the deterministic decode; np == 1: the one accumulator of the default form, ug_skinny_finish), then
+//   out_bf16 = bf16(sum + bias) | resid += bf16round(sum) (in place) | out_f32 = sum      (whichever is given)
+__global__ __launch_bounds__(256) void skinny_finish_kernel(const float* __restrict__ parts, int np, int64_t slot,
+                                                            const bf16_t* __restrict__ bias, bf16_t* __restrict__ out_bf16,
+                                                            float* __restrict__ out_f32, float* __restrict__ resid, int64_t total, int N) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = acc[i];
-    if (mode == 0) {
+    float v = parts[i];
+    for (int p = 1; p < np; ++p) v += parts[p * slot + i];
+    if (out_bf16) {
       if (bias) v += bf2f(bias[i % N]);
       out_bf16[i] = f2bf(v);
-    } else {
+    } else if (resid) {
       resid[i] += bf2f(f2bf(v));
+    } else {
+      out_f32[i] = v;
     }
   }
 }
@@ -631,107 +609,91 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 // Every finisher consumes a row-major fp32 accumulator filled by the GEMV (acc[r*lda + n]) and leaves it ZEROED
 // for the next step, so the captured graph carries no memset nodes.
 
-// q/k/v projection: + bias -> bf16, RoPE at *pos_dev on the q and k heads, q -> q_out, k/v -> cache[pos].
-// One wave per (head, row); lane i owns dims i and i+64 (the rotary pair).  Same arithmetic as rope_at_kernel.
-__device__ __forceinline__ void finish_qkv_tile(float* __restrict__ acc, int64_t lda, const bf16_t* __restrict__ bias,
-                                                const float* __restrict__ cs, const float* __restrict__ sn_tab, int pos0,
-                                                bf16_t* __restrict__ q_out, int64_t ldq, bf16_t* __restrict__ ck,
-                                                bf16_t* __restrict__ cv, int Hq, int Hk, int Tmax, int max_pos, int hh, int r,
-                                                int i) {
-#pragma clang fp contract(off)
-  const int c1 = hh * DHD + i, c2 = c1 + DHD / 2;
-  float* a = acc + (int64_t)r * lda;
-  float v1 = a[c1], v2 = a[c2];
-  a[c1] = 0.f; a[c2] = 0.f;
-  if (bias) { v1 += bf2f(bias[c1]); v2 += bf2f(bias[c2]); }
-  float x1 = bf2f(f2bf(v1)), x2 = bf2f(f2bf(v2));
-  if (hh < Hq + Hk) {
-    const int pos = min(pos0, max_pos - 1);
-    const float c = cs[(int64_t)pos * (DHD / 2) + i], s = sn_tab[(int64_t)pos * (DHD / 2) + i];
-    const float p1 = x1 * c, p2 = x2 * c;
-    const float q1 = x2 * s, q2 = x1 * s;
-    x1 = bf2f(f2bf(p1 - q1)); x2 = bf2f(f2bf(p2 + q2));
-  }
-  if (hh < Hq) {
-    bf16_t* qp = q_out + (int64_t)r * ldq + hh * DHD;
-    qp[i] = f2bf(x1); qp[i + DHD / 2] = f2bf(x2);
-  } else if (pos0 < Tmax) {
-    const bool is_k = hh < Hq + Hk;
-    const int hk = is_k ? hh - Hq : hh - Hq - Hk;
-    bf16_t* dst = (is_k ? ck : cv) + (((int64_t)r * Hk + hk) * Tmax + pos0) * DHD;
-    dst[i] = f2bf(x1); dst[i + DHD / 2] = f2bf(x2);
-  }
-}
-
-// o / down projection:  x[r] += bf16round(acc[r]);  xn[r] = bf16(rmsnorm(x[r]) * w)   (next sub-block's input).
-// One wave per row, the same per-lane accumulation order as rmsnorm_fwd_kernel so both paths agree bit for bit.
-template <int MAXV>
-__device__ __forceinline__ void finish_resid_norm_row(float* __restrict__ acc, int64_t lda, float* __restrict__ x,
-                                                      const float* __restrict__ w, bf16_t* __restrict__ xn, int cols, float eps,
-                                                      int row, int lane) {
-  float4* xr = reinterpret_cast<float4*>(x + (int64_t)row * cols);
-  float4* ar = reinterpret_cast<float4*>(acc + (int64_t)row * lda);
-  const float4* wr = reinterpret_cast<const float4*>(w);
+// o / down projection:  x[r] += bf16round(delta[r]);  xn[r] = bf16(rmsnorm(x[r]) * w)   (next sub-block's input).
+// One wave per row.  The tail of both finishers below, once the row's x (v), norm weight (gw) and delta (dl) are in registers: the
+// same per-lane accumulation order as rmsnorm_fwd_kernel so both paths agree bit for bit.
+// ACC (finish_resid_norm_kernel): the delta came from the accumulator row `ar`, which is cleared as it is consumed, and xn is always
+// written; !ACC (the ordered form): ar is not used and xn may be null.  (A compile-time distinction: a run-time one costs the
+// accumulator form 52 / 100 instructions.)
+template <int MAXV, bool ACC>
+__device__ __forceinline__ void resid_norm_tail(float4 (&v)[MAXV], const float4 (&gw)[MAXV], const float4 (&dl)[MAXV], float4* xr, float4* ar,
+                                                bf16_t* __restrict__ xn, int cols, float eps, int row, int lane) {
   const int nv = cols >> 2;
-  float4 v[MAXV], gw[MAXV], dl[MAXV];
-#pragma unroll
-  for (int c = 0; c < MAXV; ++c) {              // every load of the row in flight at once
-    const int i = lane + c * 64;
-    if (i < nv) { v[c] = xr[i]; gw[c] = wr[i]; dl[c] = ar[i]; }
-  }
   float ss = 0.f;
 #pragma unroll
   for (int c = 0; c < MAXV; ++c) {
     const int i = lane + c * 64;
     if (i < nv) {
-      ar[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (ACC) ar[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       v[c].x += bf2f(f2bf(dl[c].x)); v[c].y += bf2f(f2bf(dl[c].y));
       v[c].z += bf2f(f2bf(dl[c].z)); v[c].w += bf2f(f2bf(dl[c].w));
       xr[i] = v[c];
       ss += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
     }
   }
-  ss = wave_sum(ss);
-  const float rs = rsqrtf(ss / (float)cols + eps);
+  if (ACC || xn) {
+    ss = wave_sum(ss);
+    const float rs = rsqrtf(ss / (float)cols + eps);
 #pragma unroll
-  for (int c = 0; c < MAXV; ++c) {
-    const int i = lane + c * 64;
-    if (i < nv) {
-      uint2 o;
-      o.x = pack_bf2(gw[c].x * (v[c].x * rs), gw[c].y * (v[c].y * rs));
-      o.y = pack_bf2(gw[c].z * (v[c].z * rs), gw[c].w * (v[c].w * rs));
-      reinterpret_cast<uint2*>(xn + (int64_t)row * cols)[i] = o;
+    for (int c = 0; c < MAXV; ++c) {
+      const int i = lane + c * 64;
+      if (i < nv) {
+        uint2 o;
+        o.x = pack_bf2(gw[c].x * (v[c].x * rs), gw[c].y * (v[c].y * rs));
+        o.y = pack_bf2(gw[c].z * (v[c].z * rs), gw[c].w * (v[c].w * rs));
+        reinterpret_cast<uint2*>(xn + (int64_t)row * cols)[i] = o;
+      }
     }
   }
 }
 
+// delta = the projection's accumulator acc[r * lda + n], left ZEROED
 template <int MAXV>
 __global__ __launch_bounds__(64) void finish_resid_norm_kernel(float* __restrict__ acc, int64_t lda, float* __restrict__ x,
                                                                const float* __restrict__ w, bf16_t* __restrict__ xn, int cols,
                                                                float eps, int* __restrict__ pos_inc, int* __restrict__ len_inc) {
-  finish_resid_norm_row<MAXV>(acc, lda, x, w, xn, cols, eps, blockIdx.x, threadIdx.x);
+  const int row = blockIdx.x, lane = threadIdx.x, nv = cols >> 2;
+  float4* xr = reinterpret_cast<float4*>(x + (int64_t)row * cols);
+  float4* ar = reinterpret_cast<float4*>(acc + (int64_t)row * lda);
+  const float4* wr = reinterpret_cast<const float4*>(w);
+  float4 v[MAXV], gw[MAXV], dl[MAXV];
+#pragma unroll
+  for (int c = 0; c < MAXV; ++c) {              // every load of the row in flight at once
+    const int i = lane + c * 64;
+    if (i < nv) { v[c] = xr[i]; gw[c] = wr[i]; dl[c] = ar[i]; }
+  }
+  resid_norm_tail<MAXV, true>(v, gw, dl, xr, ar, xn, cols, eps, row, lane);
   // the step's last launch that comes after every reader of the write position: advance it here (was two one-element torch
   // kernels per decode step)
   if (pos_inc && blockIdx.x == 0 && threadIdx.x == 0) { ++*pos_inc; ++*len_inc; }
 }
 
-// gate/up projection:  act = bf16( bf16(silu(bf16 gate)) * bf16 up )  (swiglu_fwd_kernel's arithmetic).
-__device__ __forceinline__ void finish_swiglu_quad(float* __restrict__ acc, int64_t lda, bf16_t* __restrict__ act, int I, int r,
-                                                   int c) {
-  float4* ag = reinterpret_cast<float4*>(acc + (int64_t)r * lda + c);
-  float4* au = reinterpret_cast<float4*>(acc + (int64_t)r * lda + I + c);
-  const float4 gv = *ag, uv = *au;
-  *ag = make_float4(0.f, 0.f, 0.f, 0.f);
-  *au = make_float4(0.f, 0.f, 0.f, 0.f);
-  const float gs[4] = {gv.x, gv.y, gv.z, gv.w}, us[4] = {uv.x, uv.y, uv.z, uv.w};
-  float o[4];
+// Ordered form (deterministic decode): delta = np partial slots parts[p][rows][ldp] (the last layer's down k-blocks) summed in ascending
+// slot order in fp32; xn is written when given.
+template <int MAXV>
+__global__ __launch_bounds__(64) void finish_resid_norm_ord_kernel(const float* __restrict__ parts, int ldp, int np, float* __restrict__ x,
+                                                                   const float* __restrict__ w, bf16_t* __restrict__ xn, int cols, float eps,
+                                                                   int* __restrict__ pos_inc, int* __restrict__ len_inc) {
+  const int row = blockIdx.x, lane = threadIdx.x, nv = cols >> 2;
+  const int64_t slot = (int64_t)gridDim.x * ldp;
+  float4* xr = reinterpret_cast<float4*>(x + (int64_t)row * cols);
+  const float4* wr = reinterpret_cast<const float4*>(w);
+  float4 v[MAXV], gw[MAXV], dl[MAXV];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float g = bf2f(f2bf(gs[e])), u = bf2f(f2bf(us[e]));
-    o[e] = bf2f(f2bf(g / (1.f + __expf(-g)))) * u;
+  for (int c = 0; c < MAXV; ++c) {
+    const int i = lane + c * 64;
+    if (i < nv) { v[c] = xr[i]; gw[c] = wr[i]; dl[c] = reinterpret_cast<const float4*>(parts + (int64_t)row * ldp)[i]; }
   }
-  uint2 ov; ov.x = pack_bf2(o[0], o[1]); ov.y = pack_bf2(o[2], o[3]);
-  *reinterpret_cast<uint2*>(act + (int64_t)r * I + c) = ov;
+  for (int p = 1; p < np; ++p) {
+    const float4* pr = reinterpret_cast<const float4*>(parts + p * slot + (int64_t)row * ldp);
+#pragma unroll
+    for (int c = 0; c < MAXV; ++c) {
+      const int i = lane + c * 64;
+      if (i < nv) { const float4 t = pr[i]; dl[c].x += t.x; dl[c].y += t.y; dl[c].z += t.z; dl[c].w += t.w; }
+    }
+  }
+  resid_norm_tail<MAXV, false>(v, gw, dl, xr, nullptr, xn, cols, eps, row, lane);
+  if (pos_inc && blockIdx.x == 0 && threadIdx.x == 0) { ++*pos_inc; ++*len_inc; }
 }
 
 // One wave per workgroup owns ONE 256-wide k-slab and KW consecutive 16-row weight groups.  The
@@ -759,32 +721,12 @@ struct DecodeIn {
   const float* x_in; const float* pend; int64_t ld_pend; const float* norm_w; float* x_out; float* ss_out;   // RESID_NORM
   const float* gu; int64_t ld_gu; const float* ss_in; float eps; int norm_cols;                              // SWIGLU
   float* zero0; float* zero1; float* ss_zero;                                                               // clears
-  int n0_4, per0, n1_4, per1;           // float4 counts and every workgroup's share of them (set_clear_shares, on the host)
+  int n0_4, per0, n1_4, per1;           // float4 counts and every workgroup's share of them (decode_clear, decode_common.h)
   int part_slot;                        // ordered forms: floats between two k-slabs' partial tiles (gemv_ring_kernel)
 };
 
-// Round 5: everything uniform is 32-bit and comes from the host.  The round-4 form divided int64 counts by the grid size in every
-// workgroup -- ~150 dependent scalar instructions per division, twice, AHEAD of the kernel's first load (the compiler hoists them
-// over the early-exit of surplus workgroups): 540-600 instructions and 1.5-2 us between a wave's first instruction and its first
-// load (profiles/r05_ar_prefetch.md, section 3).
-__device__ __forceinline__ void decode_clear(const DecodeIn& f, int tid, int bid) {
-  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int nt = blockDim.x;
-  if (f.zero0) {
-    const int lo = bid * f.per0, hi = min(f.n0_4, lo + f.per0);
-    for (int i = lo + tid; i < hi; i += nt) reinterpret_cast<float4*>(f.zero0)[i] = z;
-  }
-  if (f.zero1) {
-    const int lo = bid * f.per1, hi = min(f.n1_4, lo + f.per1);
-    for (int i = lo + tid; i < hi; i += nt) reinterpret_cast<float4*>(f.zero1)[i] = z;
-  }
-  if (f.ss_zero && bid == 0 && tid < 32) f.ss_zero[tid] = 0.f;
-}
-
 // linear workgroup id (x fastest: the order the dispatcher deals workgroups out to the XCDs in)
 __device__ __forceinline__ int linear_block() { return (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x; }
-
-__device__ __forceinline__ float silu_bf(float g) { return bf2f(f2bf(g / (1.f + __expf(-g)))); }
 
 // Request this lane's operand pieces (row `ar`, 8 k-values at k0) for the fp32-operand modes -- hand-issued loads (vmem_asm.h): the
 // values may be used only behind the caller's wait + tie.
@@ -861,7 +803,7 @@ __global__ __launch_bounds__(64) void gemv_ring_kernel(const bf16_t* __restrict_
   const int kbase = blockIdx.x * 256;
   const bool whole = (N & 15) == 0;                                 // every 16-row group is complete: no per-row clamp
   // the clears this launch carries go out first: stores behind the loads would sit between them in the memory queue
-  if constexpr (!ORD) decode_clear(f, lane, linear_block());
+  if constexpr (!ORD) decode_clear(f, lane, linear_block(), blockDim.x);
   TileAddr ta;
   ta.init(lane, kbase, K, ldw);
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(tile[0]));
@@ -971,7 +913,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_ring4_kernel(const float* __rest
   };
   if constexpr (CLR) {
     rest_of_args();
-    decode_clear(f, threadIdx.x, linear_block());  // the clears this launch carries go out first (see gemv_ring_kernel)
+    decode_clear(f, threadIdx.x, linear_block(), blockDim.x);  // the clears this launch carries go out first (see gemv_ring_kernel)
   }
   if (slab >= nslabs) return;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -1137,77 +1079,6 @@ __global__ __launch_bounds__(64 * NW) void gemv_ring4_kernel(const float* __rest
       }
     }
   }
-}
-
-// ---- ordered finishers (deterministic decode): partial slots summed in ascending slot order in fp32, then the default form's rounding
-// parts[p * slot + ...], p < np.  out_bf16 = bf16(sum + bias) | resid += bf16round(sum) | out_f32 = sum  (whichever is given)
-__global__ __launch_bounds__(256) void skinny_finish_ord_kernel(const float* __restrict__ parts, int np, int64_t slot,
-                                                                const bf16_t* __restrict__ bias, bf16_t* __restrict__ out_bf16,
-                                                                float* __restrict__ out_f32, float* __restrict__ resid, int64_t total, int N) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = parts[i];
-    for (int p = 1; p < np; ++p) v += parts[p * slot + i];
-    if (out_bf16) {
-      if (bias) v += bf2f(bias[i % N]);
-      out_bf16[i] = f2bf(v);
-    } else if (resid) {
-      resid[i] += bf2f(f2bf(v));
-    } else {
-      out_f32[i] = v;
-    }
-  }
-}
-
-// finish_resid_norm_kernel fed by np partial slots parts[p][rows][ldp] (the last layer's down k-blocks): x[r] += bf16round(sum_p parts[p][r])
-// in place; xn[r] = bf16(rmsnorm(x[r]) * w) when xn is given.  Same per-lane statistics order as rmsnorm_fwd_kernel.
-template <int MAXV>
-__global__ __launch_bounds__(64) void finish_resid_norm_ord_kernel(const float* __restrict__ parts, int ldp, int np, float* __restrict__ x,
-                                                                   const float* __restrict__ w, bf16_t* __restrict__ xn, int cols, float eps,
-                                                                   int* __restrict__ pos_inc, int* __restrict__ len_inc) {
-  const int row = blockIdx.x, lane = threadIdx.x, nv = cols >> 2;
-  const int64_t slot = (int64_t)gridDim.x * ldp;
-  float4* xr = reinterpret_cast<float4*>(x + (int64_t)row * cols);
-  const float4* wr = reinterpret_cast<const float4*>(w);
-  float4 v[MAXV], gw[MAXV], dl[MAXV];
-#pragma unroll
-  for (int c = 0; c < MAXV; ++c) {
-    const int i = lane + c * 64;
-    if (i < nv) { v[c] = xr[i]; gw[c] = wr[i]; dl[c] = reinterpret_cast<const float4*>(parts + (int64_t)row * ldp)[i]; }
-  }
-  for (int p = 1; p < np; ++p) {
-    const float4* pr = reinterpret_cast<const float4*>(parts + p * slot + (int64_t)row * ldp);
-#pragma unroll
-    for (int c = 0; c < MAXV; ++c) {
-      const int i = lane + c * 64;
-      if (i < nv) { const float4 t = pr[i]; dl[c].x += t.x; dl[c].y += t.y; dl[c].z += t.z; dl[c].w += t.w; }
-    }
-  }
-  float ss = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXV; ++c) {
-    const int i = lane + c * 64;
-    if (i < nv) {
-      v[c].x += bf2f(f2bf(dl[c].x)); v[c].y += bf2f(f2bf(dl[c].y));
-      v[c].z += bf2f(f2bf(dl[c].z)); v[c].w += bf2f(f2bf(dl[c].w));
-      xr[i] = v[c];
-      ss += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
-    }
-  }
-  if (xn) {
-    ss = wave_sum(ss);
-    const float rs = rsqrtf(ss / (float)cols + eps);
-#pragma unroll
-    for (int c = 0; c < MAXV; ++c) {
-      const int i = lane + c * 64;
-      if (i < nv) {
-        uint2 o;
-        o.x = pack_bf2(gw[c].x * (v[c].x * rs), gw[c].y * (v[c].y * rs));
-        o.y = pack_bf2(gw[c].z * (v[c].z * rs), gw[c].w * (v[c].w * rs));
-        reinterpret_cast<uint2*>(xn + (int64_t)row * cols)[i] = o;
-      }
-    }
-  }
-  if (pos_inc && blockIdx.x == 0 && threadIdx.x == 0) { ++*pos_inc; ++*len_inc; }
 }
 
 // ---- host side: the entry points check their arguments, decode_plan.h says what to launch, and one dispatch function per kernel
@@ -1476,8 +1347,9 @@ extern "C" int ug_skinny_finish(const float* acc, const void* bias, void* out_bf
   UG_REQUIRE(M > 0 && N > 0 && (mode == 0 ? out_bf16 != nullptr : resid != nullptr), "ug_skinny_finish: bad args");
   const int64_t total = M * N;
   int64_t g = (total + 255) / 256; if (g > 1024) g = 1024;
-  hipLaunchKernelGGL(skinny_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, acc, (const bf16_t*)bias, (bf16_t*)out_bf16, resid,
-                     total, (int)N, mode);
+  // one slot; the kernel tells the output by the pointer that is given (mode 0: out_bf16, else resid)
+  hipLaunchKernelGGL(skinny_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, acc, 1, (int64_t)0, (const bf16_t*)bias,
+                     (bf16_t*)(mode == 0 ? out_bf16 : nullptr), (float*)nullptr, mode == 0 ? nullptr : resid, total, (int)N);
   UG_CHECK_LAUNCH("ug_skinny_finish");
   return UG_OK;
 }
@@ -1506,7 +1378,7 @@ extern "C" int ug_skinny_finish_ord(const float* parts, int64_t nparts, int64_t 
              "ug_skinny_finish_ord: bad args (one output of out_bf16 / out_f32 / resid; slots of at least rows x N floats)");
   const int64_t total = M * N;
   int64_t g = (total + 255) / 256; if (g > 1024) g = 1024;
-  hipLaunchKernelGGL(skinny_finish_ord_kernel, dim3((unsigned)g), dim3(256), 0, st, parts, (int)nparts, part_stride, (const bf16_t*)bias,
+  hipLaunchKernelGGL(skinny_finish_kernel, dim3((unsigned)g), dim3(256), 0, st, parts, (int)nparts, part_stride, (const bf16_t*)bias,
                      (bf16_t*)out_bf16, out_f32, resid, total, (int)N);
   UG_CHECK_LAUNCH("ug_skinny_finish_ord");
   return UG_OK;

@@ -17,6 +17,7 @@
 //   weights stream HBM -> LDS by LDS-DMA (nt), 16 rows x 256 k per tile, source-side XOR swizzle, per-wave ring, all vector memory
 //   hand-issued with counted waits (vmem_asm.h); 256 workgroups split the 1.5B model's projections exactly (6 / 70 / 32 weight rows).
 #include "common.h"
+#include "decode_common.h"
 #include "decode_plan.h"
 #include "unigen_hip.h"
 #include "vmem_asm.h"
@@ -42,9 +43,6 @@ struct SwArgs {
   int n0_4, per0, n1_4, per1;                              //   float4 counts and every workgroup's share of them
   int* pos_inc; int* len_inc;                              // advanced by workgroup 0 when given (the step's last reader of pos is behind us)
 };
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ float silu_bf(float g) { return bf2f(f2bf(g / (1.f + __expf(-g)))); }
 
 // Workgroup -> weight rows.  A tile = 16 slots (the MFMA's B columns); `units` are what a workgroup owns:
 //   EPI_RESID / EPI_STORE: unit = weight row, 16 per tile.
@@ -102,13 +100,7 @@ __global__ __launch_bounds__(64 * NW) void gemv_sw_kernel(const bf16_t* W_, cons
   // EPI_ATOMIC: the clears this launch carries (accumulators consumed by earlier launches).  They go out BEHIND the operand loads and the
   // first weight tiles (their arguments are not among the preloaded ones, and stores between those loads would delay them); a thread
   // stores at most a few float4: the counted waits below over-wait by that many tile instructions at worst (vmem_asm.h, rule 1).
-  auto clears = [&] {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int bid = blockIdx.y * gridDim.x + blockIdx.x, tid = threadIdx.x, nt = 64 * NW;
-    if (a.zero0) { const int lo = bid * a.per0, hi = min(a.n0_4, lo + a.per0); for (int i = lo + tid; i < hi; i += nt) reinterpret_cast<float4*>(a.zero0)[i] = z; }
-    if (a.zero1) { const int lo = bid * a.per1, hi = min(a.n1_4, lo + a.per1); for (int i = lo + tid; i < hi; i += nt) reinterpret_cast<float4*>(a.zero1)[i] = z; }
-    if (a.ss_zero && bid == 0 && tid < 32) a.ss_zero[tid] = 0.f;
-  };
+  auto clears = [&] { decode_clear(a, threadIdx.x, blockIdx.y * gridDim.x + blockIdx.x, 64 * NW); };      // (decode_common.h)
   const int u0 = blockIdx.x * f.upw, u1 = min(f.nunits, u0 + f.upw);
   if (u0 >= u1) return;
   const int K = f.K;

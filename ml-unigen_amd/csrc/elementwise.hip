@@ -223,11 +223,15 @@ __global__ __launch_bounds__(256) void rope_kernel(bf16_t* __restrict__ qkv, con
     float o1[4], o2[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      // plain '*' and '+' lexically inside this contract(off) scope: each rounds on its own
-      const float a1 = x1[k] * cc[k], a2 = x2[k] * cc[k];
-      const float b1 = x2[k] * ss[k], b2 = x1[k] * ss[k];
-      if constexpr (!BWD) { o1[k] = a1 - b1; o2[k] = a2 + b2; }
-      else { o1[k] = a1 + b1; o2[k] = a2 - b2; }      // transpose of the rotation
+      if constexpr (!BWD) {
+        rope_pair(x1[k], x2[k], cc[k], ss[k], o1[k], o2[k]);      // (common.h)
+      } else {
+        // rope_bwd_pair's arithmetic (common.h) without its bf16 rounding of the inputs, which are bf16 already.  Plain '*' and '+'
+        // lexically inside this contract(off) scope: each rounds on its own
+        const float a1 = x1[k] * cc[k], a2 = x2[k] * cc[k];
+        const float b1 = x2[k] * ss[k], b2 = x1[k] * ss[k];
+        o1[k] = a1 + b1; o2[k] = a2 - b2;                          // transpose of the rotation
+      }
     }
     uint2 olo, ohi;
     olo.x = pack_bf2(o1[0], o1[1]); olo.y = pack_bf2(o1[2], o1[3]);

@@ -234,17 +234,9 @@ constexpr int EP_ROWS = 32;
 constexpr int EP_PITCH_BF16 = 144, EP_PITCH_F32 = 272;
 constexpr int EP_STRIP = EP_ROWS * EP_PITCH_F32;            // 8704 B per wave (the bf16 strip needs 4608)
 
-// One rotate-half pair exactly as rope_kernel (elementwise.hip) computes it: products and sums round separately, contraction off.
-__device__ __forceinline__ void rope_pair(float x1, float x2, float c, float s, float& o1, float& o2) {
-#pragma clang fp contract(off)
-  const float a1 = x1 * c, a2 = x2 * c;
-  const float b1 = x2 * s, b2 = x1 * s;
-  o1 = a1 - b1; o2 = a2 + b2;
-}
-
 // EPI_ROPE (fused q/k/v projection, round 4): the wave's 64 columns are TWO 32-column pieces of one 128-wide head, 64 apart
 // (nbase .. nbase + 31 and nbase + 64 .. nbase + 95; accumulator column blocks 0, 1 | 2, 3), so the partner x[j + 64] of a
-// rotate-half pair is the same lane's element of block j + 2: RoPE is register arithmetic between the bf16 rounding of
+// rotate-half pair is the same lane's element of block j + 2: RoPE (rope_pair, common.h) is register arithmetic between the bf16 rounding of
 // (acc + bias) and the bf16 rounding of the result -- the same two roundings as ug_gemm_bf16 followed by ug_rope, bit for bit.
 // rope_p0 = column of the wave's first piece inside the head's first half (0 or 32); roped = this tile's columns are q / k heads.
 template <int EPI, int MF = 8>                              // MF = 16-row accumulator blocks of the wave (8, or 10 for 320-row tiles)
