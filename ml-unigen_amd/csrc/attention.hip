@@ -222,6 +222,56 @@ __device__ __forceinline__ bf16x8_t pack_p_sw(const f32x4_t& a, const f32x4_t& b
 __device__ __forceinline__ float group_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); return fmaxf(v, __shfl_xor(v, 32, 64)); }
 __device__ __forceinline__ float group_sum(float v) { v += __shfl_xor(v, 16, 64); return v + __shfl_xor(v, 32, 64); }
 
+// ------------------------------------------------------------------ steps shared by the 16-row kernels
+// (The unrolled loops that read LDS fragments into MFMAs -- the flash step of attn_fwd_kernel / attn_prefill_cached_kernel, the
+// dK/dV tile step and split epilogue of attn_bwd_dkv_kernel / attn_bwd_dkv_dma_kernel, the (kb, j, d) contraction of the 32-row
+// kernels -- stay written out in each kernel: a function is optimised on its own before it is inlined, and each of these as a
+// function moved its kernels' LDS reads, wait counts or registers; docs/experiments.md, "Attention kernels: one definition of each
+// shared step".)
+// this lane's four B-operand fragments of one 128-wide row: its query / dO row, or its key / value row in the dK/dV kernels
+__device__ __forceinline__ void load_frag16(bf16x8_t (&f)[4], const bf16_t* row, int g) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) f[ks] = *reinterpret_cast<const bf16x8_t*>(row + ks * 32 + g * 8);
+}
+// the same for two rows, their loads alternating (Q | dO of a query, K | V of a key): the order the kernels' waits count on
+__device__ __forceinline__ void load_frag16_pair(bf16x8_t (&fa)[4], bf16x8_t (&fb)[4], const bf16_t* rowa, const bf16_t* rowb, int g) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    fa[ks] = *reinterpret_cast<const bf16x8_t*>(rowa + ks * 32 + g * 8);
+    fb[ks] = *reinterpret_cast<const bf16x8_t*>(rowb + ks * 32 + g * 8);
+  }
+}
+__device__ __forceinline__ void zero_acc16(f32x4_t (&a)[8]) {
+#pragma unroll
+  for (int d = 0; d < 8; ++d) a[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+}
+// this lane's 8 x 4 accumulator values of one output row, stored as bf16 (SCALED: times inv, the forward's 1 / l)
+template <bool SCALED>
+__device__ __forceinline__ void store_rows16(bf16_t* row, const f32x4_t (&a)[8], int g, float inv = 1.f) {
+#pragma unroll
+  for (int d = 0; d < 8; ++d) {
+    uint2 w;
+    if constexpr (SCALED) { w.x = pack_bf2(a[d][0] * inv, a[d][1] * inv); w.y = pack_bf2(a[d][2] * inv, a[d][3] * inv); }
+    else { w.x = pack_bf2(a[d][0], a[d][1]); w.y = pack_bf2(a[d][2], a[d][3]); }
+    *reinterpret_cast<uint2*>(row + d * 16 + g * 4) = w;
+  }
+}
+// ------------------------------------------------------------------ steps shared by the backward kernels
+// One score of the backward: p = exp(scale s - lse) = exp2(c1 s - lse2); dS = p (dP - delta) scale = p fma(dP, scale, -delta scale):
+// two + two instructions per score (the exp() / three-factor form took seven).  c1 = scale log2(e), lse2 = lse log2(e),
+// dls = delta scale.
+struct PdS { float p, ds; };
+__device__ __forceinline__ PdS pds_elem(float s, float dp, bool on, float c1, float lse2, float scale, float dls) {
+  const float pr = on ? __builtin_amdgcn_exp2f(__builtin_fmaf(s, c1, -lse2)) : 0.f;
+  return PdS{pr, pr * __builtin_fmaf(dp, scale, -dls)};
+}
+// delta = rowsum(dO * O): the eight dims of one fragment pair added to the lane's partial sum
+__device__ __forceinline__ float dot_acc8(float acc, const bf16x8_t& o, const bf16x8_t& d) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc += bf2f((bf16_t)o[e]) * bf2f((bf16_t)d[e]);
+  return acc;
+}
+
 struct AttnArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v;   // row (b*L+t), head h at +h*128 ; row stride ldq
   bf16_t* o; const bf16_t* dout;                       // [tokens, ldo]
@@ -313,13 +363,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void attn_fwd_kernel(Attn
   const bf16_t* vseq = p.v + (int64_t)b * p.L * p.ldq + hk * HD;
 
   bf16x8_t qf[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8_t*>(qseq + (int64_t)qrow_c * p.ldq + ks * 32 + g * 8);
-
+  load_frag16(qf, qseq + (int64_t)qrow_c * p.ldq, g);
   f32x4_t ot[8];
-#pragma unroll
-  for (int d = 0; d < 8; ++d) ot[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  zero_acc16(ot);
   float m_i = -INFINITY, l_i = 0.f;
   const uint64_t* wrow = p.bits + ((int64_t)b * p.L + qrow_c) * p.nW;
   const int q64 = qt * (NW / 4) + (wave >> 2);                 // this wave's 64-row tile (its own row of tile flags)
@@ -335,7 +381,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void attn_fwd_kernel(Attn
     stage_rm<64 * NW>(Vs, vseq, p.ldq, t * 64, p.L, tid);   // rows past L repeat the last key: their probabilities are exact zeros
     __syncthreads();
     if (!mine) continue;                                        // wave-uniform: this 64-row tile sees none of these keys
-
     f32x4_t st[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -377,13 +422,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 4) void attn_fwd_kernel(Attn
     }
   }
   if (qrow < p.L) {
-    const float inv = (l_i > 0.f) ? 1.f / l_i : 0.f;
-    bf16_t* orow = p.o + ((int64_t)b * p.L + qrow) * p.ldo + h * HD;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-      uint2 w; w.x = pack_bf2(ot[d][0] * inv, ot[d][1] * inv); w.y = pack_bf2(ot[d][2] * inv, ot[d][3] * inv);
-      *reinterpret_cast<uint2*>(orow + d * 16 + g * 4) = w;
-    }
+    store_rows16<true>(p.o + ((int64_t)b * p.L + qrow) * p.ldo + h * HD, ot, g, (l_i > 0.f) ? 1.f / l_i : 0.f);
     if (g == 0) p.lse[((int64_t)b * p.H + h) * p.L + qrow] = (l_i > 0.f) ? m_i + __logf(l_i) : INFINITY;
   }
 }
@@ -420,13 +459,9 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_cached_kernel(AttnCachedA
   const uint8_t* kv = p.key_valid ? p.key_valid + (int64_t)b * p.Tmax : nullptr;
 
   bf16x8_t qf[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8_t*>(qseq + (int64_t)qs_c * p.ldq + ks * 32 + g * 8);
-
+  load_frag16(qf, qseq + (int64_t)qs_c * p.ldq, g);
   f32x4_t ot[8];
-#pragma unroll
-  for (int d = 0; d < 8; ++d) ot[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  zero_acc16(ot);
   float m_i = -INFINITY, l_i = 0.f;
   const int nt = (p.P + min(qt * 64 + 63, p.S - 1)) / 64 + 1;           // key tiles the workgroup's last query row reaches
   const int wave_lim = p.P + min(qt * 64 + wave * 16 + 15, p.S - 1);    // last key position any row of this wave sees
@@ -437,7 +472,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_cached_kernel(AttnCachedA
     stage_rm<256>(Vs, vseq, HD, t * 64, p.Tmax, tid);         // rows past Tmax repeat the last one: their probabilities are exact zeros
     __syncthreads();
     if (t * 64 > wave_lim) continue;                            // wave-uniform: these keys all lie past this wave's rows
-
+    // (from here to the loop's end: attn_fwd_kernel's flash step, but for how `on` is obtained -- change both together)
     f32x4_t st[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -479,15 +514,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_cached_kernel(AttnCachedA
       ot[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_trr(Vs, d, 1, lane), pf1, ot[d], 0, 0, 0);
     }
   }
-  if (qs < p.S) {
-    const float inv = (l_i > 0.f) ? 1.f / l_i : 0.f;
-    bf16_t* orow = p.o + ((int64_t)b * p.S + qs) * p.ldo + h * HD;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-      uint2 w; w.x = pack_bf2(ot[d][0] * inv, ot[d][1] * inv); w.y = pack_bf2(ot[d][2] * inv, ot[d][3] * inv);
-      *reinterpret_cast<uint2*>(orow + d * 16 + g * 4) = w;
-    }
-  }
+  if (qs < p.S) store_rows16<true>(p.o + ((int64_t)b * p.S + qs) * p.ldo + h * HD, ot, g, (l_i > 0.f) ? 1.f / l_i : 0.f);
 }
 
 // ================================================================== forward, 32 query rows per wave (round 3)
@@ -517,19 +544,140 @@ __device__ __forceinline__ bool rows_see_tile(const uint8_t* tileany, int b, int
   for (int q64 = lo >> 6; lo <= hi && q64 <= (hi >> 6); ++q64) v = v || tileany[((int64_t)b * nW + q64) * nW + kt];
   return v;
 }
+template <int ROWS>
+__device__ __forceinline__ int end_aligned_row0(int L, int qt) { return L - ((L + ROWS - 1) / ROWS) * ROWS + qt * ROWS; }
+
+// ---- ring set-up shared by the LDS-DMA kernels (attn_fwd32_kernel, attn_bwd_dq32_kernel, attn_bwd_dkv_dma_kernel)
+// 64-row tile flags (nW <= 64 tiles), fetched ONCE: lane i asks sees(i), bit i of the result is its answer.  (A flag byte fetched
+// per tile right before its use was a dependent global load on every iteration's critical path.)
+template <typename Sees>
+__device__ __forceinline__ uint64_t visible_tiles(int nW, int lane, Sees sees) {
+  bool v = false;
+  if (lane < nW) v = sees(lane);
+  return __ballot(v);
+}
+// the same for two questions at once (one guarded region: the flag loads of both overlap)
+template <typename SeesA, typename SeesB>
+__device__ __forceinline__ void visible_tiles(int nW, int lane, uint64_t& a, uint64_t& b, SeesA sees_a, SeesB sees_b) {
+  bool va = false, vb = false;
+  if (lane < nW) {
+    va = sees_a(lane);
+    vb = sees_b(lane);
+  }
+  a = __ballot(va);
+  b = __ballot(vb);
+}
+__device__ __forceinline__ int next_visible(uint64_t vis, int t, int nW) {
+  const uint64_t rest = t < 64 ? vis >> t : 0ull;
+  return rest ? t + __builtin_ctzll(rest) : nW;
+}
+// LDS-DMA of one 64-row tile: 16 one-KiB instructions, N of them per wave (16 / N waves); instruction i * (16 / N) + wave brings
+// rows 4 inst .. 4 inst + 3 into the image chunk_l = chunk ^ SWZ(row).
+// byte offset of this lane's 16 bytes inside a 64-row tile for each of its DMA instructions: computed ONCE -- recomputed per tile
+// (clamp, 64-bit row x stride product, swizzle) it was 43 VALU + ~40 SALU instructions = a sixth of the loop's issue slots
+template <int N, int (*SWZ)(int)>
+__device__ __forceinline__ void tile_lane_offsets(uint32_t (&off)[N], int64_t ld, int wave, int lane) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int row = (i * (16 / N) + wave) * 4 + (lane >> 4);
+    off[i] = (uint32_t)(row * ld + (((lane & 15) ^ SWZ(row)) << 3)) * 2u;
+  }
+}
+// tile t of two operands (K | V rows of a key tile, or Q | dO rows of a query tile; row strides lda / ldb) into base | base + T32_BYTES
+template <int N, int (*SWZ)(int)>
+__device__ __forceinline__ void stage_pair(char* base, const bf16_t* aseq, const bf16_t* bseq, int64_t lda, int64_t ldb,
+                                           const uint32_t (&aoff)[N], const uint32_t (&boff)[N], int t, int L, int wave, int lane) {
+  const uint64_t ab = (uint64_t)aseq + (int64_t)t * 64 * lda * 2, bb = (uint64_t)bseq + (int64_t)t * 64 * ldb * 2;
+  // hand-issued (vmem_asm.h): behind the builtin hipcc put s_waitcnt vmcnt(0) in front of the tile reads of the kernels' loops -- the
+  // tile requested a moment ago had to LAND before the first MFMA of the current one, i.e. the ring prefetched nothing (round 6)
+  if (t * 64 + 64 <= L) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int inst = i * (16 / N) + wave;
+      dma16(ab, aoff[i], __builtin_amdgcn_readfirstlane(lds_addr_of(base + inst * 1024)));
+      dma16(bb, boff[i], __builtin_amdgcn_readfirstlane(lds_addr_of(base + T32_BYTES + inst * 1024)));
+    }
+  } else {       // the sequence's last, partial tile: rows past L repeat row L - 1 (keys: their probabilities are exact zeros; queries: their mask words are 0)
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int inst = i * (16 / N) + wave;
+      const int row = inst * 4 + (lane >> 4);
+      const int c8 = ((lane & 15) ^ SWZ(row)) << 3;
+      const int rr = min(t * 64 + row, L - 1) - t * 64;
+      dma16(ab, (uint32_t)(rr * lda + c8) * 2u, __builtin_amdgcn_readfirstlane(lds_addr_of(base + inst * 1024)));
+      dma16(bb, (uint32_t)(rr * ldb + c8) * 2u, __builtin_amdgcn_readfirstlane(lds_addr_of(base + T32_BYTES + inst * 1024)));
+    }
+  }
+}
+
+// ---- steps shared by the 32-row kernels (attn_fwd32_kernel, attn_bwd_dq32_kernel)
+__device__ __forceinline__ void zero_acc32(f32x16_t (&a)[4]) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[d][r] = 0.f;
+}
+// per-lane fragment offsets inside a swz16 tile: koff[ks] the row-major A fragment of k-step ks (row n = lane & 31), voff[d][e] the
+// two transposing reads of the fragment for output columns 32 d .. 32 d + 31
+__device__ __forceinline__ void frag_offsets32(int (&koff)[8], int (&voff)[4][2], int lane) {
+  const int n = lane & 31, hh = lane >> 5, i16 = lane & 15, grp = (lane >> 4) & 1;
+  const int sw = swz16(n);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) koff[ks] = n * 256 + (((ks * 2 + hh) ^ sw) << 4);
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int key = 4 * hh + (i16 >> 2) + 8 * e;                    // + 16 j + 32 kb: multiples of 16 leave swz16 unchanged
+      const int chunk = d * 4 + grp * 2 + ((i16 & 3) >> 1);
+      voff[d][e] = key * 256 + ((chunk ^ swz16(key)) << 4) + (i16 & 1) * 8;
+    }
+}
+// registers 8 j .. 8 j + 7 of a 32 x 32 accumulator as the B operand of k-step j
+__device__ __forceinline__ bf16x8_t pack16(const f32x16_t& s, int j) {
+  uint4 u;
+  u.x = pack_bf2(s[j * 8 + 0], s[j * 8 + 1]); u.y = pack_bf2(s[j * 8 + 2], s[j * 8 + 3]);
+  u.z = pack_bf2(s[j * 8 + 4], s[j * 8 + 5]); u.w = pack_bf2(s[j * 8 + 6], s[j * 8 + 7]);
+  return __builtin_bit_cast(bf16x8_t, u);
+}
+// A fragment of tile^T for output columns 32 d .. 32 d + 31 over the 16 rows at tb (vo = voff[d]): two transposing reads of 4
+// consecutive rows each
+__device__ __forceinline__ bf16x8_t frag32_tr(const char* tb, const int (&vo)[2]) {
+  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(tb + vo[0]));
+  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(tb + vo[1]));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// register r of block d is column d * 32 + (r >> 2) * 8 + hh * 4 + (r & 3) of this lane's row (SCALED: times inv, the forward's 1 / l)
+template <bool SCALED>
+__device__ __forceinline__ void store_rows32(bf16_t* row, const f32x16_t (&a)[4], int hh, float inv = 1.f) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint2 w;
+      if constexpr (SCALED) {
+        w.x = pack_bf2(a[d][q * 4 + 0] * inv, a[d][q * 4 + 1] * inv);
+        w.y = pack_bf2(a[d][q * 4 + 2] * inv, a[d][q * 4 + 3] * inv);
+      } else {
+        w.x = pack_bf2(a[d][q * 4 + 0], a[d][q * 4 + 1]);
+        w.y = pack_bf2(a[d][q * 4 + 2], a[d][q * 4 + 3]);
+      }
+      *reinterpret_cast<uint2*>(row + d * 32 + q * 8 + hh * 4) = w;
+    }
+}
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd32_kernel(AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char ring[2 * 2 * T32_BYTES];       // [slot][K | V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = lane & 31, hh = lane >> 5, i16 = lane & 15, grp = (lane >> 4) & 1;
+  const int n = lane & 31, hh = lane >> 5;
   constexpr int ROWS = 32 * NW;
   const WgCoord wc = wg_coord((int)blockIdx.x, (p.L + ROWS - 1) / ROWS, p.H, p.HKV, p.B, true, p.order != 0);
   if (!wc.ok) return;
   const int qt = wc.tile, h = wc.h, b = wc.b;
   const int hk = h / (p.H / p.HKV);
-  const int row0 = p.L - ((p.L + ROWS - 1) / ROWS) * ROWS + qt * ROWS;       // end-aligned tiles: < 0 in the first one
+  const int row0 = end_aligned_row0<ROWS>(p.L, qt);                          // < 0 in the first tile
   const int qrow = row0 + wave * 32 + n;
   const bool qlive = qrow >= 0;                                              // (always < L)
   const int qrow_c = max(qrow, 0);
@@ -542,80 +690,24 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd32_kernel(AttnArgs p) {
   for (int ks = 0; ks < 8; ++ks)
     qf[ks] = *reinterpret_cast<const bf16x8_t*>(qseq + (int64_t)qrow_c * p.ldq + ks * 16 + hh * 8);
   f32x16_t ot[4];
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ot[d][r] = 0.f;
+  zero_acc32(ot);
   float m_i = -INFINITY, l_i = 0.f;                    // running maximum of the RAW scores, running sum
   const float c1 = p.scale * 1.4426950408889634f;      // exp(scale * s) = exp2(c1 * s)
   const uint64_t* wrow = p.bits + ((int64_t)b * p.L + qrow_c) * p.nW;
-  // 64-row tile flags (nW <= 64 tiles), fetched ONCE: bit t of `vis` = some row of the workgroup sees key tile t (uniform),
-  // bit t of `minem` = this wave's 32 rows do.  (A flag byte fetched per tile right before its use was a dependent global
-  // load on every iteration's critical path.)
+  // bit t of `vis` = some row of the workgroup sees key tile t (uniform), bit t of `minem` = this wave's 32 rows do
   uint64_t vis, minem;
-  {
-    bool v = false, m = false;
-    if (lane < p.nW) {
-      v = rows_see_tile(p.tileany, b, p.nW, row0, row0 + ROWS - 1, p.L, lane);
-      m = rows_see_tile(p.tileany, b, p.nW, row0 + wave * 32, row0 + wave * 32 + 31, p.L, lane);
-    }
-    vis = __ballot(v);
-    minem = __ballot(m);
-  }
-  auto next_visible = [&](int t) {
-    const uint64_t rest = t < 64 ? vis >> t : 0ull;
-    return rest ? t + __builtin_ctzll(rest) : p.nW;
-  };
-  // LDS-DMA of one K / V tile pair: 16 one-KiB instructions per operand, 16 / NW per wave
-  // byte offset of this lane's 16 bytes inside a 64-key tile for each of its DMA instructions: computed ONCE -- recomputed per tile
-  // (clamp, 64-bit row x stride product, swizzle) it was 43 VALU + ~40 SALU instructions = a sixth of the loop's issue slots
+  visible_tiles(
+      p.nW, lane, vis, minem, [&](int kt) { return rows_see_tile(p.tileany, b, p.nW, row0, row0 + ROWS - 1, p.L, kt); },
+      [&](int kt) { return rows_see_tile(p.tileany, b, p.nW, row0 + wave * 32, row0 + wave * 32 + 31, p.L, kt); });
   uint32_t toff[16 / NW];
-#pragma unroll
-  for (int i = 0; i < 16 / NW; ++i) {
-    const int row = (i * NW + wave) * 4 + (lane >> 4);
-    toff[i] = (uint32_t)(row * p.ldq + (((lane & 15) ^ swz16(row)) << 3)) * 2u;
-  }
+  tile_lane_offsets<16 / NW, swz16>(toff, p.ldq, wave, lane);
   auto stage = [&](int t, int slot) {
-    char* base = ring + slot * 2 * T32_BYTES;
-    const int64_t tb = (int64_t)t * 64 * p.ldq * 2;
-    const uint64_t kb = (uint64_t)kseq + tb, vb = (uint64_t)vseq + tb;
-    // hand-issued (vmem_asm.h): behind the builtin hipcc put s_waitcnt vmcnt(0) in front of the tile reads below -- the tile
-    // requested a moment ago had to LAND before the first MFMA of the current one, i.e. the ring prefetched nothing (round 6)
-    if (t * 64 + 64 <= p.L) {
-#pragma unroll
-      for (int i = 0; i < 16 / NW; ++i) {
-        const int inst = i * NW + wave;
-        dma16(kb, toff[i], __builtin_amdgcn_readfirstlane(lds_addr_of(base + inst * 1024)));
-        dma16(vb, toff[i], __builtin_amdgcn_readfirstlane(lds_addr_of(base + T32_BYTES + inst * 1024)));
-      }
-    } else {                                             // the sequence's last, partial tile: rows past L repeat row L - 1
-#pragma unroll
-      for (int i = 0; i < 16 / NW; ++i) {
-        const int inst = i * NW + wave;
-        const int row = inst * 4 + (lane >> 4);
-        const uint32_t off = (uint32_t)((min(t * 64 + row, p.L - 1) - t * 64) * p.ldq + (((lane & 15) ^ swz16(row)) << 3)) * 2u;
-        dma16(kb, off, __builtin_amdgcn_readfirstlane(lds_addr_of(base + inst * 1024)));
-        dma16(vb, off, __builtin_amdgcn_readfirstlane(lds_addr_of(base + T32_BYTES + inst * 1024)));
-      }
-    }
+    stage_pair<16 / NW, swz16>(ring + slot * 2 * T32_BYTES, kseq, vseq, p.ldq, p.ldq, toff, toff, t, p.L, wave, lane);
   };
-  // per-lane fragment offsets inside a tile
   int koff[8], voff[4][2];
-  {
-    const int sw = swz16(n);
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) koff[ks] = n * 256 + (((ks * 2 + hh) ^ sw) << 4);
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int key = 4 * hh + (i16 >> 2) + 8 * e;                    // + 16 j + 32 kb: multiples of 16 leave swz16 unchanged
-        const int chunk = d * 4 + grp * 2 + ((i16 & 3) >> 1);
-        voff[d][e] = key * 256 + ((chunk ^ swz16(key)) << 4) + (i16 & 1) * 8;
-      }
-  }
+  frag_offsets32(koff, voff, lane);
 
-  int t = next_visible(0);
+  int t = next_visible(vis, 0, p.nW);
   if (t < p.nW) stage(t, 0);
   // The mask word of a tile is requested one tile ahead, like its K / V rows.  It stays a compiler-visible load (a hand-issued one
   // would be a loop-carried register in flight, which the compiler may copy before it lands); what matters is WHERE its first use
@@ -625,7 +717,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd32_kernel(AttnArgs p) {
 #pragma unroll
   for (int ks = 0; ks < 8; ++ks) tie(qf[ks]);            // (the query fragments' own wait falls here, ahead of the loop)
   for (int it = 0; t < p.nW; ++it) {
-    const int tn = next_visible(t + 1);
+    const int tn = next_visible(vis, t + 1, p.nW);
     wait_vm<0>();                                        // this wave's share of tile t has landed (and its mask word)
     tie(wcur);
     asm volatile("s_barrier" ::: "memory");               // ... everyone's has; everyone is past its reads of the other slot
@@ -688,12 +780,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd32_kernel(AttnArgs p) {
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          uint4 u;
-          u.x = pack_bf2(st[kb][j * 8 + 0], st[kb][j * 8 + 1]); u.y = pack_bf2(st[kb][j * 8 + 2], st[kb][j * 8 + 3]);
-          u.z = pack_bf2(st[kb][j * 8 + 4], st[kb][j * 8 + 5]); u.w = pack_bf2(st[kb][j * 8 + 6], st[kb][j * 8 + 7]);
-          pf[kb][j] = __builtin_bit_cast(bf16x8_t, u);
-        }
+        for (int j = 0; j < 2; ++j) pf[kb][j] = pack16(st[kb], j);
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -701,9 +788,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd32_kernel(AttnArgs p) {
 #pragma unroll
           for (int d = 0; d < 4; ++d) {                    // four independent accumulators in turn
             const char* vb = Vs + kb * 8192 + j * 4096;
-            const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(vb + voff[d][0]));
-            const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(vb + voff[d][1]));
-            const bf16x8_t a = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            const bf16x8_t a = frag32_tr(vb, voff[d]);
             ot[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(hwbf16x8_t, a), __builtin_bit_cast(hwbf16x8_t, pf[kb][j]),
                                                             ot[d], 0, 0, 0);
           }
@@ -712,17 +797,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd32_kernel(AttnArgs p) {
     wcur = wnext;
   }
   if (qlive) {
-    const float inv = (l_i > 0.f) ? 1.f / l_i : 0.f;
-    bf16_t* orow = p.o + ((int64_t)b * p.L + qrow) * p.ldo + h * HD;
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        uint2 w;
-        w.x = pack_bf2(ot[d][q * 4 + 0] * inv, ot[d][q * 4 + 1] * inv);
-        w.y = pack_bf2(ot[d][q * 4 + 2] * inv, ot[d][q * 4 + 3] * inv);
-        *reinterpret_cast<uint2*>(orow + d * 32 + q * 8 + hh * 4) = w;
-      }
+    store_rows32<true>(p.o + ((int64_t)b * p.L + qrow) * p.ldo + h * HD, ot, hh, (l_i > 0.f) ? 1.f / l_i : 0.f);
     if (hh == 0) p.lse[((int64_t)b * p.H + h) * p.L + qrow] = (l_i > 0.f) ? m_i * p.scale + __logf(l_i) : INFINITY;
   }
 }
@@ -745,30 +820,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
   const bf16_t* doseq = p.dout + (int64_t)b * p.L * p.ldo + h * HD;
 
   bf16x8_t qf[4], dof[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    qf[ks] = *reinterpret_cast<const bf16x8_t*>(qseq + (int64_t)qrow_c * p.ldq + ks * 32 + g * 8);
-    dof[ks] = *reinterpret_cast<const bf16x8_t*>(doseq + (int64_t)qrow_c * p.ldo + ks * 32 + g * 8);
-  }
+  load_frag16_pair(qf, dof, qseq + (int64_t)qrow_c * p.ldq, doseq + (int64_t)qrow_c * p.ldo, g);
   const float lse = p.lse[((int64_t)b * p.H + h) * p.L + qrow_c];
   // delta = rowsum(dO * O) of this lane's query row, computed here (the four lanes g = 0..3 of a row hold its 128 dims)
   // and published for the dK/dV kernel that runs next: no separate pass over O and dO
   float dl = 0.f;
   {
     const bf16_t* oseq = p.o + (int64_t)b * p.L * p.ldo + h * HD;
+    bf16x8_t of[4];
+    load_frag16(of, oseq + (int64_t)qrow_c * p.ldo, g);
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const bf16x8_t of = *reinterpret_cast<const bf16x8_t*>(oseq + (int64_t)qrow_c * p.ldo + ks * 32 + g * 8);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) dl += bf2f((bf16_t)of[e]) * bf2f((bf16_t)dof[ks][e]);
-    }
+    for (int ks = 0; ks < 4; ++ks) dl = dot_acc8(dl, of[ks], dof[ks]);
     dl += __shfl_xor(dl, 16, 64);
     dl += __shfl_xor(dl, 32, 64);
     if (g == 0 && qrow < p.L) const_cast<float*>(p.delta)[((int64_t)b * p.H + h) * p.L + qrow] = dl;
   }
   f32x4_t dqt[8];
-#pragma unroll
-  for (int d = 0; d < 8; ++d) dqt[d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  zero_acc16(dqt);
   const float c1 = p.scale * 1.4426950408889634f, lse2 = lse * 1.4426950408889634f, dls = dl * p.scale;
   const uint64_t* wrow = p.bits + ((int64_t)b * p.L + qrow_c) * p.nW;
   const uint8_t* tany = p.tileany + ((int64_t)b * p.nW + qt) * p.nW;
@@ -790,14 +858,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
         s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rm(Ks, j, ks, lane), qf[ks], s, 0, 0, 0);
         dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_rm(Vs, j, ks, lane), dof[ks], dp, 0, 0, 0);
       }
-      // p = exp(scale s - lse) = exp2(c1 s - lse2); dS = p (dP - delta) scale = p fma(dP, scale, -delta scale): two + two
-      // instructions per score (the exp() / three-factor form took seven).  (A wave-uniform "tile fully visible" branch around
-      // the bit test was measured SLOWER: +9 % on the full mask -- the branch keeps the next block's MFMAs from overlapping.)
+      // (A wave-uniform "tile fully visible" branch around the bit test was measured SLOWER: +9 % on the full mask -- the branch
+      // keeps the next block's MFMAs from overlapping.)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const bool on = ((j < 2 ? mlo : mhi) >> ((j & 1) * 16 + r)) & 1u;
-        const float pr = on ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c1, -lse2)) : 0.f;
-        ds[j][r] = pr * __builtin_fmaf(dp[r], p.scale, -dls);
+        ds[j][r] = pds_elem(s[r], dp[r], on, c1, lse2, p.scale, dls).ds;
       }
     }
     const bf16x8_t sf0 = pack_p_sw(ds[0], ds[1]), sf1 = pack_p_sw(ds[2], ds[3]);
@@ -806,14 +872,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
 #pragma unroll
     for (int d = 0; d < 8; ++d) dqt[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_trr(Ks, d, 1, lane), sf1, dqt[d], 0, 0, 0);
   }
-  if (qrow < p.L) {
-    bf16_t* drow = p.dq + ((int64_t)b * p.L + qrow) * p.ldg + h * HD;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-      uint2 w; w.x = pack_bf2(dqt[d][0], dqt[d][1]); w.y = pack_bf2(dqt[d][2], dqt[d][3]);
-      *reinterpret_cast<uint2*>(drow + d * 16 + g * 4) = w;
-    }
-  }
+  if (qrow < p.L) store_rows16<false>(p.dq + ((int64_t)b * p.L + qrow) * p.ldg + h * HD, dqt, g);
 }
 
 // ================================================================== backward: dQ on 32-row waves (round 3)
@@ -826,13 +885,13 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_dq32_kernel(AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char ring[2 * 2 * T32_BYTES];       // [slot][K | V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = lane & 31, hh = lane >> 5, i16 = lane & 15, grp = (lane >> 4) & 1;
+  const int n = lane & 31, hh = lane >> 5;
   constexpr int ROWS = 32 * NW;
   const WgCoord wc = wg_coord((int)blockIdx.x, (p.L + ROWS - 1) / ROWS, p.H, p.HKV, p.B, true, p.order != 0);
   if (!wc.ok) return;
   const int qt = wc.tile, h = wc.h, b = wc.b;
   const int hk = h / (p.H / p.HKV);
-  const int row0 = p.L - ((p.L + ROWS - 1) / ROWS) * ROWS + qt * ROWS;       // end-aligned tiles: < 0 in the first one
+  const int row0 = end_aligned_row0<ROWS>(p.L, qt);                          // < 0 in the first tile
   const int qrow = row0 + wave * 32 + n;
   const bool qlive = qrow >= 0;                                              // (always < L)
   const int qrow_c = max(qrow, 0);
@@ -849,87 +908,34 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_dq32_kernel(AttnArgs p) {
     qf[ks] = *reinterpret_cast<const bf16x8_t*>(qseq + (int64_t)qrow_c * p.ldq + ks * 16 + hh * 8);
     dof[ks] = *reinterpret_cast<const bf16x8_t*>(doseq + (int64_t)qrow_c * p.ldo + ks * 16 + hh * 8);
     const bf16x8_t of = *reinterpret_cast<const bf16x8_t*>(oseq + (int64_t)qrow_c * p.ldo + ks * 16 + hh * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) dl += bf2f((bf16_t)of[e]) * bf2f((bf16_t)dof[ks][e]);
+    dl = dot_acc8(dl, of, dof[ks]);
   }
   dl += __shfl_xor(dl, 32, 64);                           // the two lanes of a row hold 64 of its 128 dims each
   if (hh == 0 && qlive) const_cast<float*>(p.delta)[((int64_t)b * p.H + h) * p.L + qrow] = dl;
   const float lse = p.lse[((int64_t)b * p.H + h) * p.L + qrow_c];
   const float c1 = p.scale * 1.4426950408889634f, lse2 = lse * 1.4426950408889634f, dls = dl * p.scale;
   f32x16_t dqt[4];
-#pragma unroll
-  for (int d = 0; d < 4; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dqt[d][r] = 0.f;
+  zero_acc32(dqt);
   const uint64_t* wrow = p.bits + ((int64_t)b * p.L + qrow_c) * p.nW;
   uint64_t vis, minem;
-  {
-    bool v = false, m = false;
-    if (lane < p.nW) {
-      v = rows_see_tile(p.tileany, b, p.nW, row0, row0 + ROWS - 1, p.L, lane);
-      m = rows_see_tile(p.tileany, b, p.nW, row0 + wave * 32, row0 + wave * 32 + 31, p.L, lane);
-    }
-    vis = __ballot(v);
-    minem = __ballot(m);
-  }
-  auto next_visible = [&](int t) {
-    const uint64_t rest = t < 64 ? vis >> t : 0ull;
-    return rest ? t + __builtin_ctzll(rest) : p.nW;
-  };
-  // byte offset of this lane's 16 bytes inside a 64-key tile for each of its DMA instructions: computed ONCE -- recomputed per tile
-  // (clamp, 64-bit row x stride product, swizzle) it was 43 VALU + ~40 SALU instructions = a sixth of the loop's issue slots
+  visible_tiles(
+      p.nW, lane, vis, minem, [&](int kt) { return rows_see_tile(p.tileany, b, p.nW, row0, row0 + ROWS - 1, p.L, kt); },
+      [&](int kt) { return rows_see_tile(p.tileany, b, p.nW, row0 + wave * 32, row0 + wave * 32 + 31, p.L, kt); });
   uint32_t toff[16 / NW];
-#pragma unroll
-  for (int i = 0; i < 16 / NW; ++i) {
-    const int row = (i * NW + wave) * 4 + (lane >> 4);
-    toff[i] = (uint32_t)(row * p.ldq + (((lane & 15) ^ swz16(row)) << 3)) * 2u;
-  }
+  tile_lane_offsets<16 / NW, swz16>(toff, p.ldq, wave, lane);
   auto stage = [&](int t, int slot) {
-    char* base = ring + slot * 2 * T32_BYTES;
-    const int64_t tb = (int64_t)t * 64 * p.ldq * 2;
-    const uint64_t kb = (uint64_t)kseq + tb, vb = (uint64_t)vseq + tb;
-    // hand-issued (vmem_asm.h): behind the builtin hipcc put s_waitcnt vmcnt(0) in front of the tile reads below -- the tile
-    // requested a moment ago had to LAND before the first MFMA of the current one, i.e. the ring prefetched nothing (round 6)
-    if (t * 64 + 64 <= p.L) {
-#pragma unroll
-      for (int i = 0; i < 16 / NW; ++i) {
-        const int inst = i * NW + wave;
-        dma16(kb, toff[i], __builtin_amdgcn_readfirstlane(lds_addr_of(base + inst * 1024)));
-        dma16(vb, toff[i], __builtin_amdgcn_readfirstlane(lds_addr_of(base + T32_BYTES + inst * 1024)));
-      }
-    } else {                                             // the sequence's last, partial tile: rows past L repeat row L - 1
-#pragma unroll
-      for (int i = 0; i < 16 / NW; ++i) {
-        const int inst = i * NW + wave;
-        const int row = inst * 4 + (lane >> 4);
-        const uint32_t off = (uint32_t)((min(t * 64 + row, p.L - 1) - t * 64) * p.ldq + (((lane & 15) ^ swz16(row)) << 3)) * 2u;
-        dma16(kb, off, __builtin_amdgcn_readfirstlane(lds_addr_of(base + inst * 1024)));
-        dma16(vb, off, __builtin_amdgcn_readfirstlane(lds_addr_of(base + T32_BYTES + inst * 1024)));
-      }
-    }
+    stage_pair<16 / NW, swz16>(ring + slot * 2 * T32_BYTES, kseq, vseq, p.ldq, p.ldq, toff, toff, t, p.L, wave, lane);
   };
   int koff[8], voff[4][2];
-  {
-    const int sw = swz16(n);
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) koff[ks] = n * 256 + (((ks * 2 + hh) ^ sw) << 4);
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int key = 4 * hh + (i16 >> 2) + 8 * e;
-        const int chunk = d * 4 + grp * 2 + ((i16 & 3) >> 1);
-        voff[d][e] = key * 256 + ((chunk ^ swz16(key)) << 4) + (i16 & 1) * 8;
-      }
-  }
+  frag_offsets32(koff, voff, lane);
 
-  int t = next_visible(0);
+  int t = next_visible(vis, 0, p.nW);
   if (t < p.nW) stage(t, 0);
   uint64_t wcur = t < p.nW ? wrow[t] : 0ull;             // (first use right behind the loop-top drain: see attn_fwd32_kernel)
 #pragma unroll
   for (int ks = 0; ks < 8; ++ks) { tie(qf[ks]); tie(dof[ks]); }
   for (int it = 0; t < p.nW; ++it) {
-    const int tn = next_visible(t + 1);
+    const int tn = next_visible(vis, t + 1, p.nW);
     wait_vm<0>();
     tie(wcur);
     asm volatile("s_barrier" ::: "memory");
@@ -955,27 +961,19 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_dq32_kernel(AttnArgs p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const bool on = (w2 >> (kb * 32 + (r >> 2) * 8 + (r & 3))) & 1ull;
-          const float pr = on ? __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], c1, -lse2)) : 0.f;
-          sc[r] = pr * __builtin_fmaf(dp[r], p.scale, -dls);
+          sc[r] = pds_elem(sc[r], dp[r], on, c1, lse2, p.scale, dls).ds;
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          uint4 u;
-          u.x = pack_bf2(sc[j * 8 + 0], sc[j * 8 + 1]); u.y = pack_bf2(sc[j * 8 + 2], sc[j * 8 + 3]);
-          u.z = pack_bf2(sc[j * 8 + 4], sc[j * 8 + 5]); u.w = pack_bf2(sc[j * 8 + 6], sc[j * 8 + 7]);
-          sf[kb][j] = __builtin_bit_cast(bf16x8_t, u);
-        }
+        for (int j = 0; j < 2; ++j) sf[kb][j] = pack16(sc, j);
       }
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-          for (int d = 0; d < 4; ++d) {
+          for (int d = 0; d < 4; ++d) {                    // (attn_fwd32_kernel's P.V loop with K for V and dS for P)
             const char* kb_ = Ks + kb * 8192 + j * 4096;
-            const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(kb_ + voff[d][0]));
-            const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(kb_ + voff[d][1]));
-            const bf16x8_t a = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            const bf16x8_t a = frag32_tr(kb_, voff[d]);
             dqt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(hwbf16x8_t, a), __builtin_bit_cast(hwbf16x8_t, sf[kb][j]),
                                                              dqt[d], 0, 0, 0);
           }
@@ -1002,18 +1000,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_dq32_kernel(AttnArgs p) {
         }
       }
   }
-  if (qlive) {
-    bf16_t* drow = p.dq + ((int64_t)b * p.L + qrow) * p.ldg + h * HD;
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        uint2 w;
-        w.x = pack_bf2(dqt[d][q * 4 + 0], dqt[d][q * 4 + 1]);
-        w.y = pack_bf2(dqt[d][q * 4 + 2], dqt[d][q * 4 + 3]);
-        *reinterpret_cast<uint2*>(drow + d * 32 + q * 8 + hh * 4) = w;
-      }
-  }
+  if (qlive) store_rows32<false>(p.dq + ((int64_t)b * p.L + qrow) * p.ldg + h * HD, dqt, hh);
   if (p.dbias) {
     // bias gradient of the q projection: column sums of the stored (bf16) values over this workgroup's rows
     float x[64];
@@ -1065,14 +1052,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnArgs p) {
   const bf16_t* kseq = p.k + (int64_t)b * p.L * p.ldq + hk * HD;
   const bf16_t* vseq = p.v + (int64_t)b * p.L * p.ldq + hk * HD;
   bf16x8_t kf[4], vf[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    kf[ks] = *reinterpret_cast<const bf16x8_t*>(kseq + (int64_t)krow_c * p.ldq + ks * 32 + g * 8);
-    vf[ks] = *reinterpret_cast<const bf16x8_t*>(vseq + (int64_t)krow_c * p.ldq + ks * 32 + g * 8);
-  }
+  load_frag16_pair(kf, vf, kseq + (int64_t)krow_c * p.ldq, vseq + (int64_t)krow_c * p.ldq, g);
   f32x4_t dkt[8], dvt[8];
-#pragma unroll
-  for (int d = 0; d < 8; ++d) { dkt[d] = f32x4_t{0.f, 0.f, 0.f, 0.f}; dvt[d] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+  zero_acc16(dkt);
+  zero_acc16(dvt);
   const int kbit = wave * 16 + (lane & 15);
   const float c1 = p.scale * 1.4426950408889634f;
 
@@ -1109,9 +1092,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnArgs p) {
         for (int r = 0; r < 4; ++r) {
           const int ql = j * 16 + g * 4 + r;
           const bool on = (word_s[ql] >> kbit) & 1ull;
-          const float e = on ? __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c1, -ls[r])) : 0.f;
-          pr[j][r] = e;
-          ds[j][r] = e * __builtin_fmaf(dp[r], p.scale, -dl4[r]);
+          const PdS e = pds_elem(s[r], dp[r], on, c1, ls[r], p.scale, dl4[r]);
+          pr[j][r] = e.p;
+          ds[j][r] = e.ds;
         }
       }
       const bf16x8_t pf0 = pack_p(pr[0], pr[1]), pf1 = pack_p(pr[2], pr[3]);
@@ -1215,57 +1198,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(AttnArgs p) {
   const bf16_t* doseq = p.dout + (int64_t)b * p.L * p.ldo + h0 * HD;
   int h = h0;
   bf16x8_t kf[4], vf[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    kf[ks] = *reinterpret_cast<const bf16x8_t*>(kseq + (int64_t)krow_c * p.ldq + ks * 32 + g * 8);
-    vf[ks] = *reinterpret_cast<const bf16x8_t*>(vseq + (int64_t)krow_c * p.ldq + ks * 32 + g * 8);
-  }
+  load_frag16_pair(kf, vf, kseq + (int64_t)krow_c * p.ldq, vseq + (int64_t)krow_c * p.ldq, g);
   f32x4_t dkt[8], dvt[8];
-#pragma unroll
-  for (int d = 0; d < 8; ++d) { dkt[d] = f32x4_t{0.f, 0.f, 0.f, 0.f}; dvt[d] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+  zero_acc16(dkt);
+  zero_acc16(dvt);
   const int kbit = wave * 16 + (lane & 15);
   const float c1 = p.scale * 1.4426950408889634f;
-  // visible query tiles of this key tile (nW <= 64), fetched once
-  uint64_t vis;
-  {
-    bool v = false;
-    if (lane < p.nW) v = p.tileany[((int64_t)b * p.nW + lane) * p.nW + t];
-    vis = __ballot(v);
-  }
-  auto next_visible = [&](int q) {
-    const uint64_t rest = q < 64 ? vis >> q : 0ull;
-    return rest ? q + __builtin_ctzll(rest) : p.nW;
-  };
-  // lane offsets inside a query tile (Q rows and dO rows have their own strides), computed once (see attn_fwd32_kernel)
+  // visible query tiles of this key tile
+  const uint64_t vis = visible_tiles(p.nW, lane, [&](int q) { return (bool)p.tileany[((int64_t)b * p.nW + q) * p.nW + t]; });
+  // lane offsets inside a query tile: Q rows and dO rows have their own strides
   uint32_t qoff[4], dooff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (i * 4 + wave) * 4 + (lane >> 4);
-    const int c8 = ((lane & 15) ^ swz16b(row)) << 3;
-    qoff[i] = (uint32_t)(row * p.ldq + c8) * 2u;
-    dooff[i] = (uint32_t)(row * p.ldo + c8) * 2u;
-  }
+  tile_lane_offsets<4, swz16b>(qoff, p.ldq, wave, lane);
+  tile_lane_offsets<4, swz16b>(dooff, p.ldo, wave, lane);
   auto stage = [&](int qt, int slot) {
-    char* base = ring + slot * 2 * T32_BYTES;
-    const uint64_t qb = (uint64_t)qseq + (int64_t)qt * 64 * p.ldq * 2, dob = (uint64_t)doseq + (int64_t)qt * 64 * p.ldo * 2;
-    if (qt * 64 + 64 <= p.L) {                           // (hand-issued: see attn_fwd32_kernel)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int inst = i * 4 + wave;
-        dma16(qb, qoff[i], __builtin_amdgcn_readfirstlane(lds_addr_of(base + inst * 1024)));
-        dma16(dob, dooff[i], __builtin_amdgcn_readfirstlane(lds_addr_of(base + T32_BYTES + inst * 1024)));
-      }
-    } else {                                             // rows past L repeat the last row: their mask words are 0
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int inst = i * 4 + wave;
-        const int row = inst * 4 + (lane >> 4);
-        const int c8 = ((lane & 15) ^ swz16b(row)) << 3;
-        const int rr = min(qt * 64 + row, p.L - 1) - qt * 64;
-        dma16(qb, (uint32_t)(rr * p.ldq + c8) * 2u, __builtin_amdgcn_readfirstlane(lds_addr_of(base + inst * 1024)));
-        dma16(dob, (uint32_t)(rr * p.ldo + c8) * 2u, __builtin_amdgcn_readfirstlane(lds_addr_of(base + T32_BYTES + inst * 1024)));
-      }
-    }
+    stage_pair<4, swz16b>(ring + slot * 2 * T32_BYTES, qseq, doseq, p.ldq, p.ldo, qoff, dooff, qt, p.L, wave, lane);
   };
   // row record of a query tile (wave 0, one lane per row): requested a tile ahead, parked in LDS before the tile's barrier
   float r_lse = 0.f, r_dl = 0.f;
@@ -1281,13 +1227,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(AttnArgs p) {
   };
 
   // the (head, visible query tile) sequence: head h0's tiles, then head h0 + 1's, ... -- one ring, one barrier per step
-  int qt = next_visible(0);
+  int qt = next_visible(vis, 0, p.nW);
   int hleft = qt < p.nW ? HPW - 1 : 0;                    // heads still to come after the current one
   if (qt < p.nW) { stage(qt, 0); if (wave == 0) fetch_rows(qt); }
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) { tie(kf[ks]); tie(vf[ks]); }          // (the key / value fragments' own wait falls here, ahead of the loop)
   for (int it = 0; qt < p.nW; ++it) {
-    int qn = next_visible(qt + 1);
+    int qn = next_visible(vis, qt + 1, p.nW);
     const int slot = it & 1;
     wait_vm<0>();                                        // this wave's share of the tile has landed (and wave 0's row records)
     if (wave == 0) {
@@ -1301,7 +1247,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(AttnArgs p) {
     if (qn >= p.nW && hleft > 0) {                        // next head: its Q / dO / row records from the first visible tile on
       --hleft; ++h;
       qseq += HD; doseq += HD;
-      qn = next_visible(0);
+      qn = next_visible(vis, 0, p.nW);
     }
     if (qn < p.nW) { stage(qn, slot ^ 1); if (wave == 0) fetch_rows(qn); }
     const char* Qs = ring + slot * 2 * T32_BYTES;
@@ -1321,9 +1267,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(AttnArgs p) {
       for (int r = 0; r < 4; ++r) {
         const int ql = j * 16 + g * 4 + r;
         const bool on = (word_s[slot][ql] >> kbit) & 1ull;
-        const float e = on ? __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], c1, -ls[r])) : 0.f;
-        pr[j][r] = e;
-        ds[j][r] = e * __builtin_fmaf(dp[r], p.scale, -dl4[r]);
+        const PdS e = pds_elem(sc[r], dp[r], on, c1, ls[r], p.scale, dl4[r]);
+        pr[j][r] = e.p;
+        ds[j][r] = e.ds;
       }
     }
     const bf16x8_t pf0 = pack_p(pr[0], pr[1]), pf1 = pack_p(pr[2], pr[3]);
@@ -1340,8 +1286,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(AttnArgs p) {
     }
     qt = qn;
   }
-  // wave-private transpose through LDS (the ring is dead once every wave is past its last tile): [16 keys][128 d] fp32 per
-  // tensor, then every atomic instruction covers 64 consecutive floats of one key row
+  // attn_bwd_dkv_kernel<true>'s epilogue on the ring (dead once every wave is past its last tile) -- change both together
   __syncthreads();
   float* tw = reinterpret_cast<float*>(ring) + wave * (16 * 132);
   const int ldws = 2 * p.HKV * HD;
